@@ -14,6 +14,10 @@ Adam step + 80 value Adam steps (the reference REINFORCE.train_model, REINFORCE.
 with one RCCL all-reduce of the flat gradient per optimiser step across ranks.  Nothing is
 skipped inside the timed region.  Weak scaling: per-GPU envs are fixed as N grows.
 
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs DIR`` if asked and
+prints the record.  Everything below -- and the phase timing, host-env path, Pong A2C,
+convergence and actor-learner measurements -- runs after the timed steps with ``--full`` only.
+
 BASELINE.md: the reference publishes no numbers, so ``vs_baseline`` is null.  The second
 half of the metric, wall-clock to CartPole-v1 solved (mean return of the newest >= 100
 episodes >= 475), is measured through the reference API -- the clock starts at
@@ -42,6 +46,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement (phase timing, host-env "
+                         "path, Pong A2C, convergence presets, the actor-learner phase, time to threshold, the "
+                         "reference-equivalent CPU run); without it the run warms up, times --steps epochs and "
+                         "prints the headline record, and the options of those measurements have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed epoch left (policy / value parameters, "
+                         "episode statistics, env state, a fixed seeded sample of env columns of the rollout "
+                         "buffers) as DIR/<name>.npy; rank r > 0 writes <name>.rank<r>.npy")
     ap.add_argument("--num-envs", type=int, default=32768, help="envs per GPU")
     ap.add_argument("--rollout-len", type=int, default=64)
     ap.add_argument("--no-baseline", action="store_true", help="REINFORCE without the value baseline")
@@ -329,6 +342,45 @@ def convergence_probe(seeds: int, budget_s: float) -> dict:
     return out
 
 
+# ---------------------------------------------------------------------- outputs of the timed path
+DUMP_ENV_COLUMNS = 1024  # env columns kept of each time-major rollout buffer (all of them if fewer)
+
+
+def dump_outputs(tr, out_dir: str, rank: int) -> None:
+    """What the last timed epoch left in the trainer, one ``<name>.npy`` each (float32; integer
+    tensors as float64): the updated policy / value parameters, the epoch's episode statistics,
+    the env state the next rollout starts from, and the rollout the epoch learned from.  The
+    time-major rollout buffers (T x N ...) keep a fixed sample of env columns -- the same sorted
+    indices in every run (seed 0) -- so the whole dump stays a few MB at any --num-envs.  Weights,
+    env streams and action sampling are seeded by the trainer config, so two runs with the same
+    arguments start from identical inputs."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    learner = tr.learner
+    arrays = {"pi_params": learner.pi.params, "vf_params": None if learner.vf is None else learner.vf.params}
+    for name, attr in (("ep_stats", "ep_stats"), ("env_state", "state"), ("ep_len", "ep_len"), ("ep_ret", "ep_ret")):
+        arrays[name] = getattr(tr, attr, None)
+    n = tr.cfg.num_envs
+    cols = None
+    if n > DUMP_ENV_COLUMNS:
+        cols = np.sort(np.random.default_rng(0).choice(n, DUMP_ENV_COLUMNS, replace=False))
+        arrays["env_columns"] = torch.from_numpy(cols)
+    for name in ("obs", "act", "logp", "rew", "done"):
+        t = getattr(tr, name, None)
+        if torch.is_tensor(t) and cols is not None:
+            t = t[:, torch.from_numpy(cols).to(t.device)]
+        arrays[name] = t
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, t in arrays.items():
+        if not torch.is_tensor(t):
+            continue
+        a = t.detach().cpu()
+        a = a.float() if a.is_floating_point() else a.double()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.numpy())
+
+
 # ---------------------------------------------------------------------- comm-phase observability
 def phase_probe(tr, comm, steps: int) -> dict:
     """``steps`` more epochs with the trainer's HIP-event PhaseTimer on (after the timed
@@ -459,6 +511,11 @@ def _arm_deadline(seconds: float, rank: int, emit, cleanup=None):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the headline record
+        args.phase_steps = args.host_steps = args.pong_steps = 0
+        args.convergence = args.actor_learner = "off"
+        args.no_ttt = True
+        args.ref_cpu_seconds = 0.0
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
         return spawn_ranks(argv)
@@ -533,6 +590,8 @@ def main(argv=None):
     comm.all_reduce_max_(t)
     dt = float(t.item())
     m = tr.metrics()
+    if args.dump_outputs:
+        dump_outputs(tr, args.dump_outputs, rank)
     steps_per_epoch = cfg.num_envs * cfg.rollout_len * world
     value = steps_per_epoch * args.steps / dt
     per_rank = comm.all_gather_object(round(cfg.num_envs * cfg.rollout_len * args.steps / dt_local, 1))

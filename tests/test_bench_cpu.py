@@ -19,7 +19,7 @@ def _run(args, env_extra=None, timeout=300):
 
 
 def test_bench_spawns_ranks_without_torchrun():
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--device", "cpu", "--num-envs", "16",
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--device", "cpu", "--num-envs", "16",
               "--rollout-len", "8", "--vf-iters", "2"], {"RRL_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -45,6 +45,33 @@ def test_bench_spawns_ranks_without_torchrun():
     assert len(vers) == 2 and vers[0] - vers[1] == 1  # own rollout on v_k, the remote actor's on v_{k-1}
 
 
+def test_bench_plain_run_times_the_steps_only_and_dumps_outputs(tmp_path):
+    """Without --full the record is the headline alone (no secondary phase, even at world 2), and
+    --dump-outputs writes the trainer's parameters after the last timed step; the same arguments
+    start from the same inputs, so two runs agree to fp32 rounding, and another --steps does not."""
+    import numpy as np
+
+    small = ["--warmup", "1", "--device", "cpu", "--num-envs", "16", "--rollout-len", "8", "--vf-iters", "2"]
+    r = _run(["--gpus", "2", "--steps", "2"] + small, {"RRL_DIST_BACKEND": "gloo"})
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = _line(r)
+    assert rec["n_gpus"] == 2 and rec["steps"] == 2 and rec["value"] > 0 and rec["ms_per_step"] > 0
+    for k in ("phase_ms_per_step", "actor_learner", "time_to_threshold_s", "reference_equivalent_cpu"):
+        assert k not in rec, k
+    dumps = []
+    for name, steps in (("a", "2"), ("b", "2"), ("c", "3")):
+        r = _run(["--gpus", "1", "--steps", steps, "--dump-outputs", str(tmp_path / name)] + small)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert _line(r)["steps"] == int(steps)
+        dumps.append({p.name: np.load(p) for p in (tmp_path / name).iterdir()})
+    a, b, c = dumps
+    assert set(a) == set(b) == {"pi_params.npy", "vf_params.npy"}
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all()
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6)
+        assert not np.array_equal(a[k], c[k])  # --steps sets how many epochs ran
+
+
 def test_bench_rejects_world_size_mismatch():
     r = _run(["--gpus", "2", "--device", "cpu"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"}, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
@@ -54,7 +81,7 @@ def test_bench_actor_learner_deadline_keeps_the_headline():
     """A secondary phase that overruns its deadline (a hung transfer) still yields ONE JSON line
     with the headline and the phase marked failed, and the run exits NON-zero (bench.DEADLINE_EXIT
     on every rank) so torchrun / CI see the hang."""
-    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--device", "cpu", "--num-envs", "16",
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--device", "cpu", "--num-envs", "16",
               "--rollout-len", "8", "--vf-iters", "2", "--phase-steps", "0", "--al-steps", "100000",
               "--al-deadline-s", "3"], {"RRL_DIST_BACKEND": "gloo"})
     assert r.returncode != 0, r.stderr[-3000:]

@@ -32,7 +32,7 @@ def _json_lines(out):
 
 
 def test_bench_single_gpu_contract(cuda):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--num-envs", "2048",
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--full", "--num-envs", "2048",
                         "--vf-iters", "4", "--ttt-seeds", "1", "--ttt-ref-seeds", "1", "--ref-cpu-seconds", "0",
                         "--convergence", "off"],
                        cwd=REPO, capture_output=True, text=True, timeout=110)
@@ -48,12 +48,46 @@ def test_bench_single_gpu_contract(cuda):
     assert "time_to_threshold_s" in rec  # the second half of the metric, on by default on one GPU
 
 
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(cuda, tmp_path):
+    """Without --full: warm-up, the timed steps and the record -- no secondary measurement -- and
+    --dump-outputs writes what the last timed epoch left as float32 / float64 .npy files."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--num-envs",
+                        "2048", "--vf-iters", "4", "--dump-outputs", str(out)],
+                       cwd=REPO, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-3000:]
+    recs = _json_lines(r.stdout)
+    assert len(recs) == 1
+    rec = recs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 2 and rec["value"] > 0 and rec["ms_per_step"] > 0
+    # ms_per_step is the time of one timed step (rounded to 1 us: < 1 % of an epoch of >= 0.1 ms)
+    assert rec["value"] == pytest.approx(2048 * 64 / (rec["ms_per_step"] * 1e-3), rel=1e-2)
+    for k in ("time_to_threshold_s", "phase_ms_per_step", "host_env_path", "pong_a2c", "pong_a2c_big", "convergence",
+              "actor_learner", "reference_equivalent_cpu"):
+        assert k not in rec, k
+    arrays = {p.name[:-4]: np.load(p) for p in out.iterdir()}
+    assert {"pi_params", "vf_params", "ep_stats", "env_state", "ep_len", "ep_ret", "env_columns", "obs", "act",
+            "logp", "rew", "done"} == set(arrays)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) < 64 << 20
+    cols = arrays["env_columns"]
+    assert cols.shape == (1024,) and (np.diff(cols) > 0).all() and cols[-1] < 2048
+    assert arrays["obs"].shape == (65, 1024, 4) and arrays["logp"].shape == (64, 1024)
+    assert arrays["env_state"].shape[0] == 2048
+    # the sampled columns are the rollout the epoch learned from: CartPole pays 1 per step
+    assert (arrays["rew"] == 1.0).all() and set(np.unique(arrays["act"])) <= {0.0, 1.0}
+
+
 def test_bench_two_ranks_gloo_shared_gpu(cuda):
     env = dict(os.environ, RRL_DIST_BACKEND="gloo", RRL_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", "bench.py", "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--num-envs", "1024", "--vf-iters", "4", "--al-num-envs", "256", "--al-rollout-len", "32",
-           "--al-vf-iters", "8", "--multi-ttt-seeds", "1", "--ttt-max-s", "15"]
+           "--warmup", "1", "--full", "--num-envs", "1024", "--vf-iters", "4", "--al-num-envs", "256",
+           "--al-rollout-len", "32", "--al-vf-iters", "8", "--multi-ttt-seeds", "1", "--ttt-max-s", "15"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=115)
     assert r.returncode == 0, r.stderr[-3000:]
     recs = _json_lines(r.stdout)

@@ -10,6 +10,7 @@ from relayrl_prototype_amd.config import (
     ConfigLoader,
     resolve_config_json_path,
 )
+from tests import reference_fixtures
 
 
 @pytest.fixture
@@ -71,22 +72,13 @@ def test_missing_sections_individual_fallbacks(tmpcwd):
 
 
 def test_top_level_tensorboard_block_accepted(tmpcwd):
-    ref_default = "/root/reference/relayrl_framework/src/default_config.json"
-    if os.path.exists(ref_default):
-        text = open(ref_default).read()
-    else:
-        cfg = json.loads(DEFAULT_CONFIG_CONTENT)
-        cfg["training_tensorboard"] = cfg.pop("tensorboard")["training_tensorboard"]
-        text = json.dumps(cfg)
-    (tmpcwd / "d.json").write_text(text)
+    (tmpcwd / "d.json").write_text(open(reference_fixtures.DEFAULT_CONFIG).read())  # the reference's own default
     c = ConfigLoader("REINFORCE", str(tmpcwd / "d.json"))
     assert c.get_tb_params()["scalar_tags"] == ["AverageEpRet", "LossQ"]
 
 
 def test_example_configs_load(tmpcwd):
-    base = "/root/reference/examples"
-    if not os.path.isdir(base):
-        pytest.skip("reference examples not mounted")
+    base = reference_fixtures.EXAMPLES  # the relayrl_config.json of every reference example
     n = 0
     for root, _, files in os.walk(base):
         for f in files:

@@ -8,7 +8,6 @@ the reference's own shipped ``client_model.pt`` (read as zip storages, never unp
 Parity against the real Rust server stays unpinned: it cannot be built here.
 """
 import json
-import os
 import socket
 import threading
 import time
@@ -21,7 +20,7 @@ from relayrl_prototype_amd.api.agent import RelayRLAgent
 from relayrl_prototype_amd.config import DEFAULT_CONFIG_CONTENT
 from relayrl_prototype_amd.transport import serde_pickle as sp
 
-REF_PT = "/root/reference/examples/REINFORCE_with_baseline/classic_control/cartpole/zmq/client_model.pt"
+from tests import reference_fixtures
 
 
 def _port():
@@ -118,11 +117,11 @@ class ScriptedReferenceServer:
         self.pull.close()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PT), reason="reference checkout not mounted")
 def test_reference_wire_against_scripted_reference_server(tmp_path, monkeypatch):
     monkeypatch.setenv("RRL_QUIET_CONFIG", "1")
     cfg, path = _config(tmp_path)
-    srv = ScriptedReferenceServer(cfg, open(REF_PT, "rb").read())
+    ref_pt = reference_fixtures.client_model_file(tmp_path)  # the reference's shipped weights
+    srv = ScriptedReferenceServer(cfg, open(ref_pt, "rb").read())
     agent = None
     try:
         agent = RelayRLAgent(config_path=path, server_type="zmq", wire_format="reference", seed=0)
@@ -133,7 +132,7 @@ def test_reference_wire_against_scripted_reference_server(tmp_path, monkeypatch)
         assert (p.obs_dim, p.act_dim, p.hidden) == (4, 2, 128) and p.vf is None
         from relayrl_prototype_amd.utils.checkpoint import import_reference_weights
 
-        pi_ref, _ = import_reference_weights(REF_PT, 4, 2)
+        pi_ref, _ = import_reference_weights(ref_pt, 4, 2)
         x = np.array([0.1, -0.2, 0.3, 0.05], np.float32)
         np.testing.assert_allclose(np.asarray(p.logits(x)).reshape(-1), _logits(pi_ref, x), rtol=1e-5, atol=1e-5)
         # one 5-step episode -> one serde_pickle(Vec<RelayRLAction>) frame

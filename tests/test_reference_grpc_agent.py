@@ -11,7 +11,6 @@ The message classes are the hand-built descriptors of rf/proto/relayrl_grpc.prot
 built here.
 """
 import json
-import os
 import socket
 import threading
 from concurrent import futures
@@ -23,7 +22,8 @@ from relayrl_prototype_amd import _native
 from relayrl_prototype_amd.api.agent import RelayRLAgent
 from relayrl_prototype_amd.config import DEFAULT_CONFIG_CONTENT
 from relayrl_prototype_amd.transport.grpc_transport import (SERVICE, PbModel, PbRequest, PbResponse, PbTrajectory)
-from tests.test_reference_agent import REF_PT, _logits, _our_archive
+from tests import reference_fixtures
+from tests.test_reference_agent import _logits, _our_archive
 
 grpc = pytest.importorskip("grpc")
 
@@ -77,7 +77,6 @@ class ScriptedReferenceGrpcServer:
         self.server.stop(0.2).wait(5)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PT), reason="reference checkout not mounted")
 def test_reference_grpc_wire_against_scripted_server(tmp_path, monkeypatch):
     monkeypatch.setenv("RRL_QUIET_CONFIG", "1")
     cfg = json.loads(DEFAULT_CONFIG_CONTENT)
@@ -86,7 +85,8 @@ def test_reference_grpc_wire_against_scripted_server(tmp_path, monkeypatch):
     path = tmp_path / "relayrl_config.json"
     path.write_text(json.dumps(cfg))
     update, pi_new = _our_archive(9, with_vf=True)
-    srv = ScriptedReferenceGrpcServer(port, open(REF_PT, "rb").read(), update)
+    ref_pt = reference_fixtures.client_model_file(tmp_path)  # the reference's shipped weights
+    srv = ScriptedReferenceGrpcServer(port, open(ref_pt, "rb").read(), update)
     agent = None
     try:
         agent = RelayRLAgent(config_path=str(path), server_type="grpc", wire_format="reference", seed=0,
@@ -97,7 +97,7 @@ def test_reference_grpc_wire_against_scripted_server(tmp_path, monkeypatch):
         assert (p.obs_dim, p.act_dim, p.hidden) == (4, 2, 128) and p.vf is None
         from relayrl_prototype_amd.utils.checkpoint import import_reference_weights
 
-        pi_ref, _ = import_reference_weights(REF_PT, 4, 2)
+        pi_ref, _ = import_reference_weights(ref_pt, 4, 2)
         x = np.array([0.1, -0.2, 0.3, 0.05], np.float32)
         np.testing.assert_allclose(np.asarray(p.logits(x)).reshape(-1), _logits(pi_ref, x), rtol=1e-5, atol=1e-5)
         v0 = agent.model_version

@@ -9,8 +9,7 @@ import torch
 from relayrl_prototype_amd.utils.checkpoint import import_reference_weights, load_checkpoint, save_checkpoint
 from relayrl_prototype_amd.utils.logger import EpochLogger, read_progress, setup_logger_kwargs
 from relayrl_prototype_amd.utils.tensorboard import EventWriter, ProgressTensorboard, crc32c, read_events
-
-REF_CKPT = "/root/reference/examples/REINFORCE_without_baseline/classic_control/cartpole/zmq/client_model.pt"
+from tests import reference_fixtures
 
 
 def test_crc32c_known_vector():
@@ -35,11 +34,7 @@ def test_epoch_logger_progress_format(tmp_path):
 
 
 def test_reference_progress_parses():
-    p = ("/root/reference/examples/REINFORCE_without_baseline/box2d/lunar_lander/grpc/logs/relayrl-reinforce-info/"
-         "relayrl-reinforce-info_s298690001/progress.txt")
-    if not os.path.exists(p):
-        pytest.skip("reference not mounted")
-    cols = read_progress(p)
+    cols = read_progress(reference_fixtures.PROGRESS)  # as the reference's logger wrote it
     assert len(cols["Epoch"]) == 118 and "DeltaLossPi" in cols
 
 
@@ -52,11 +47,11 @@ def test_checkpoint_roundtrip(tmp_path):
     assert back["cfg"]["name"] == "x"
 
 
-def test_import_reference_weights_without_unpickling():
-    if not os.path.exists(REF_CKPT):
-        pytest.skip("reference not mounted")
-    pi, vf = import_reference_weights(REF_CKPT, 4, 2, 128)
+def test_import_reference_weights_without_unpickling(tmp_path):
+    # the reference's shipped CartPole weights in a PolicyWithoutBaseline archive (tests/reference_fixtures.py)
+    pi, vf = import_reference_weights(reference_fixtures.client_model_file(tmp_path), 4, 2, 128)
     assert pi.size == 17410 and vf is None and np.isfinite(pi).all()
+    assert np.array_equal(pi, reference_fixtures.client_model_pi())
     from relayrl_prototype_amd.models.cpu_policy import CPUPolicy
 
     p = CPUPolicy(4, 2, 128, True, pi)

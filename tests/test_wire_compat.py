@@ -22,7 +22,7 @@ from relayrl_prototype_amd import _native
 from relayrl_prototype_amd.transport import serde_pickle as sp
 from relayrl_prototype_amd.types import RelayRLAction, tensordata_json
 
-REF_MODEL = "/root/reference/examples/REINFORCE_without_baseline/classic_control/cartpole/zmq/client_model.pt"
+from tests import reference_fixtures
 
 
 # ---------------------------------------------------------------------- serde_pickle frames
@@ -352,7 +352,6 @@ def _members(path_or_bytes):
     return z.namelist()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MODEL), reason="reference checkout not present")
 def test_torchscript_archive_layout_matches_reference(tmp_path):
     import subprocess
     import sys
@@ -364,7 +363,7 @@ def test_torchscript_archive_layout_matches_reference(tmp_path):
         os.path.dirname(os.path.dirname(os.path.abspath(__file__))), str(tmp_path / "server_model.pt"))
     subprocess.run([sys.executable, "-c", code], check=True)
     ours = _members(str(tmp_path / "server_model.pt"))
-    ref = _members(REF_MODEL)
+    ref = reference_fixtures.client_model_members()  # of the client_model.pt the reference's examples ship
     assert "server_model/code/__torch__/REINFORCE/kernel.py" in ours
     assert {m for m in ours if "/code/" in m} == {m for m in ref if "/code/" in m}
     assert {m for m in ours if "/data/" in m} == {m for m in ref if "/data/" in m}  # W1 b1 W2 b2 W3 b3
