@@ -32,10 +32,18 @@
 // reduced over the 8 waves through LDS.  4 workgroup barriers per slab.  The same body serves
 // the value step and the policy steps (categorical and Gaussian heads, PG and PPO).
 //
+// The CartPole value step (factored head, DP = 4, variant V = 7) runs a shorter slab: top
+// barrier, forward loop, head barrier, dh1 loop, dW2 loop.  Layer 1 of the workgroup's NEXT
+// slab is computed between the forward loop's MFMAs into the second of two h1 images, which
+// takes the dh2 image's place (dW2's A fragments are built in registers from mask bits and the
+// rows' dout pieces): no layer-1 phase, 2 workgroup barriers per slab (docs/KERNELS.md).
+//
 // Measured (tools/kbench.py grad, B = 2,097,152 rows, CartPole D = 4): 1.06 ms vs 1.91 ms for
 // the fp32-MFMA kernel.  A ds_bpermute-based reduce-scatter gave run-to-run different dW1
 // entries in one lane at D = 4 (tests/test_value_grad_gpu.py::test_deterministic); the DPP
 // form is bitwise reproducible.
+#include <type_traits>
+
 #include "common.h"
 #include "grad_args.h"
 #include "heads.h"
@@ -109,6 +117,17 @@ constexpr int vg_total_bytes(int DP, int HEAD, int NA) {
          (vg_red_in_image(DP, NA) ? 0 : (vg_hbuf2(DP, HEAD, NA) ? 2 : 1) * vg_hbuf_bytes(HEAD, NA)) +
          vg_dtab_bytes(HEAD, NA) + vg_dw_bytes(DP, HEAD, NA);
 }
+// Variant bit 2 (layer 1 pipelined: the DP = 4 value head, see the kernel): the dh2 image's
+// space is the second h1 image, and after everything else come a third x slab, each wave's
+// relu'(h2) bits of its own 16 features [8 waves][64 rows] (16 bits a row) and the slab's dout
+// pieces [3][64 rows] bf16.
+constexpr bool vg_pipe(int DP, int HEAD, int V) { return HEAD == HEAD_VALUE_MSE && DP == 4 && (V & 7) == 7; }
+constexpr int vg_pipe_bytes(int DP, int HEAD, int V) {
+  return vg_pipe(DP, HEAD, V) ? 64 * DP * 4 + 8 * 64 * 2 + 3 * 64 * 2 : 0;
+}
+static_assert(vg_total_bytes(4, HEAD_VALUE_MSE, 1) % 16 == 0 &&
+                  vg_total_bytes(4, HEAD_VALUE_MSE, 1) + vg_pipe_bytes(4, HEAD_VALUE_MSE, 7) <= 160 * 1024,
+              "pipelined layer-1 LDS plan");
 static_assert(vg_red_bytes(6) + vg_hbuf_bytes(HEAD_PPO_GAUSS, 6) <= 3 * kVgImg * 2, "head inputs in the dh2 image");
 static_assert(vg_total_bytes(8, HEAD_VALUE_MSE, 1) <= 160 * 1024, "factored LDS plan");
 static_assert(vg_total_bytes(4, HEAD_PG_CAT, 2) <= 160 * 1024 && vg_total_bytes(4, HEAD_PPO_CAT, 2) <= 160 * 1024,
@@ -366,10 +385,13 @@ RRL_DEV float wave_sum_vl(float v) {
 // tune bit 7, V = tune bits 4..6, tools/kbench.py --tunes): bit 0 = dh1 from the mask table without the dh2 barrier
 // (else from the hi piece of dh2', rescaled by dout / hi(dout), after a barrier); bit 1 (with
 // bit 0) = the dh2 tiles' vector work runs between dh1's MFMAs and dW1's between dW2's, so each
-// wave's own matrix instructions cover it (otherwise the phases run one after the other).  (A
-// bit-2 variant with fp32-MFMA dW1 at DP = 4 measured 905 vs 839 us and was removed.)
+// wave's own matrix instructions cover it (otherwise the phases run one after the other); bit 2
+// (with bits 0 and 1, value head at DP = 4: V = 7, tune 240) = layer 1 pipelined a slab ahead
+// (kPipe below).  (An earlier bit-2 variant with fp32-MFMA dW1 at DP = 4 measured 905 vs 839 us
+// and was removed.)
 // production variant per input width (DP = 8 spills 4 VGPRs with the interleave)
-constexpr int vg_prod_v(int DP) { return DP <= 4 ? 3 : 1; }
+// (DP = 4: 7 for the value head when a workgroup gets more than one slab, see launch_var)
+constexpr int vg_prod_v(int DP) { return DP <= 4 ? 7 : 1; }
 
 // FWD: the value forward only (layers 1 and 2 and the head dot product on the same
 // weight-stationary bf16x6 layout, V written to p.vout; no loss, no backward, no slabs).
@@ -405,6 +427,11 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
   constexpr bool kBin = kFactor && !kValue;
   constexpr bool kMaskB = kFactor && (V & 1);
   constexpr bool kInterleave = kMaskB && (V & 2);
+  // bit 2 (with bits 0 and 1, DP = 4 value head): layer 1 of the workgroup's NEXT slab runs
+  // between the forward MFMAs of the current one, into the other of two h1 images (the dh2'
+  // image's space: dW2's A fragments are built in registers from the wave's mask bits and the
+  // slab's dout pieces).  No layer-1 phase and no layer-1 barrier: 2 barriers per slab.
+  constexpr bool kPipe = kInterleave && !FWD && vg_pipe(DP, HEAD, V);
   constexpr int NF = NA + 2;
   constexpr int NG = (NF + 3) / 4;  // 16-slot groups (one register each)
   constexpr bool kRedImg = vg_red_in_image(DP, NA);
@@ -428,6 +455,11 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
       reinterpret_cast<char*>(mk) + vg_mask_bytes(DP, HEAD, NA) +
       (kRedImg ? 0 : (vg_hbuf2(DP, HEAD, NA) ? 2 : 1) * vg_hbuf_bytes(HEAD, NA)));
   float* hacc = dtab + 64 * NA;  // kSplitHead: [8 waves][db3[NA], dlog_std[NA]]
+  // kPipe: the third x slab, this wave's mask-bit table and the shared dout pieces (every wave
+  // computes the same dout and stores the same pieces; each reads back after its own stores)
+  float* xs3 = reinterpret_cast<float*>(reinterpret_cast<char*>(vg_lds) + vg_total_bytes(DP, HEAD, NA));
+  uint16_t* mbt = reinterpret_cast<uint16_t*>(xs3 + 64 * DP) + 64 * (threadIdx.x >> 6);
+  uint16_t* dpt = reinterpret_cast<uint16_t*>(xs3 + 64 * DP) + 8 * 64;
   if (kSplitHead && lane_id() < 2 * NA) hacc[(threadIdx.x >> 6) * 2 * NA + lane_id()] = 0.f;
   if (kMaskB) {
     // entry i: element e (feature 8 g + e of a fragment) = 1.0 if bit e of i is set
@@ -437,6 +469,7 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
     }
   }
   int parity = 0;
+  int xi = 0;  // kPipe: the current slab's x buffer (0..2)
   constexpr int KS1 = DP / 4;
   const int l = lane_id();
   const int j = l & 15, g = l >> 4, w = threadIdx.x >> 6;
@@ -456,6 +489,15 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
   }
   const float* __restrict__ P = p.params;
   const int own = 16 * w;  // this wave's 16 hidden features
+  // kPipe: where batch row l sits in the per-row tables.  dW2's A fragment of k-chunk c holds, in
+  // lane group g, rows 32 c + 4 g + {0..3} and 32 c + 16 + 4 g + {0..3}: slot 32 c + 8 g + e, so
+  // a lane group's 8 rows are one 16-byte read.  (Recomputed where used, from a lane id the
+  // compiler cannot hoist: kept live across the slab loop these addresses were spilled.)
+  auto frag_slot = [&]() {
+    int ll = l;
+    asm volatile("" : "+v"(ll));
+    return (ll & 32) + 8 * ((ll >> 2) & 3) + ((ll >> 2) & 4) + (ll & 3);
+  };
 
   // Global inputs go straight to LDS by DMA (global_load_lds_dword: lane l's dword lands at
   // the wave-uniform destination + 4 l), so no register holds them across the slab (held in
@@ -507,6 +549,33 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
         xr[i] = p.X[(size_t)min(b, Bc - 1) * D + min(d, D - 1)];
       }
       if (!FWD) hin_r = p.ret[min(b0 + l, p.B - 1)];
+    }
+  };
+  // kPipe: three x slabs in rotation.  Layer 1 of slab s + 1 reads its x inside slab s, while
+  // dW1 of slab s - 1 may still be reading the slab before that in a slower wave, so the store
+  // at the top of slab s (before its barrier) needs a third buffer.  x is in registers two
+  // slabs ahead of its use by dW1 (one ahead of layer 1), ret one slab ahead.
+  auto xbuf = [&](int i) { return i < 2 ? xsb + i * 64 * DP : xs3; };
+  auto load_x = [&](int b0) {
+    // (addresses from a thread id the compiler cannot hoist: kept across the slab loop they were
+    // spilled, and the reload's wait also waited for the ret load just issued)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+#pragma unroll
+    for (int i = 0; i < (kDmaIn ? 1 : XQ); ++i) {
+      const int q = min(tid + 512 * i, 64 * DP - 1);
+      const int rl = q / DP, d = q % DP, b = b0 + rl;
+      xr[i] = p.X[(size_t)min(b, Bc - 1) * D + min(d, D - 1)];
+    }
+  };
+  auto store_x = [&](int b0, float* dst) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+#pragma unroll
+    for (int i = 0; i < (kDmaIn ? 1 : XQ); ++i) {
+      const int q = tid + 512 * i;
+      const int rl = q / DP, d = q % DP;
+      if (q < 64 * DP) dst[q] = (b0 + rl < Bv && d < D) ? xr[i] : 0.f;
     }
   };
   constexpr bool kHb2 = kDmaIn && vg_hbuf2(DP, HEAD, NA);
@@ -577,6 +646,11 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
       *reinterpret_cast<vbf16x4*>(w2lo + (q >> 5) * kVgLd + 4 * (q & 31)) = lo;
     }
   }
+  if constexpr (kPipe) {
+    // the first slab's x to LDS for the prologue's layer 1; the second slab's into registers
+    store_x(blockIdx.x * 64, xsb);
+    if ((int)(blockIdx.x + gridDim.x) * 64 < Bv) load_x((blockIdx.x + gridDim.x) * 64);
+  }
   __syncthreads();  // staged W2 and b1 / b2 / w3 visible
   // hi + mid pieces in registers; the lo pieces of W2 sit in the LDS image [o][i] that both
   // fragment kinds read once per 32-wide k-chunk (b128 for wA, transposed for wB)
@@ -615,6 +689,38 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
   const float* b1p = vecs + own + 4 * g;
   const float* b2p = vecs + kVgH + own + 4 * g;
   const float* w3p = vecs + 2 * kVgH + own + 4 * g;
+
+  // layer 1 of the x slab xs into the h1 image img (fp32 MFMA, relu, split)
+  auto layer1 = [&](const float* xs, uint16_t* img) {
+    // all x reads first, then the 4 tiles' MFMAs back to back, then relu + split + stores
+    // (a read placed after the previous tile's image stores would wait for them: LDS alias)
+    float xv[4][KS1];
+#pragma unroll
+    for (int bt = 0; bt < 4; ++bt) {
+#pragma unroll
+      for (int s = 0; s < KS1; ++s) xv[bt][s] = xs[(16 * bt + j) * DP + 4 * s + g];
+    }
+    const floatx4 b1v = *reinterpret_cast<const floatx4*>(b1p);
+    floatx4 a1[4];
+#pragma unroll
+    for (int bt = 0; bt < 4; ++bt) {
+      a1[bt] = b1v;
+#pragma unroll
+      for (int s = 0; s < KS1; ++s) a1[bt] = mfma4(w1a[s], xv[bt][s], a1[bt]);
+    }
+#pragma unroll
+    for (int bt = 0; bt < 4; ++bt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a1[bt][r] = relu1(a1[bt][r]);
+      store_split(img, 16 * bt + j, own + 4 * g, a1[bt]);
+    }
+  };
+  if constexpr (kPipe) {
+    // the first slab's layer 1, once every wave has its W2 fragments out of the staging area
+    // (which covers the images); the loop's top barrier publishes it
+    __syncthreads();
+    layer1(xsb, vg_lds);
+  }
 
   floatx4 acc2[8];
   float accv[NG];      // slot j of each 16-slot group of fields (4 features each), batch-summed
@@ -675,10 +781,18 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
     VG_STAMP(0);
     // ------------------------------------------------------------ x slab (DMA'd a slab ago)
     // (double-buffered by slab parity: the next slab's DMA targets the other half)
-    float* xs = xsb + (parity & 1) * 64 * DP;
+    float* xs = kPipe ? xbuf(xi) : xsb + (parity & 1) * 64 * DP;
     float* hbuf = hbuf0 + (kHb2 ? (parity & 1) * HBF : 0);
+    // kPipe: this slab's h1 image (written a slab ago) and the one its look-ahead fills
+    uint16_t* const h1s = kPipe ? vg_lds + (parity & 1) * 3 * kVgImg : h1img;
+    uint16_t* const h1n = vg_lds + ((parity & 1) ^ 1) * 3 * kVgImg;
+    const int xin = xi == 2 ? 0 : xi + 1;
+    const float* xsn = xbuf(xin);
+    xi = xin;
     parity ^= 1;
-    if (kDmaIn) {
+    if constexpr (kPipe) {
+      store_x(base + (int)gridDim.x * 64, xbuf(xin));  // the next slab's x, for its layer 1 below
+    } else if (kDmaIn) {
       vm_wait0();
     } else {
 #pragma unroll
@@ -692,31 +806,11 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
     VG_STAMP(1);
 
     // ------------------------------------------------------------ layer 1 (fp32 MFMA)
-    {
-      // all x reads first, then the 4 tiles' MFMAs back to back, then relu + split + stores
-      // (a read placed after the previous tile's image stores would wait for them: LDS alias)
-      float xv[4][KS1];
-#pragma unroll
-      for (int bt = 0; bt < 4; ++bt) {
-#pragma unroll
-        for (int s = 0; s < KS1; ++s) xv[bt][s] = xs[(16 * bt + j) * DP + 4 * s + g];
-      }
-      const floatx4 b1v = *reinterpret_cast<const floatx4*>(b1p);
-      floatx4 a1[4];
-#pragma unroll
-      for (int bt = 0; bt < 4; ++bt) {
-        a1[bt] = b1v;
-#pragma unroll
-        for (int s = 0; s < KS1; ++s) a1[bt] = mfma4(w1a[s], xv[bt][s], a1[bt]);
-      }
-#pragma unroll
-      for (int bt = 0; bt < 4; ++bt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) a1[bt][r] = relu1(a1[bt][r]);
-        store_split(h1img, 16 * bt + j, own + 4 * g, a1[bt]);
-      }
+    // (kPipe: done a slab ago, between that slab's forward MFMAs)
+    if constexpr (!kPipe) {
+      layer1(xs, h1img);
+      __syncthreads();
     }
-    __syncthreads();
     // this slab's head inputs (not double-buffered): issued after layer 1's barrier, which would
     // otherwise wait for them (vmcnt 0), and landed behind layer 2 (vm_wait0 before the head's)
     if (kDmaIn && !kHb2) dma_head(base, hbuf);
@@ -726,7 +820,79 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
     floatx4 h2[4];
 #pragma unroll
     for (int bt = 0; bt < 4; ++bt) h2[bt] = *reinterpret_cast<const floatx4*>(b2p);
-    {
+    if constexpr (kPipe) {
+      // The 16 steps (c, bt) of the loop below, with layer 1 of the workgroup's next slab in the
+      // vector-issue slots between their MFMAs (a 16x16x32 MFMA holds the issue port for half
+      // its 16 cycles: two slots per MFMA).  Batch tile t takes steps 4 t .. 4 t + 3: its x and
+      // b1 reads, its fp32 MFMA (after the step's six), then relu and split of two features in
+      // each of two steps and the tile's 3 image stores into the OTHER image.  The next step's
+      // operand reads are pinned to the top of the step, a full step ahead of their use.
+      auto fwd_steps = [&](auto look) {
+        constexpr bool kLook = decltype(look)::value;
+        // (lane indices the compiler cannot hoist: the look-ahead's LDS addresses are rebuilt per
+        // slab instead of being carried, and spilled, across the slab loop)
+        int tf = threadIdx.x;
+        asm volatile("" : "+v"(tf));
+        const int jl = tf & 15, gl = (tf >> 4) & 3, ownl = 16 * (tf >> 6);
+        const float* b1l = vecs + ownl + 4 * gl;
+        Split8 cur = frag_row(h1s, j, 8 * g);
+        vbf16x8 al = *reinterpret_cast<const vbf16x8*>(w2lo + (own + j) * kVgLd + 8 * g);
+        float xv;
+        floatx4 t1;
+        uint32_t ph[2], pm[2], pl[2];
+        auto store_tile = [&](int t) {
+          Pieces pc;
+          pc.h = __builtin_bit_cast(vbf16x4, make_uint2(ph[0], ph[1]));
+          pc.m = __builtin_bit_cast(vbf16x4, make_uint2(pm[0], pm[1]));
+          pc.l = __builtin_bit_cast(vbf16x4, make_uint2(pl[0], pl[1]));
+          store_pieces(h1n, 16 * t + jl, ownl + 4 * gl, pc);
+        };
+#pragma unroll
+        for (int it = 0; it < 16; ++it) {
+          const int c = it >> 2, bt = it & 3;
+          Split8 nxt;
+          vbf16x8 aln;
+          if (it + 1 < 16) nxt = frag_row(h1s, 16 * ((it + 1) & 3) + j, 32 * ((it + 1) >> 2) + 8 * g);
+          if (bt == 3 && it + 1 < 16)
+            aln = *reinterpret_cast<const vbf16x8*>(w2lo + (own + j) * kVgLd + 32 * (c + 1) + 8 * g);
+          const int lt = it >> 2, ls = it & 3;  // look-ahead tile and its stage
+          if (kLook && ls == 0) {
+            xv = xsn[(16 * lt + jl) * DP + gl];
+            t1 = *reinterpret_cast<const floatx4*>(b1l);
+          }
+          if (kLook && ls == 1) t1 = mfma4(w1a[0], xv, t1);  // (first: a step of MFMAs before its result is read)
+          const Split8 a{wA[c].h, wA[c].m, al};
+          h2[bt] = mma6(a, cur, h2[bt]);
+          if (kLook && ls >= 2) {
+            const int q = ls - 2;
+            split2(vf32x2{relu1(t1[2 * q]), relu1(t1[2 * q + 1])}, ph[q], pm[q], pl[q]);
+          }
+          if (kLook && ls == 3) store_tile(lt);
+          // issue order of the step: LDS reads, the tile's fp32 MFMA, then MFMA + up to three
+          // vector instructions six times (the image stores follow)
+          if (it == 0) __builtin_amdgcn_sched_group_barrier(0x100, 10, 0);  // + the loop's first operands
+          else if (ls == 0) __builtin_amdgcn_sched_group_barrier(0x100, kLook ? 5 : 3, 0);
+          else if (ls == 3) {  // (the W2-lo read's address is rebuilt here: its three instructions first)
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+          } else {
+            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+          }
+          if (kLook && ls == 1) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+#pragma unroll
+          for (int k = 0; k < 6; ++k) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if (it + 1 < 16) cur = nxt;
+          if (bt == 3 && it + 1 < 16) al = aln;
+        }
+      };
+      // a workgroup's last slab has nothing to look ahead to (wave-uniform)
+      if (base + (int)gridDim.x * 64 < Bv) fwd_steps(std::true_type{});
+      else fwd_steps(std::false_type{});
+    } else {
       // 16 steps (c, bt); the next step's B fragment (and W2-lo piece) load before this one's MFMAs
       Split8 cur = frag_row(h1img, j, 8 * g);
       vbf16x8 al = *reinterpret_cast<const vbf16x8*>(w2lo + (own + j) * kVgLd + 8 * g);
@@ -771,6 +937,9 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
       uint8_t* mb = reinterpret_cast<uint8_t*>(mk) + (16 * g + j) * 16 + 8 * (w & 1) + (w >> 1);
       mb[0] = (uint8_t)(u & 0xffu);
       mb[4] = (uint8_t)(u >> 8);
+      // kPipe: the same 16 bits (bit f = feature own + f of row l = 16 g + j) into the wave's
+      // own table, at the row's place in dW2's A-fragment order
+      if constexpr (kPipe) mbt[frag_slot()] = (uint16_t)u;
     }
 
     VG_STAMP(3);
@@ -1002,7 +1171,17 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
       }
     };
     constexpr bool kHeadBar = kRedImg || kSplitHead;
-    if (!kHeadBar && kFactor) prefetch_next();  // (V1 / V3: no barrier before the next slab's)
+    if constexpr (kPipe) {
+      // x two slabs ahead (stored at the next slab's top for the layer 1 that runs inside it),
+      // ret one ahead
+      const int stride = (int)gridDim.x * 64;
+      if (base + stride < Bv) {
+        hin_r = p.ret[min(base + stride + l, p.B - 1)];
+        if (base + 2 * stride < Bv) load_x(base + 2 * stride);
+      }
+    } else if (!kHeadBar && kFactor) {
+      prefetch_next();  // (V1 / V3: no barrier before the next slab's)
+    }
     // every wave read the partials before dh2 overwrites them (kSplitHead: the dout table is visible)
     if (kHeadBar) {
       __syncthreads();
@@ -1022,7 +1201,7 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc) {
         typedef unsigned short vu16x8 __attribute__((ext_vector_type(8)));
-        const vu16x8 hb = __builtin_bit_cast(vu16x8, frag_tr1(h1img, 32 * cc, own, l));
+        const vu16x8 hb = __builtin_bit_cast(vu16x8, frag_tr1(h1s, 32 * cc, own, l));
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const int bt = 2 * cc + (e >> 2), i = e & 3;
@@ -1058,20 +1237,22 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
       // dh2' pieces of batch tile bt (stores) and its field partials
       auto kf_tile = [&](const int bt) {
         const float v = dv[bt];
-        // the row's dout split once: v = vh + vm + vl
-        uint32_t ph, pm, pl;
-        split2(vf32x2{v, v}, ph, pm, pl);
-        uint32_t mw[2];  // relu'(h2) of this lane's 4 features as bf16 lane masks
+        if constexpr (!kPipe) {  // (kPipe: no dh2' image, dW2 builds its A fragments itself)
+          // the row's dout split once: v = vh + vm + vl
+          uint32_t ph, pm, pl;
+          split2(vf32x2{v, v}, ph, pm, pl);
+          uint32_t mw[2];  // relu'(h2) of this lane's 4 features as bf16 lane masks
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const bool p0 = h2[bt][2 * q] > 0.f, p1 = h2[bt][2 * q + 1] > 0.f;
-          mw[q] = (p0 ? 0x0000ffffu : 0u) | (p1 ? 0xffff0000u : 0u);
+          for (int q = 0; q < 2; ++q) {
+            const bool p0 = h2[bt][2 * q] > 0.f, p1 = h2[bt][2 * q + 1] > 0.f;
+            mw[q] = (p0 ? 0x0000ffffu : 0u) | (p1 ? 0xffff0000u : 0u);
+          }
+          Pieces pc;
+          pc.h = __builtin_bit_cast(vbf16x4, make_uint2(mw[0] & ph, mw[1] & ph));
+          pc.m = __builtin_bit_cast(vbf16x4, make_uint2(mw[0] & pm, mw[1] & pm));
+          pc.l = __builtin_bit_cast(vbf16x4, make_uint2(mw[0] & pl, mw[1] & pl));
+          store_pieces(dhimg, 16 * bt + j, own + 4 * g, pc);
         }
-        Pieces pc;
-        pc.h = __builtin_bit_cast(vbf16x4, make_uint2(mw[0] & ph, mw[1] & ph));
-        pc.m = __builtin_bit_cast(vbf16x4, make_uint2(mw[0] & pm, mw[1] & pm));
-        pc.l = __builtin_bit_cast(vbf16x4, make_uint2(mw[0] & pl, mw[1] & pl));
-        store_pieces(dhimg, 16 * bt + j, own + 4 * g, pc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           tv[r] += h2[bt][r] > 0.f ? v : 0.f;
@@ -1112,10 +1293,24 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
             dh1[bt] = mfma_bf16(q0, wBl[c % (kFactor ? 4 : 1)], dh1[bt]);
             dh1[bt] = mfma_bf16(q0, wB[c].m, dh1[bt]);
             dh1[bt] = mfma_bf16(q0, wB[c].h, dh1[bt]);
+            if constexpr (kPipe) {
+              // row l's dout split once, for dW2's A fragments (mask x piece, as the dh2' image
+              // held), beside the first step's MFMAs; fenced with the dh2 tiles' work (kf_finish)
+              if (it == 0) {
+                uint32_t ph, pm, pl;
+                split2(vf32x2{dfac, dfac}, ph, pm, pl);
+                uint16_t* dp = dpt + frag_slot();
+                dp[0] = (uint16_t)ph;
+                dp[64] = (uint16_t)pm;
+                dp[128] = (uint16_t)pl;
+              }
+            }
             if (kInterleave) {  // this wave's dh2 work beside its own MFMAs
               if ((it & 3) == 1) kf_tile(it >> 2);
               if (it == 15) kf_finish();
             }
+            // (kPipe: the table read for two steps on goes out at the top of the step)
+            if constexpr (kPipe) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (kAhead == 2) {
               q0 = q1;
@@ -1345,19 +1540,45 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
     };
     // dW2 MFMAs with dW1 vector work between them (kInterleave, DP = 4): one dh1 row per
     // step, its x row read one step ahead
+    // kPipe: dW2's A fragment of k-chunk c (dh2' = mask x dout piece of feature own + j at the
+    // lane group's 8 rows) from the wave's mask-bit table and the dout pieces: bit j of a row's
+    // 16 bits spread over the row's bf16, ANDed into each piece
+    auto a_frag = [&](int c) {
+      typedef uint32_t vu32x4 __attribute__((ext_vector_type(4)));
+      const vu32x4 mb = *reinterpret_cast<const vu32x4*>(mbt + 32 * c + 8 * g);
+      const uint16_t* tp = dpt + 32 * c + 8 * g;
+      vu32x4 m;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_sbfe((int)mb[k], (uint32_t)j, 1u);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_sbfe((int)mb[k], (uint32_t)(j + 16), 1u);
+        m[k] = (lo & 0x0000ffffu) | (hi & 0xffff0000u);
+      }
+      Split8 a;
+      a.h = __builtin_bit_cast(vbf16x8, m & *reinterpret_cast<const vu32x4*>(tp));
+      a.m = __builtin_bit_cast(vbf16x8, m & *reinterpret_cast<const vu32x4*>(tp + 64));
+      a.l = __builtin_bit_cast(vbf16x8, m & *reinterpret_cast<const vu32x4*>(tp + 128));
+      return a;
+    };
     auto do_dw2_dw1 = [&]() {
       VG_STAMP(8);
       VG_STAMP(9);
-      Split8 a = frag_tr(dhimg, 0, own, l);
-      Split8 cur = frag_tr(h1img, 0, 0, l);
+      Split8 a;
+      if constexpr (kPipe) a = a_frag(0);
+      else a = frag_tr(dhimg, 0, own, l);
+      Split8 cur = frag_tr(h1s, 0, 0, l);
       floatx4 xq[DP / 4];
       load_xrow(4 * g, xq);
 #pragma unroll
       for (int it = 0; it < 16; ++it) {
         const int t = it & 7;
         Split8 nxt, an;
-        if (it + 1 < 16) nxt = frag_tr(h1img, 32 * ((it + 1) >> 3), 16 * ((it + 1) & 7), l);
-        if (it == 7) an = frag_tr(dhimg, 32, own, l);
+        if (it + 1 < 16) nxt = frag_tr(h1s, 32 * ((it + 1) >> 3), 16 * ((it + 1) & 7), l);
+        if constexpr (kPipe) {
+          if (it == 7) an = a_frag(1);
+        } else {
+          if (it == 7) an = frag_tr(dhimg, 32, own, l);
+        }
         acc2[t] = mma6(a, cur, acc2[t]);
         {
           floatx4 xc[DP / 4];
@@ -1383,100 +1604,107 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
   // ------------------------------------------------------------------ epilogue
   if constexpr (FWD) return;
   if (kTvPersist) accv[0] += fold_tvs();
-  float* slab = p.grad_slab + (size_t)blockIdx.x * p.P;
-  // kFactor: dW2 rows / db2 are w3' x the accumulated dh2' sums (w3' = w3, or w3[1] - w3[0])
-  auto w3g = [&](int f) { return kBin ? P[o.w3 + kVgH + f] - P[o.w3 + f] : P[o.w3 + f]; };
-  floatx4 w3s;
+  // (kPipe: the epilogue's lane indices from ids the compiler cannot carry across the loop,
+  // where they were spilled)
+  int te = threadIdx.x;
+  if constexpr (kPipe) asm volatile("" : "+v"(te));
+  {
+    const int l = te & 63, j = l & 15, g = l >> 4, w = te >> 6, own = 16 * w;
+    float* slab = p.grad_slab + (size_t)blockIdx.x * p.P;
+    // kFactor: dW2 rows / db2 are w3' x the accumulated dh2' sums (w3' = w3, or w3[1] - w3[0])
+    auto w3g = [&](int f) { return kBin ? P[o.w3 + kVgH + f] - P[o.w3 + f] : P[o.w3 + f]; };
+    floatx4 w3s;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) w3s[r] = kFactor ? w3g(own + 4 * g + r) : 1.f;
+    for (int r = 0; r < 4; ++r) w3s[r] = kFactor ? w3g(own + 4 * g + r) : 1.f;
 #pragma unroll
-  for (int it = 0; it < 8; ++it) {
+    for (int it = 0; it < 8; ++it) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) slab[o.w2 + (own + 4 * g + r) * kVgH + 16 * it + j] = acc2[it][r] * w3s[r];
-  }
-#pragma unroll
-  for (int q = 0; q < NG; ++q) {
-    const int f = 4 * q + (j >> 2), feat = own + 4 * g + (j & 3);
-    if (f < NF) {
-      const int off = f == 0 ? o.b2 : f == 1 ? o.w3 : f == 2 ? o.b1 : o.w3 + (f == 3 ? 1 : f - 2) * kVgH;
-      if (f != 2) slab[off + feat] = (kFactor && f == 0) ? accv[q] * w3g(feat) : accv[q];
+      for (int r = 0; r < 4; ++r) slab[o.w2 + (own + 4 * g + r) * kVgH + 16 * it + j] = acc2[it][r] * w3s[r];
     }
-  }
-  if (kDw1Mfma) {
 #pragma unroll
-    for (int nt = 0; nt < (kDw1Mfma ? NT1 : 1); ++nt) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int d = 16 * nt + j;
-        if (d < D) slab[o.w1 + (own + 4 * g + i) * D + d] = acc1m[nt][i];
+    for (int q = 0; q < NG; ++q) {
+      const int f = 4 * q + (j >> 2), feat = own + 4 * g + (j & 3);
+      if (f < NF) {
+        const int off = f == 0 ? o.b2 : f == 1 ? o.w3 : f == 2 ? o.b1 : o.w3 + (f == 3 ? 1 : f - 2) * kVgH;
+        if (f != 2) slab[off + feat] = (kFactor && f == 0) ? accv[q] * w3g(feat) : accv[q];
       }
     }
+    if (kDw1Mfma) {
 #pragma unroll
-    for (int e = 0; e < kTail1; ++e) {
-      const float sd = group_sum_swap(acc1[e % NA1]);  // over the 4 lane groups (all lanes call)
-      const int d = 16 * NT1 + e;
-      if (g == e && d < D) slab[o.w1 + (own + j) * D + d] = sd;
+      for (int nt = 0; nt < (kDw1Mfma ? NT1 : 1); ++nt) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int d = 16 * nt + j;
+          if (d < D) slab[o.w1 + (own + 4 * g + i) * D + d] = acc1m[nt][i];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < kTail1; ++e) {
+        const float sd = group_sum_swap(acc1[e % NA1]);  // over the 4 lane groups (all lanes call)
+        const int d = 16 * NT1 + e;
+        if (g == e && d < D) slab[o.w1 + (own + j) * D + d] = sd;
+      }
+    } else {
+#pragma unroll
+      for (int d = 0; d < NA1; ++d) {
+        const float sd = group_sum_swap(acc1[d]);  // over the 4 lane groups (all lanes call)
+        if (g == (d & 3) && d < D) slab[o.w1 + (own + j) * D + d] = sd;
+      }
     }
-  } else {
-#pragma unroll
-    for (int d = 0; d < NA1; ++d) {
-      const float sd = group_sum_swap(acc1[d]);  // over the 4 lane groups (all lanes call)
-      if (g == (d & 3) && d < D) slab[o.w1 + (own + j) * D + d] = sd;
+    {
+      const float sb = group_sum_swap(db1acc);
+      if (g == 0) slab[o.b1 + own + j] = sb;
     }
-  }
-  {
-    const float sb = group_sum_swap(db1acc);
-    if (g == 0) slab[o.b1 + own + j] = sb;
-  }
-  if constexpr (kSplitHead) {
-    // db3 / dlog_std: the waves' hacc slots; loss sums: lanes 8 r of every wave, folded in the
-    // wave and then over the 8 waves through LDS (fixed order)
-    const float st[6] = {wave_sum_vl(s_loss), wave_sum_vl(s_ent), wave_sum_vl(s_kl),
-                         wave_sum_vl(s_clip), wave_sum_vl(s_val), wave_sum_vl(s_cnt)};
-    __syncthreads();  // every wave is past its last dh2 phase: the dout table is free
-    float* ep = dtab;  // [8 waves][6]: loss sums
-    if (l == 0) {
+    if constexpr (kSplitHead) {
+      // db3 / dlog_std: the waves' hacc slots; loss sums: lanes 8 r of every wave, folded in the
+      // wave and then over the 8 waves through LDS (fixed order)
+      const float st[6] = {wave_sum_vl(s_loss), wave_sum_vl(s_ent), wave_sum_vl(s_kl),
+                           wave_sum_vl(s_clip), wave_sum_vl(s_val), wave_sum_vl(s_cnt)};
+      __syncthreads();  // every wave is past its last dh2 phase: the dout table is free
+      float* ep = dtab;  // [8 waves][6]: loss sums
+      if (l == 0) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) ep[w * 6 + k] = st[k];
+        for (int k = 0; k < 6; ++k) ep[w * 6 + k] = st[k];
+      }
+      __syncthreads();
+      const int t = threadIdx.x;
+      if (t < 2 * NA) {
+        float v = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < 8; ++ww) v += hacc[ww * 2 * NA + t];
+        slab[(t < NA ? o.b3 : o.log_std - NA) + t] = v;
+      } else if (t >= 64 && t < 70) {
+        float v = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < 8; ++ww) v += ep[ww * 6 + t - 64];
+        p.loss_slab[blockIdx.x * 8 + t - 64] = v;
+      }
     }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < 2 * NA) {
-      float v = 0.f;
-#pragma unroll
-      for (int ww = 0; ww < 8; ++ww) v += hacc[ww * 2 * NA + t];
-      slab[(t < NA ? o.b3 : o.log_std - NA) + t] = v;
-    } else if (t >= 64 && t < 70) {
-      float v = 0.f;
-#pragma unroll
-      for (int ww = 0; ww < 8; ++ww) v += ep[ww * 6 + t - 64];
-      p.loss_slab[blockIdx.x * 8 + t - 64] = v;
+    if (!kSplitHead && w < NA && l == 0) {
+      slab[o.b3 + w] = bacc3;
+      if (kGauss) slab[o.log_std + w] = dls;
     }
-  }
-  if (!kSplitHead && w < NA && l == 0) {
-    slab[o.b3 + w] = bacc3;
-    if (kGauss) slab[o.log_std + w] = dls;
-  }
-  if (!kSplitHead && w == 0) {
-    const float sl = wave_sum(s_loss), sv = wave_sum(s_val), sc = wave_sum(s_cnt);
-    const float se = wave_sum(s_ent), sk = wave_sum(s_kl), scl = wave_sum(s_clip);
-    if (l == 0) {
-      float* lsl = p.loss_slab + blockIdx.x * 8;
-      lsl[0] = sl;
-      lsl[1] = se;
-      lsl[2] = sk;
-      lsl[3] = scl;
-      lsl[4] = sv;
-      lsl[5] = sc;
+    if (!kSplitHead && w == 0) {
+      const float sl = wave_sum(s_loss), sv = wave_sum(s_val), sc = wave_sum(s_cnt);
+      const float se = wave_sum(s_ent), sk = wave_sum(s_kl), scl = wave_sum(s_clip);
+      if (l == 0) {
+        float* lsl = p.loss_slab + blockIdx.x * 8;
+        lsl[0] = sl;
+        lsl[1] = se;
+        lsl[2] = sk;
+        lsl[3] = scl;
+        lsl[4] = sv;
+        lsl[5] = sc;
+      }
     }
-  }
-  if (STAMP && p.stamps != nullptr) {
-    unsigned long long t_end;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_end)::"memory");
-    st_sum[11] = t_end - st_prev;
-    if (l == 0) {
+    if (STAMP && p.stamps != nullptr) {
+      unsigned long long t_end;
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_end)::"memory");
+      st_sum[11] = t_end - st_prev;
+      if (l == 0) {
 #pragma unroll
-      for (int k = 0; k < 12; ++k) p.stamps[(blockIdx.x * 8 + w) * 16 + k] = st_sum[k];
+        for (int k = 0; k < 12; ++k) p.stamps[(blockIdx.x * 8 + w) * 16 + k] = st_sum[k];
+      }
     }
   }
 }
@@ -1497,7 +1725,7 @@ static unsigned long long* g_vg_stamps = nullptr;
 
 template <int DP, int HEAD, int NA, bool STAMP, int V>
 static int launch_inst(const GradArgs& a, int grid, hipStream_t s) {
-  constexpr int bytes = vg_total_bytes(DP, HEAD, NA);
+  constexpr int bytes = vg_total_bytes(DP, HEAD, NA) + vg_pipe_bytes(DP, HEAD, V);
   static_assert(bytes <= 160 * 1024, "value-grad LDS plan exceeds 160 KB");
   static bool attr_set = false;
   if (!attr_set) {
@@ -1517,9 +1745,17 @@ static int launch_var(const GradArgs& a, int grid, hipStream_t s) {
         case 0: return launch_inst<DP, HEAD, NA, STAMP, 0>(a, grid, s);
         case 1: return launch_inst<DP, HEAD, NA, STAMP, 1>(a, grid, s);
         case 3: return launch_inst<DP, HEAD, NA, STAMP, 3>(a, grid, s);
+        case 7:  // layer 1 pipelined: DP = 4 only
+          if constexpr (DP == 4) return launch_inst<DP, HEAD, NA, STAMP, 7>(a, grid, s);
+          break;
         default: break;
       }
     }
+  }
+  // One slab per workgroup leaves the pipelined variant nothing to look ahead to, and its
+  // prologue is longer (8,192 rows: 14.2 vs 14.1 us): V = 3 there.
+  if constexpr (vg_pipe(DP, HEAD, vg_prod_v(DP))) {
+    if ((long)a.B <= 64L * grid) return launch_inst<DP, HEAD, NA, STAMP, 3>(a, grid, s);
   }
   return launch_inst<DP, HEAD, NA, STAMP, vg_prod_v(DP)>(a, grid, s);
 }

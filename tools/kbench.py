@@ -96,7 +96,10 @@ def main():
         if a.tunes:
             for t in [int(x) for x in a.tunes.split(",")]:
                 old_t = hip().set_value_grad_tune(t)
-                res[f"value_grad_tune{t}_us"] = timeit(
+                key, n = f"value_grad_tune{t}_us", 2
+                while key in res:  # a tune listed again (e.g. 176,240,176,240): another round of it
+                    key, n = f"value_grad_tune{t}_r{n}_us", n + 1
+                res[key] = timeit(
                     lambda: mlp_grad(GradHead.VALUE_MSE, pv, X, 1, H, ret=ret, grad_slab=slab, loss_slab=ls), a.iters)
                 hip().set_value_grad_tune(old_t)
         old = hip().set_value_grad_mode(0)  # the fp32-MFMA kernel, for comparison
