@@ -43,6 +43,11 @@ int rrl_adam(float* param, float* m, float* v, const float* grad, const float* s
              float* grad_out, int* step, unsigned* ticket, int P, float lr, float beta1, float beta2,
              float eps, float grad_scale, float weight_decay, int step_add, int step_inc, void* stream);
 int rrl_reduce_slabs(const float* slab, int nslab, int P, float scale, float* out, void* stream);
+int rrl_payload_checksum_blocks(const unsigned long long* words, int nseg, int num_cu);
+int rrl_payload_checksum(const void* const* ptrs, const unsigned long long* words, int nseg,
+                         unsigned long long* part, unsigned long long* out, int num_cu, void* stream);
+int rrl_payload_verify(const unsigned long long* sums, const double* hdr, int ld, int ck_col, int K,
+                       double expected_seq, double lo, double hi, int* status, void* stream);
 int rrl_env_dims(int env, int* D, int* A, int* NS, int* max_steps);
 int rrl_rollout_cont(int env, const float* params, const float* env_consts, int N, int T, int H, float* state,
                      int* ep_len, float* ep_ret, float* obs_buf, float* act_buf, float* logp_buf, float* rew_buf,
@@ -334,6 +339,51 @@ void reduce_slabs(const Tensor& slab, double scale, const Tensor& out) {
            "reduce_slabs");
 }
 
+// (s1, s2) over the bit patterns of up to 8 contiguous segments, in order (checksum.hip).
+void payload_checksum(const std::vector<Tensor>& segments, const Tensor& out) {
+  TORCH_CHECK(segments.size() <= 8, "payload_checksum: at most 8 segments, got ", segments.size());
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kLong && out.numel() == 2 && out.is_contiguous(),
+              "payload_checksum: out must be a contiguous int64[2] device tensor");
+  const void* ptrs[8];
+  unsigned long long words[8];
+  for (size_t s = 0; s < segments.size(); ++s) {
+    const Tensor& t = segments[s];
+    TORCH_CHECK(t.is_cuda() && t.get_device() == out.get_device(), "payload_checksum: segment ", s,
+                " must be on the device of out");
+    TORCH_CHECK(t.is_contiguous(), "payload_checksum: segment ", s, " must be contiguous");
+    const int64_t isz = (int64_t)t.element_size();
+    TORCH_CHECK(isz % 4 == 0, "payload_checksum: segment ", s, " has dtype ", t.scalar_type(),
+                "; the element size must be a multiple of 4 bytes");
+    ptrs[s] = t.numel() ? t.data_ptr() : nullptr;
+    words[s] = (unsigned long long)(t.numel() * (isz / 4));
+    TORCH_CHECK(((uintptr_t)ptrs[s] & 3u) == 0, "payload_checksum: segment ", s, " is not 4-byte aligned");
+  }
+  // per-workgroup partials: from the caching allocator (stream-ordered reuse, no hipMalloc per call)
+  const int nseg = (int)segments.size(), cus = num_cus();
+  const Tensor part = at::empty({2 * (int64_t)rrl_payload_checksum_blocks(words, nseg, cus)}, out.options());
+  check_rc(rrl_payload_checksum(ptrs, words, nseg, reinterpret_cast<unsigned long long*>(part.data_ptr<int64_t>()),
+                                reinterpret_cast<unsigned long long*>(out.data_ptr<int64_t>()), cus, cur_stream()),
+           "payload_checksum");
+}
+
+// status[k] bits: 1 checksum mismatch, 2 seq != expected, 4 version outside [lo, hi] (checksum.hip).
+void payload_verify(const Tensor& sums, const Tensor& hdr, int64_t ck_col, int64_t expected_seq, int64_t lo,
+                    int64_t hi, const Tensor& status) {
+  TORCH_CHECK(hdr.is_cuda() && hdr.scalar_type() == at::kDouble && hdr.dim() == 2 && hdr.is_contiguous(),
+              "payload_verify: hdr must be a contiguous float64 [K, HDR] device tensor");
+  const int64_t K = hdr.size(0), ld = hdr.size(1);
+  TORCH_CHECK(K >= 1 && ld >= 8 && ck_col >= 0 && ck_col + 2 <= ld, "payload_verify: bad header shape [", K, ", ",
+              ld, "] for checksum column ", ck_col);
+  TORCH_CHECK(sums.is_cuda() && sums.scalar_type() == at::kLong && sums.is_contiguous() && sums.numel() == 2 * K,
+              "payload_verify: sums must be a contiguous int64 [K, 2] device tensor");
+  check_dev(status, "status", at::kInt);
+  TORCH_CHECK(status.numel() == K, "payload_verify: status must have K elements");
+  check_rc(rrl_payload_verify(reinterpret_cast<const unsigned long long*>(sums.data_ptr<int64_t>()),
+                              hdr.data_ptr<double>(), (int)ld, (int)ck_col, (int)K, (double)expected_seq,
+                              (double)lo, (double)hi, status.data_ptr<int>(), cur_stream()),
+           "payload_verify");
+}
+
 std::tuple<int64_t, int64_t, int64_t, int64_t> env_dims(int64_t env) {
   int D = 0, A = 0, NS = 0, ms = 0;
   TORCH_CHECK(rrl_env_dims((int)env, &D, &A, &NS, &ms) == 0, "unknown device env id ", env);
@@ -466,6 +516,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("grad_scale"), pybind11::arg("weight_decay"), pybind11::arg("step_add") = 0,
         pybind11::arg("step_inc") = 1);
   m.def("reduce_slabs", &reduce_slabs);
+  m.def("payload_checksum", &payload_checksum, "int64[2] (s1, s2) over the words of up to 8 contiguous segments");
+  m.def("payload_verify", &payload_verify);
   m.def("env_dims", &env_dims);
   m.def("rollout_grid", &rollout_grid);
   m.def("rollout", &rollout);

@@ -13,6 +13,7 @@ _LAZY = {
     "RelayRLTrajectory": ("relayrl_prototype_amd.types", "RelayRLTrajectory"),
     "TrainingServer": ("relayrl_prototype_amd.api.server", "TrainingServer"),
     "RelayRLAgent": ("relayrl_prototype_amd.api.agent", "RelayRLAgent"),
+    "RolloutIntegrityError": ("relayrl_prototype_amd.runtime.actor_learner", "RolloutIntegrityError"),
 }
 
 __all__ = list(_LAZY)

@@ -66,8 +66,11 @@ from .mlp import (  # noqa: E402
     gae_scan_tm,
     scan_flat,
 )
+from .integrity import payload_checksum, payload_verify  # noqa: E402
 
 __all__ = [
+    "payload_checksum",
+    "payload_verify",
     "hip",
     "hip_available",
     "use_hip",

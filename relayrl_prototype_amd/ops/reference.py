@@ -266,3 +266,47 @@ def adam_ref(param, m, v, grad, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weig
     bc2 = 1 - beta2**step
     denom = (v.sqrt() / (bc2**0.5)).add_(eps)
     param.addcdiv_(m, denom, value=-lr / bc1)
+
+
+# ---------------------------------------------------------------------- rollout integrity
+STATUS_CHECKSUM, STATUS_SEQ, STATUS_VERSION = 1, 2, 4
+
+
+def _words(t) -> np.ndarray:
+    """The 32-bit words of a tensor's storage order (element size a multiple of 4 bytes)."""
+    if isinstance(t, torch.Tensor):
+        t = t.detach().cpu().contiguous().numpy()
+    a = np.ascontiguousarray(t)
+    if a.dtype.itemsize % 4:
+        raise ValueError(f"payload_checksum: dtype {a.dtype} is not a multiple of 4 bytes wide")
+    return a.reshape(-1).view(np.uint32)
+
+
+def payload_checksum_ref(segments) -> torch.Tensor:
+    """int64[2] holding the bits of (s1, s2) mod 2^64 over the concatenated 32-bit words
+    w_0 .. w_{n-1} of ``segments``: s1 = sum w_i, s2 = sum (i + 1) w_i (checksum.hip).
+    numpy uint64 arithmetic wraps modulo 2^64 by definition."""
+    s1 = np.uint64(0)
+    s2 = np.uint64(0)
+    base = 0
+    with np.errstate(over="ignore"):
+        for seg in segments:
+            w = _words(seg).astype(np.uint64)
+            idx = np.arange(base + 1, base + 1 + w.size, dtype=np.uint64)
+            s1 = s1 + w.sum(dtype=np.uint64)
+            s2 = s2 + (idx * w).sum(dtype=np.uint64)
+            base += w.size
+    return torch.from_numpy(np.array([s1, s2], dtype=np.uint64).view(np.int64).copy())
+
+
+def payload_verify_ref(sums, hdr, ck_col, expected_seq, lo, hi) -> torch.Tensor:
+    """int32[K] status: bit 0 sums != header columns ck_col, ck_col + 1 (raw 64-bit integers),
+    bit 1 header seq (column 0) != expected_seq, bit 2 header version (column 7) outside [lo, hi]."""
+    h = hdr.detach().cpu().contiguous().numpy()
+    s = sums.detach().cpu().contiguous().numpy().reshape(-1, 2).view(np.uint64)
+    got = np.ascontiguousarray(h[:, ck_col:ck_col + 2]).view(np.uint64)
+    st = np.zeros(h.shape[0], dtype=np.int32)
+    st |= np.where((got != s).any(axis=1), STATUS_CHECKSUM, 0).astype(np.int32)
+    st |= np.where(h[:, 0] == float(expected_seq), 0, STATUS_SEQ).astype(np.int32)
+    st |= np.where((h[:, 7] >= float(lo)) & (h[:, 7] <= float(hi)), 0, STATUS_VERSION).astype(np.int32)
+    return torch.from_numpy(st)

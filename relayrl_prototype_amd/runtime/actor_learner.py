@@ -30,6 +30,25 @@ copy, so a rollout never reads a half-written policy.  Learners send from a snap
 the parameters, never from the live vector the next Adam step updates in place.  With
 ``verify_versions`` the learner checks every received header: version in
 [k - max_lag, k] and checksum equal to the one recorded when that version was produced.
+
+Rollout integrity (``integrity`` = "off" | "lagged" | "strict", docs/KERNELS.md).  The header is
+``HDR`` = 12 float64 columns:
+
+    0 seq   1 n_episodes   2 sum_ret   3 sumsq_ret   4 max_ret   5 min_ret   6 sum_len
+    7 weight version   8, 9 weight checksum (``verify_versions``)   10, 11 payload checksum s1, s2
+
+Columns 10 and 11 are raw 64-bit integers, read and written through ``header.view(torch.int64)``
+(P2P and same-dtype ``copy_`` move the bits verbatim); they stay zero with ``integrity="off"``.
+The actor checksums (ops.payload_checksum: integer sums over bit patterns) the parts of its
+rollout in the order of the tuple it returns, then header columns 0-9.  The learner recomputes
+the sums over every slot it received, and one verify launch compares them, the sequence number
+(epoch + 1) and the version window [version - max_lag, version] on the device.  "strict" waits
+for the status before learning: a stale, torn, mixed or skipped rollout raises
+``RolloutIntegrityError`` before it touches the weights.  "lagged" copies the status to pinned
+memory behind an event and reads it at the start of the next step (or in ``finish``): no sync
+per step, the error comes one step late and only on the learner that detected it -- its peers
+end through their step watchdogs, and under the elastic launcher the epoch is an ordinary
+failed one.
 """
 from __future__ import annotations
 
@@ -41,12 +60,20 @@ import torch.distributed as dist
 
 from ..algorithms.learner import PGLearner
 from ..parallel.comm import Comm, collective_timeout
-from ..utils.faults import maybe_stall_at
+from ..ops import integrity as integ
+from ..utils.faults import maybe_stall_at, rollout_fault
 from ..utils.tracing import PhaseTimer
 from .rollout_learn import RolloutLearner
 
-# header (float64): seq, n_episodes, sum_ret, sumsq_ret, max_ret, min_ret, sum_len, version, checksum, wsum
-HDR = 10
+# header (float64): seq, n_episodes, sum_ret, sumsq_ret, max_ret, min_ret, sum_len, version, checksum, wsum,
+# then the payload checksum (s1, s2) as raw 64-bit integers
+HDR = 12
+HDR_CK = 10  # first payload-checksum column; columns 0 .. HDR_CK - 1 are covered by the checksum
+INTEGRITY_MODES = ("off", "lagged", "strict")
+
+
+class RolloutIntegrityError(RuntimeError):
+    """A received rollout failed the device check: checksum, sequence number or weight version."""
 
 
 @dataclass
@@ -77,9 +104,16 @@ class ActorLearnerConfig:
     stall_timeout_s: float = 120.0  # per-step watchdog floor (0 = off); budget = max(floor, factor x avg step)
     stall_factor: float = 20.0
     phase_timing: bool = False     # HIP-event phases: Rollout, Gather, Learn, AllReduce, WeightSend, ...
+    integrity: str = "off"         # rollout checksum + seq + version check on the device: off | lagged | strict
 
     def to_dict(self):
         return asdict(self)
+
+
+def _hnum(x):
+    """A header number for messages: an int when it is one (a torn header can hold anything)."""
+    x = float(x)
+    return int(x) if x == x and abs(x) < 2.0 ** 62 and x == int(x) else x
 
 
 def weight_checksum(p: torch.Tensor) -> torch.Tensor:
@@ -154,8 +188,10 @@ class _Actor:
             self.params = self.eng.learner.pi.params
         self.need_tobs = need_tobs
         self.verify = bool(cfg.verify_versions)
+        self.integrity = cfg.integrity != "off"
         self.seq = 0
         self.header = torch.zeros(HDR, dtype=torch.float64, device=self.device)
+        self._ck_out = self.header.view(torch.int64)[HDR_CK:HDR_CK + 2]  # the kernel writes the sums here
 
     @property
     def dims(self):
@@ -198,7 +234,11 @@ class _Actor:
             h[8:10].copy_(ck)
         if self.need_tobs and tobs is None:
             tobs = torch.zeros_like(obs[:T])
-        return (obs[:T], obs[T], act, logp, rew, done, tobs if self.need_tobs else None, h)
+        parts = (obs[:T], obs[T], act, logp, rew, done, tobs if self.need_tobs else None, h)
+        if self.integrity:
+            # the parts in tuple order, then header columns 0-9 (filled above): a torn header is caught too
+            integ.payload_checksum([p for p in parts[:-1] if p is not None] + [h[:HDR_CK]], out=self._ck_out)
+        return parts
 
 
 class ActorLearner:
@@ -211,6 +251,8 @@ class ActorLearner:
                              "unless the learners also act (learner_acts=True)")
         if cfg.max_lag not in (0, 1):
             raise ValueError("max_lag must be 0 or 1")
+        if cfg.integrity not in INTEGRITY_MODES:
+            raise ValueError(f"integrity={cfg.integrity!r}: expected one of {INTEGRITY_MODES}")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
@@ -268,6 +310,19 @@ class ActorLearner:
             self.rl = RolloutLearner(self.learner, T, N, cfg.gamma, cfg.lam, self.lcomm, self.timer, blocks=K)
             self.wsend = torch.zeros_like(self.learner.pi.params)  # snapshot the P2P sends read
             self.front = self.learner.pi.params
+            self.integrity_checked = 0
+            self.integrity_mismatches = 0
+            self._sink = None         # where a fault-injected "stale" / "mix" rollout is received
+            self._ipending = []       # lagged: (epoch, version, slot index) of posted, unread checks
+            if cfg.integrity != "off":
+                pin = dev.type == "cuda"
+                self._isums = torch.zeros(K, 2, dtype=torch.int64, device=dev)
+                self._istatus = torch.zeros(K, dtype=torch.int32, device=dev)
+                # two pinned slots (status, header copy) + events: the LaggedFlag pattern (engine.py)
+                self._islots = [(torch.zeros(K, dtype=torch.int32, pin_memory=pin),
+                                 torch.zeros(K, HDR, dtype=torch.float64, pin_memory=pin)) for _ in range(2)]
+                self._ievents = [torch.cuda.Event() for _ in range(2)] if pin else None
+                self._ik = 0
         else:
             self.learner = None
             self.front = self.actor.params
@@ -353,9 +408,13 @@ class ActorLearner:
     def _gather(self, parts):
         """Fan-in: own rollout -> slot 0 (device copy), remote actors -> their slots (P2P)."""
         maybe_stall_at("gather")
+        fault = rollout_fault(self.rank, self.epoch)  # None unless configured (utils/faults.py)
+        last = len(self.shard) - 1
         ops = []
         for k, a in enumerate(self.shard):
             dst = self._slot(k)
+            if k == last and fault in ("stale", "mix"):
+                dst = self._fault_sink(dst, keep_header=fault == "mix")
             if a == self.rank:
                 for d, s in zip(dst, parts):
                     if d is not None:
@@ -372,6 +431,32 @@ class ActorLearner:
             for w in works:
                 w.wait()
             self._pending_peers = []
+        if fault in ("tear", "skip"):
+            self._fault_damage(last, fault)
+
+    def _fault_sink(self, dst, keep_header: bool):
+        """Fault injection: receive the last slot's rollout into scratch tensors instead of the
+        slot, which keeps what the previous epoch left there ("mix": the header does arrive)."""
+        if self._sink is None:
+            self._sink = [None if d is None else torch.empty_like(d) for d in dst]
+        sink = list(self._sink)
+        if keep_header:
+            sink[-1] = dst[-1]
+        return tuple(sink)
+
+    def _fault_damage(self, k: int, kind: str):
+        """Fault injection on the filled slot k: "tear" flips one bit of one reward word; "skip"
+        is an actor whose sequence number advanced by 2 (its checksum covers the number it sent)."""
+        slot = self._slot(k)
+        if kind == "tear":
+            rew = slot[4].view(-1)
+            rew[rew.numel() // 2:rew.numel() // 2 + 1].view(torch.int32).bitwise_xor_(1 << 9)
+            return
+        hdr = slot[-1]
+        hdr[0] += 1.0
+        if self.cfg.integrity != "off":
+            integ.payload_checksum([p for p in slot[:-1] if p is not None] + [hdr[:HDR_CK]],
+                                   out=hdr.view(torch.int64)[HDR_CK:HDR_CK + 2])
 
     def _send_rollout(self, parts):
         maybe_stall_at("send")
@@ -429,6 +514,8 @@ class ActorLearner:
             w.wait()
         self._send_works = []
         self.watchdog.close()
+        if self.is_learner and self.cfg.integrity != "off":
+            self._integrity_poll()  # lagged: the last step's status
 
     @property
     def wbuf(self) -> torch.Tensor:
@@ -438,12 +525,63 @@ class ActorLearner:
     def _learn(self):
         cfg = self.cfg
         K = self.topo.K
+        if cfg.integrity == "lagged":
+            self._integrity_poll()  # the previous step's status: its copy finished long ago
+        if cfg.integrity != "off":
+            self._integrity_post()
+        if cfg.integrity == "strict":
+            self._integrity_poll()  # waits: a bad batch never reaches the weights
         self.rl.learn(self.b_obs, self.b_act, self.b_rew, self.b_done, self.b_logp, tobs=self.b_tobs)
         self.last_hdr = self.b_hdr
         self.received += K
-        self._seen_seq = {a: self.epoch + 1 for a in self.shard}  # headers carry seq = epoch + 1
-        if cfg.verify_versions:
-            self._verify(self.b_hdr.cpu())
+        hdr = self.b_hdr.cpu() if cfg.verify_versions else None
+        if cfg.integrity == "off":
+            # read from the headers when they are on the host anyway; otherwise the actors' contract
+            # (seq = epoch + 1, unchecked in this mode)
+            self._seen_seq = {a: int(hdr[j, 0].item()) if hdr is not None else self.epoch + 1
+                              for j, a in enumerate(self.shard)}
+        if hdr is not None:
+            self._verify(hdr)
+
+    def _integrity_post(self):
+        """Queue the device check of every slot of this step: K checksum launches, one verify
+        launch, and the copy of (status, headers) into a pinned slot behind an event."""
+        cfg, K = self.cfg, self.topo.K
+        for k in range(K):
+            slot = self._slot(k)
+            integ.payload_checksum([p for p in slot[:-1] if p is not None] + [slot[-1][:HDR_CK]],
+                                   out=self._isums[k])
+        integ.payload_verify(self._isums, self.b_hdr, self.epoch + 1, self.version - cfg.max_lag, self.version,
+                             ck_col=HDR_CK, out=self._istatus)
+        i = self._ik % 2
+        self._ik += 1
+        st, hd = self._islots[i]
+        st.copy_(self._istatus, non_blocking=True)
+        hd.copy_(self.b_hdr, non_blocking=True)
+        if self._ievents is not None:
+            self._ievents[i].record()
+        self._ipending.append((self.epoch, self.version, i))
+
+    def _integrity_poll(self):
+        """Read every posted status (waiting only for its own event) and raise on a non-zero one."""
+        lag = self.cfg.max_lag
+        while self._ipending:
+            epoch, version, i = self._ipending.pop(0)
+            if self._ievents is not None:
+                self._ievents[i].synchronize()
+            st, hd = self._islots[i]
+            self.integrity_checked += len(self.shard)
+            bad = []
+            for j, a in enumerate(self.shard):
+                seq, ver, s = _hnum(hd[j, 0]), _hnum(hd[j, 7]), int(st[j].item())
+                self._seen_seq[a] = seq
+                if s:
+                    bad.append(f"actor {a}: bits={integ.status_bits(s)} (seq expected {epoch + 1} received {seq}, "
+                               f"version expected v{version - lag}..v{version} received v{ver})")
+            if bad:
+                self.integrity_mismatches += len(bad)
+                raise RolloutIntegrityError(f"learner {self.rank}: rollout of epoch {epoch} failed the integrity "
+                                            f"check: " + "; ".join(bad))
 
     def _verify(self, hdr):
         k, lag = self.version, self.cfg.max_lag
@@ -503,6 +641,9 @@ class ActorLearner:
             out["ActorSeqs"] = h[:, 0].tolist()
             out["ActorVersions"] = [int(x) for x in h[:, 7].tolist()]
             out.update(self.learner.summarize())
+        if self.is_learner and self.cfg.integrity != "off":
+            out["IntegrityChecked"] = self.integrity_checked        # slots verified (and read back) so far
+            out["IntegrityMismatches"] = self.integrity_mismatches
         out["EnvSteps"] = self.epoch * self.cfg.rollout_len * self.cfg.num_envs * self.n_actors
         if self.timer.enabled:
             out.update(self.timer.columns())
@@ -525,6 +666,15 @@ class ActorLearner:
         self.comm.broadcast_(vec, src)
         self.epoch, self.version = int(vec[0].item()), int(vec[1].item())
         self._front_version = self.version
+        self._epoch_restored()
+
+    def _epoch_restored(self):
+        """``epoch`` was set from outside: the next header carries seq = epoch + 1, and a lagged
+        check posted before the restore no longer refers to anything."""
+        if self.actor is not None:
+            self.actor.seq = self.epoch
+        if self.is_learner:
+            self._ipending = []
 
     # ------------------------------------------------------------------ elastic snapshot
     def snapshot_tensors(self):
@@ -540,6 +690,7 @@ class ActorLearner:
     def set_counters(self, c: dict):
         self.epoch, self.version, self.received = int(c["epoch"]), int(c["version"]), int(c["received"])
         self._front_version = int(c["_front_version"])
+        self._epoch_restored()
         if self.learner is not None and self.actor is not None:
             self.actor.params.copy_(self.learner.pi.params)
 
@@ -554,6 +705,7 @@ class ActorLearner:
 
     def load_state_dict(self, sd: dict):
         self.epoch, self.version = int(sd["epoch"]), int(sd["version"])
+        self._epoch_restored()
         if self.learner is not None and "learner" in sd:
             self.learner.load_state_dict(sd["learner"])
             if self.actor is not None:

@@ -26,6 +26,15 @@ Process-level faults for the elastic-restart path (runtime/launcher.py):
                               receiving its shard, ``send`` = an actor before sending its
                               rollout.  The peers fail mid-epoch, with part of the epoch's
                               updates applied (the elastic epoch-start snapshot's test case).
+
+Data-plane faults for the rollout integrity check (runtime/actor_learner.py ``integrity``):
+
+    RRL_FAULT_ROLLOUT="0:2:stale" -- learner rank 0 damages the LAST slot of its shard batch in
+                              epoch 2 (``set_rollout_fault`` sets or clears the same spec in-process):
+                              ``stale`` = the slot keeps last epoch's payload and header (the incoming
+                              rollout goes to a sink), ``mix`` = only the header is updated, ``tear`` =
+                              one bit of one reward word is flipped after the slot was filled,
+                              ``skip`` = the actor's sequence number advances by 2.
 """
 from __future__ import annotations
 
@@ -123,6 +132,40 @@ def maybe_stall_rank(rank: int, epoch: int, run_dir: str) -> None:
     open(marker, "w").close()
     print(f"[faults] injected stall of rank {rank} before epoch {epoch} ({sec} s)", flush=True)
     time.sleep(float(sec))
+
+
+ROLLOUT_FAULT_KINDS = ("stale", "mix", "tear", "skip")
+_ROLLOUT = None  # parsed RRL_FAULT_ROLLOUT (rank, epoch, kind), or False when unset
+
+
+def _parse_rollout_fault(spec: str):
+    if not spec:
+        return False
+    r, e, kind = spec.split(":")
+    if kind not in ROLLOUT_FAULT_KINDS:
+        raise ValueError(f"RRL_FAULT_ROLLOUT kind {kind!r}: expected one of {ROLLOUT_FAULT_KINDS}")
+    return (int(r), int(e), kind)
+
+
+def set_rollout_fault(spec: Optional[str]) -> None:
+    """Set ("rank:epoch:kind") or clear (None / "") the rollout fault of this process; overrides
+    RRL_FAULT_ROLLOUT, which is parsed once."""
+    global _ROLLOUT
+    _ROLLOUT = _parse_rollout_fault(spec or "")
+
+
+def rollout_fault(rank: int, epoch: int) -> Optional[str]:
+    """The fault kind learner ``rank`` applies to its last slot in ``epoch``, or None."""
+    global _ROLLOUT
+    if _ROLLOUT is None:
+        _ROLLOUT = _parse_rollout_fault(os.environ.get("RRL_FAULT_ROLLOUT", ""))
+    if not _ROLLOUT:
+        return None
+    r, e, kind = _ROLLOUT
+    if (r, e) != (int(rank), int(epoch)):
+        return None
+    print(f"[faults] injected {kind} rollout on learner {rank} in epoch {epoch}", flush=True)
+    return kind
 
 
 _CTX = {"rank": -1, "epoch": -1, "run_dir": "."}
