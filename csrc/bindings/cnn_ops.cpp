@@ -1,109 +1,20 @@
 // PyTorch bindings for the pixel-model kernels (csrc/kernels/cnn.hip, pong.hip).
 // Same contract as hip_ops.cpp: every tensor is validated (device, dtype, contiguity,
 // size) before a launch, launches go to the current HIP stream.
-#include <ATen/hip/HIPContext.h>
 #include <pybind11/stl.h>
-#include <torch/extension.h>
 
-#include <cstdint>
-#include <optional>
 #include <tuple>
 #include <vector>
 
-extern "C" {
-int rrl_conv_fwd(const void* x, int x_u8, const uint16_t* w, const float* b, uint16_t* y, int N, int H, int W,
-                 int C, int KH, int KW, int S, int Cout, int relu, float* work, long long work_elems, void* stream);
-int rrl_gemm_dgrad(const uint16_t* dy, const uint16_t* w, const uint16_t* mask, uint16_t* out, int M, int Cout,
-                   int K, void* stream);
-int rrl_col2im_mask(const uint16_t* dcol, const uint16_t* xact, uint16_t* dx, int N, int H, int W, int C, int KH,
-                    int KW, int S, void* stream);
-int rrl_conv_wgrad(const uint16_t* dy, const void* x, int x_u8, float* part, float* bias_part, int splits, int N,
-                   int H, int W, int C,
-                   int KH, int KW, int S, int Cout, void* stream);
-int rrl_gemm_splits(int R, int splits);
-int rrl_conv_dgrad(const uint16_t* dy, const uint16_t* w, const uint16_t* xact, uint16_t* dx, int N, int H, int W,
-                   int C, int KH, int KW, int S, int Cout, void* stream);
-int rrl_sum_splits(const float* part, int splits, long long n, float* out, void* stream);
-int rrl_sum_splits_multi(const float* const* parts, const int* splits, const long long* ns, float* const* outs,
-                         int count, void* stream);
-int rrl_colsum(const uint16_t* y, int M, int C, float* part, int splits, void* stream);
-int rrl_sumsq(const float* x, long long n, float* work, int work_n, float* out, void* stream);
-int rrl_adam_clip(float* p, float* m, float* v, const float* g, uint16_t* shadow, long long n, const float* norm_sq,
-                  float max_norm, float lr, float b1, float b2, float eps, int step, const long long* step_dev, int norm_parts,
-                  void* stream);
-int rrl_sumsq_partial(const float* x, long long n, float* work, int work_n, void* stream);
-int rrl_counter_add(long long* c, long long inc, void* stream);
-int rrl_counter_add_n(long long* const* c, const long long* inc, int n, void* stream);
-int rrl_to_bf16(const float* x, uint16_t* y, long long n, void* stream);
-int rrl_a2c_head(int mode, const uint16_t* h, const float* head_params, int B, int A, int32_t* act, float* logp,
-                 float* value, float* logits_out, unsigned long long seed, unsigned long long step,
-                 const unsigned long long* step_base, int row_offset,
-                 const int32_t* act_in, const float* adv, const float* ret, float inv_B, float vf_coef,
-                 float ent_coef, uint16_t* dh, float* dhead, float* stats, int grid, const float* part,
-                 int splits, const float* fc_b, uint16_t* h_out, void* stream);
-int rrl_fc_nt_part(const uint16_t* a, const uint16_t* b, float* part, int M, int N, int K, int splits, void* stream);
-
-int rrl_fc_nt_mask(const uint16_t* a, const uint16_t* b, const uint16_t* mask, uint16_t* out, int M, int N, int K,
-                   void* stream);
-int rrl_transpose_bf16(const uint16_t* in, uint16_t* out, int R, int C, void* stream);
-int rrl_fc_tn_part(const uint16_t* x, const uint16_t* y, float* part, int R, int I, int J, int splits,
-                   const uint16_t* ones, float* bias_part, void* stream);
-int rrl_head_wgrad(const uint16_t* h, const float* dhead, int B, int A, float* part, int nblk, void* stream);
-int rrl_pong_state_size();
-int rrl_pong_step(float* state, const int32_t* act, float* rew, float* done, float* fin_ret, float* fin_len,
-                  float* ep_acc, int N, unsigned long long seed, unsigned long long step,
-                  const unsigned long long* step_base, int max_steps, int reset_all, float* hist_out, void* stream);
-int rrl_pong_render(const float* state, uint8_t* obs, int N, void* stream);
-int rrl_pong_step_render(float* state, const int32_t* act, float* rew, float* done, float* fin_ret, float* fin_len,
-                         float* ep_acc, uint8_t* obs, int N, unsigned long long seed, unsigned long long step,
-                         const unsigned long long* step_base, int max_steps, int reset_all, uint8_t* frames,
-                         int32_t* fidx, int R, void* stream);
-int rrl_pong_ring_fill(float* state, uint8_t* frames, int32_t* fidx, int N, int R, unsigned long long step,
-                       const unsigned long long* step_base, void* stream);
-int rrl_conv_stack_fwd(const uint8_t* x, const float* hist, const uint8_t* frames, const int32_t* fidx,
-                       const uint16_t* w1, const float* b1,
-                       const uint16_t* w2, const float* b2, const uint16_t* w3, const float* b3, uint16_t* y1,
-                       uint16_t* y2, uint16_t* y3, int N, int max_grid, void* stream);
-int rrl_conv3_bwd(const uint16_t* dy, const uint16_t* w, const uint16_t* xact, uint16_t* dx, float* part,
-                  float* bias_part, int N, int grid, int variant, void* stream);
-int rrl_conv2_bwd(const uint16_t* dy, const uint16_t* w, const uint16_t* xact, uint16_t* dx, float* part,
-                  float* bias_part, int N, int grid, int staged, void* stream);
-int rrl_conv1_wgrad8(const uint8_t* x, const float* hist, const uint8_t* frames, const int32_t* fidx,
-                     const uint16_t* dy, float* part, float* bias_part, int N, int grid, int T, void* stream);
-int rrl_pong_render_hist(const float* hist, uint8_t* obs, int N, void* stream);
-int rrl_pong_head_step_render(const float* part, int splits, const float* fc_b, const float* head_params, int A,
-                              uint16_t* h_out, int32_t* act, float* logp, float* value, unsigned long long sample_seed,
-                              unsigned long long sample_step, const unsigned long long* sample_base, float* state,
-                              float* rew, float* done, float* fin_ret, float* fin_len, float* ep_acc, uint8_t* obs,
-                              int N, unsigned long long seed, unsigned long long step,
-                              const unsigned long long* step_base, int max_steps, uint8_t* frames, int32_t* fidx,
-                              int R, void* stream);
-
-}
+#include "api.h"
+#include "check.h"
 
 namespace {
 
-using at::Tensor;
-using OptT = std::optional<Tensor>;
+using namespace rrl_bind;
 
-void* stream() { return (void*)at::hip::getCurrentHIPStream().stream(); }
-
-void check(const Tensor& t, const char* name, at::ScalarType dt, int64_t min_numel) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.scalar_type() == dt, name, " has dtype ", t.scalar_type(), ", expected ", dt);
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.numel() >= min_numel, name, " has ", t.numel(), " elements, need >= ", min_numel);
-}
-template <class T>
-T* opt_ptr(const OptT& t, const char* name, at::ScalarType dt, int64_t n) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  check(*t, name, dt, n);
-  return reinterpret_cast<T*>(t->data_ptr());
-}
-void rc_check(int rc, const char* what) {
-  TORCH_CHECK(rc == 0, what, " failed with code ", rc,
-              " (", (rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported shape"), ")");
-}
+// the pixel kernels' negative return codes mean a shape they have no kernel for
+void rc_check(int rc, const char* what) { check_rc(rc, what, "unsupported shape"); }
 uint16_t* bf(const Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
 
 constexpr int64_t kFrameBytes = 7056;  // one PongSynth frame in the ring (pong_render.h)
@@ -152,7 +63,7 @@ void conv_fwd(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& y
   float* wk = opt_ptr<float>(work, "work", at::kFloat, 0);
   const long long wn = wk ? work->numel() : 0;
   rc_check(rrl_conv_fwd(x.data_ptr(), u8, bf(w), b.data_ptr<float>(), bf(y), N, H, W, C, KH, KW, S, Cout, relu, wk,
-                        wn, stream()),
+                        wn, cur_stream()),
            "conv_fwd");
 }
 
@@ -187,7 +98,7 @@ void conv_stack_fwd(const OptT& x, const Tensor& w1, const Tensor& b1, const Ten
                               bf(y3), (int)N,
                               probe > 0 ? -(int)((probe << 16) | (grid > 0 ? grid : cus))
                                         : (grid > 0 ? (int)grid : cus),
-                              stream()),
+                              cur_stream()),
            "conv_stack_fwd");
 }
 
@@ -203,7 +114,7 @@ void conv3_bwd(const Tensor& dy, const Tensor& w, const Tensor& xact, const Tens
   check(part, "part", at::kFloat, grid * 64 * 576);
   check(bias_part, "bias_part", at::kFloat, grid * 512);
   rc_check(rrl_conv3_bwd(bf(dy), bf(w), bf(xact), bf(dx), part.data_ptr<float>(), bias_part.data_ptr<float>(),
-                         (int)N, (int)grid, (int)variant, stream()),
+                         (int)N, (int)grid, (int)variant, cur_stream()),
            "conv3_bwd");
 }
 
@@ -219,7 +130,7 @@ void conv2_bwd(const Tensor& dy, const Tensor& w, const Tensor& xact, const Tens
   check(part, "part", at::kFloat, grid * 64 * 512);
   check(bias_part, "bias_part", at::kFloat, grid * 512);
   rc_check(rrl_conv2_bwd(bf(dy), bf(w), bf(xact), bf(dx), part.data_ptr<float>(), bias_part.data_ptr<float>(),
-                         (int)N, (int)grid, (int)staged, stream()),
+                         (int)N, (int)grid, (int)staged, cur_stream()),
            "conv2_bwd");
 }
 
@@ -240,7 +151,7 @@ int64_t conv1_wgrad8(const OptT& x, const Tensor& dy, const Tensor& part, const 
   // back to back share 3 of their 4 frames)
   TORCH_CHECK(env_major_T <= 1 || (fp && N % env_major_T == 0), "conv1_wgrad8: env_major_T needs the ring and T | N");
   rc_check(rrl_conv1_wgrad8(xp, hp, fp, ip, bf(dy), part.data_ptr<float>(), bias_part.data_ptr<float>(), (int)N, (int)grid,
-                            (int)env_major_T, stream()),
+                            (int)env_major_T, cur_stream()),
            "conv1_wgrad8");
   return 2 * grid;
 }
@@ -252,7 +163,7 @@ void gemm_dgrad(const Tensor& dy, const Tensor& w, const OptT& mask, const Tenso
   check(w, "w", at::kBFloat16, Cout * K);
   check(out, "out", at::kBFloat16, M * K);
   const uint16_t* mp = opt_ptr<uint16_t>(mask, "mask", at::kBFloat16, M * K);
-  rc_check(rrl_gemm_dgrad(bf(dy), bf(w), mp, bf(out), M, Cout, K, stream()), "gemm_dgrad");
+  rc_check(rrl_gemm_dgrad(bf(dy), bf(w), mp, bf(out), M, Cout, K, cur_stream()), "gemm_dgrad");
 }
 
 void col2im_mask(const Tensor& dcol, const Tensor& xact, const Tensor& dx, int64_t N, int64_t H, int64_t W,
@@ -263,7 +174,7 @@ void col2im_mask(const Tensor& dcol, const Tensor& xact, const Tensor& dx, int64
   check(dcol, "dcol", at::kBFloat16, N * g.OH() * g.OW() * KH * KW * C);
   check(xact, "xact", at::kBFloat16, N * H * W * C);
   check(dx, "dx", at::kBFloat16, N * H * W * C);
-  rc_check(rrl_col2im_mask(bf(dcol), bf(xact), bf(dx), N, H, W, C, KH, KW, S, stream()), "col2im_mask");
+  rc_check(rrl_col2im_mask(bf(dcol), bf(xact), bf(dx), N, H, W, C, KH, KW, S, cur_stream()), "col2im_mask");
 }
 
 // Returns false (nothing launched) for geometries without an implicit-dgrad kernel.
@@ -275,7 +186,7 @@ bool conv_dgrad(const Tensor& dy, const Tensor& w, const Tensor& xact, const Ten
   check(w, "w", at::kBFloat16, Cout * KH * KW * C);
   check(xact, "xact", at::kBFloat16, N * H * W * C);
   check(dx, "dx", at::kBFloat16, N * H * W * C);
-  const int rc = rrl_conv_dgrad(bf(dy), bf(w), bf(xact), bf(dx), N, H, W, C, KH, KW, S, Cout, stream());
+  const int rc = rrl_conv_dgrad(bf(dy), bf(w), bf(xact), bf(dx), N, H, W, C, KH, KW, S, Cout, cur_stream());
   if (rc == -1) return false;
   rc_check(rc, "conv_dgrad");
   return true;
@@ -302,7 +213,7 @@ int64_t conv_wgrad(const Tensor& dy, const Tensor& x, const Tensor& part, int64_
     bp = bias_part->data_ptr<float>();
   }
   rc_check(rrl_conv_wgrad(bf(dy), x.data_ptr(), u8, part.data_ptr<float>(), bp, (int)splits, N, H, W, C, KH, KW, S,
-                          Cout, stream()),
+                          Cout, cur_stream()),
            "conv_wgrad");
   return s;
 }
@@ -310,7 +221,7 @@ int64_t conv_wgrad(const Tensor& dy, const Tensor& x, const Tensor& part, int64_
 void sum_splits(const Tensor& part, int64_t splits, int64_t n, const Tensor& out) {
   check(part, "part", at::kFloat, splits * n);
   check(out, "out", at::kFloat, n);
-  rc_check(rrl_sum_splits(part.data_ptr<float>(), (int)splits, n, out.data_ptr<float>(), stream()), "sum_splits");
+  rc_check(rrl_sum_splits(part.data_ptr<float>(), (int)splits, n, out.data_ptr<float>(), cur_stream()), "sum_splits");
 }
 
 // [(part, splits, n, out), ...] (<= 8 segments) summed in one launch
@@ -332,14 +243,14 @@ void sum_splits_multi(const std::vector<std::tuple<Tensor, int64_t, int64_t, Ten
     splits.push_back((int)s);
     ns.push_back(n);
   }
-  rc_check(rrl_sum_splits_multi(parts.data(), splits.data(), ns.data(), outs.data(), (int)segs.size(), stream()),
+  rc_check(rrl_sum_splits_multi(parts.data(), splits.data(), ns.data(), outs.data(), (int)segs.size(), cur_stream()),
            "sum_splits_multi (16-byte aligned part / out needed)");
 }
 
 void colsum(const Tensor& y, int64_t M, int64_t C, const Tensor& part, int64_t splits) {
   check(y, "y", at::kBFloat16, M * C);
   check(part, "part", at::kFloat, splits * C);
-  rc_check(rrl_colsum(bf(y), M, C, part.data_ptr<float>(), (int)splits, stream()), "colsum");
+  rc_check(rrl_colsum(bf(y), M, C, part.data_ptr<float>(), (int)splits, cur_stream()), "colsum");
 }
 
 void sumsq(const Tensor& x, const Tensor& work, const Tensor& out) {
@@ -347,7 +258,7 @@ void sumsq(const Tensor& x, const Tensor& work, const Tensor& out) {
   check(work, "work", at::kFloat, 1);
   check(out, "out", at::kFloat, 1);
   rc_check(rrl_sumsq(x.data_ptr<float>(), x.numel(), work.data_ptr<float>(), (int)work.numel(),
-                     out.data_ptr<float>(), stream()),
+                     out.data_ptr<float>(), cur_stream()),
            "sumsq");
 }
 
@@ -367,7 +278,7 @@ void adam_clip(const Tensor& p, const Tensor& m, const Tensor& v, const Tensor& 
   const float* ns = opt_ptr<const float>(norm_sq, "norm_sq", at::kFloat, norm_parts > 0 ? norm_parts : 1);
   rc_check(rrl_adam_clip(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g.data_ptr<float>(), sh, n,
                          ns, (float)max_norm, (float)lr, (float)b1, (float)b2, (float)eps, (int)step, sd,
-                         (int)norm_parts, stream()),
+                         (int)norm_parts, cur_stream()),
            "adam_clip");
 }
 
@@ -375,7 +286,7 @@ void adam_clip(const Tensor& p, const Tensor& m, const Tensor& v, const Tensor& 
 int64_t sumsq_partial(const Tensor& x, const Tensor& work) {
   check(x, "x", at::kFloat, 0);
   check(work, "work", at::kFloat, 0);
-  const int g = rrl_sumsq_partial(x.data_ptr<float>(), x.numel(), work.data_ptr<float>(), (int)work.numel(), stream());
+  const int g = rrl_sumsq_partial(x.data_ptr<float>(), x.numel(), work.data_ptr<float>(), (int)work.numel(), cur_stream());
   TORCH_CHECK(g > 0, "sumsq_partial failed");
   return g;
 }
@@ -392,19 +303,19 @@ void counter_add_many(const std::vector<std::tuple<Tensor, int64_t>>& adds) {
     incs[i] = std::get<1>(adds[i]);
     for (size_t j = 0; j < i; ++j) TORCH_CHECK(cs[j] != cs[i], "counter_add_many: counters must be distinct");
   }
-  rc_check(rrl_counter_add_n(cs, incs, (int)adds.size(), stream()), "counter_add_many");
+  rc_check(rrl_counter_add_n(cs, incs, (int)adds.size(), cur_stream()), "counter_add_many");
 }
 
 void counter_add(const Tensor& c, int64_t inc) {
   check(c, "counter", at::kLong, 1);
-  rc_check(rrl_counter_add((long long*)c.data_ptr(), inc, stream()),
+  rc_check(rrl_counter_add((long long*)c.data_ptr(), inc, cur_stream()),
            "counter_add");
 }
 
 void to_bf16(const Tensor& x, const Tensor& y) {
   check(x, "x", at::kFloat, 0);
   check(y, "y", at::kBFloat16, x.numel());
-  rc_check(rrl_to_bf16(x.data_ptr<float>(), bf(y), x.numel(), stream()), "to_bf16");
+  rc_check(rrl_to_bf16(x.data_ptr<float>(), bf(y), x.numel(), cur_stream()), "to_bf16");
 }
 
 void a2c_head(int64_t mode, const Tensor& h, const Tensor& head_params, int64_t B, int64_t A, const OptT& act,
@@ -437,7 +348,7 @@ void a2c_head(int64_t mode, const Tensor& h, const Tensor& head_params, int64_t 
   if (pp) TORCH_CHECK(mode == 0 && fb && splits >= 1, "a2c_head: part needs mode 0, fc_b and splits >= 1");
   rc_check(rrl_a2c_head((int)mode, bf(h), head_params.data_ptr<float>(), B, A, ap, lp, vp, lo, (uint64_t)seed,
                         (uint64_t)step, sb, (int)row_offset, ai, ad, re, (float)inv_B, (float)vf_coef, (float)ent_coef,
-                        dhp, dhd, st, (int)grid, pp, (int)splits, fb, pp ? bf(h) : nullptr, stream()),
+                        dhp, dhd, st, (int)grid, pp, (int)splits, fb, pp ? bf(h) : nullptr, cur_stream()),
            "a2c_head");
 }
 
@@ -450,7 +361,7 @@ int64_t fc_nt_part(const Tensor& a, const Tensor& b, const Tensor& part, int64_t
   check(b, "b", at::kBFloat16, N * K);
   const int64_t kt = K / 64, kps = (kt + splits - 1) / splits, used = (kt + kps - 1) / kps;
   check(part, "part", at::kFloat, used * M * N);
-  const int rc = rrl_fc_nt_part(bf(a), bf(b), part.data_ptr<float>(), M, N, K, (int)splits, stream());
+  const int rc = rrl_fc_nt_part(bf(a), bf(b), part.data_ptr<float>(), M, N, K, (int)splits, cur_stream());
   TORCH_CHECK(rc > 0, "fc_nt_part failed with code ", rc);
   return rc;
 }
@@ -463,7 +374,7 @@ void fc_nt_mask(const Tensor& a, const Tensor& b, const Tensor& mask, const Tens
   check(b, "b", at::kBFloat16, N * K);
   check(mask, "mask", at::kBFloat16, M * N);
   check(out, "out", at::kBFloat16, M * N);
-  rc_check(rrl_fc_nt_mask(bf(a), bf(b), bf(mask), bf(out), M, N, K, stream()), "fc_nt_mask");
+  rc_check(rrl_fc_nt_mask(bf(a), bf(b), bf(mask), bf(out), M, N, K, cur_stream()), "fc_nt_mask");
 }
 
 // fp32 partials part[splits][I][J] of x[R][I]^T . y[R][J] (fc.hip, the fc weight gradient);
@@ -482,7 +393,7 @@ int64_t fc_tn_part(const Tensor& x, const Tensor& y, const Tensor& part, int64_t
   float* bp = opt_ptr<float>(bias_part, "bias_part", at::kFloat, used * I);
   TORCH_CHECK((on == nullptr) == (bp == nullptr) && (!bp || J % 128 != 0),
               "fc_tn_part: ones and bias_part go together and need J % 128 != 0");
-  const int rc = rrl_fc_tn_part(bf(x), bf(y), part.data_ptr<float>(), R, I, J, (int)splits, on, bp, stream());
+  const int rc = rrl_fc_tn_part(bf(x), bf(y), part.data_ptr<float>(), R, I, J, (int)splits, on, bp, cur_stream());
   TORCH_CHECK(rc > 0, "fc_tn_part failed with code ", rc);
   return rc;
 }
@@ -491,7 +402,7 @@ void transpose_bf16(const Tensor& in, const Tensor& out, int64_t R, int64_t C) {
   TORCH_CHECK(R > 0 && C > 0 && R % 8 == 0 && C % 8 == 0, "transpose_bf16: R, C must be multiples of 8");
   check(in, "in", at::kBFloat16, R * C);
   check(out, "out", at::kBFloat16, R * C);
-  rc_check(rrl_transpose_bf16(bf(in), bf(out), R, C, stream()), "transpose_bf16");
+  rc_check(rrl_transpose_bf16(bf(in), bf(out), R, C, cur_stream()), "transpose_bf16");
 }
 
 void head_wgrad(const Tensor& h, const Tensor& dhead, int64_t B, int64_t A, const Tensor& part, int64_t nblk) {
@@ -500,7 +411,7 @@ void head_wgrad(const Tensor& h, const Tensor& dhead, int64_t B, int64_t A, cons
   check(h, "h", at::kBFloat16, B * F);
   check(dhead, "dhead", at::kFloat, B * (A + 1));
   check(part, "part", at::kFloat, nblk * ((A + 1) * F + A + 1));
-  rc_check(rrl_head_wgrad(bf(h), dhead.data_ptr<float>(), B, A, part.data_ptr<float>(), nblk, stream()),
+  rc_check(rrl_head_wgrad(bf(h), dhead.data_ptr<float>(), B, A, part.data_ptr<float>(), nblk, cur_stream()),
            "head_wgrad");
 }
 
@@ -523,7 +434,7 @@ void pong_step(const Tensor& state, const Tensor& act, const Tensor& rew, const 
     rc_check(rrl_pong_step_render(state.data_ptr<float>(), act.data_ptr<int32_t>(), rew.data_ptr<float>(),
                                   done.data_ptr<float>(), fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), acc,
                                   nullptr, (int)N, (uint64_t)seed, (uint64_t)step, sb, (int)max_steps,
-                                  reset_all ? 1 : 0, fp, fidx->data_ptr<int32_t>(), (int)ring_slots, stream()),
+                                  reset_all ? 1 : 0, fp, fidx->data_ptr<int32_t>(), (int)ring_slots, cur_stream()),
              "pong_step_render (frame ring)");
     return;
   }
@@ -532,14 +443,14 @@ void pong_step(const Tensor& state, const Tensor& act, const Tensor& rew, const 
     rc_check(rrl_pong_step_render(state.data_ptr<float>(), act.data_ptr<int32_t>(), rew.data_ptr<float>(),
                                   done.data_ptr<float>(), fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), acc,
                                   obs->data_ptr<uint8_t>(), (int)N, (uint64_t)seed, (uint64_t)step, sb,
-                                  (int)max_steps, reset_all ? 1 : 0, nullptr, nullptr, 0, stream()),
+                                  (int)max_steps, reset_all ? 1 : 0, nullptr, nullptr, 0, cur_stream()),
              "pong_step_render");
     return;
   }
   float* hout = opt_ptr<float>(hist, "hist", at::kFloat, N * 16);  // the new frame histories (fused render)
   rc_check(rrl_pong_step(state.data_ptr<float>(), act.data_ptr<int32_t>(), rew.data_ptr<float>(),
                          done.data_ptr<float>(), fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), acc, (int)N,
-                         (uint64_t)seed, (uint64_t)step, sb, (int)max_steps, reset_all ? 1 : 0, hout, stream()),
+                         (uint64_t)seed, (uint64_t)step, sb, (int)max_steps, reset_all ? 1 : 0, hout, cur_stream()),
            "pong_step");
 }
 
@@ -583,7 +494,7 @@ void pong_head_step(const Tensor& part, int64_t splits, const Tensor& fc_b, cons
                                      (uint64_t)sample_step, ssb, state.data_ptr<float>(), rew.data_ptr<float>(),
                                      done.data_ptr<float>(), fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), acc,
                                      op, (int)N, (uint64_t)seed, (uint64_t)step, sb, (int)max_steps, fp,
-                                     fp ? fidx->data_ptr<int32_t>() : nullptr, (int)ring_slots, stream()),
+                                     fp ? fidx->data_ptr<int32_t>() : nullptr, (int)ring_slots, cur_stream()),
            "pong_head_step");
 }
 
@@ -594,7 +505,7 @@ void pong_ring_fill(const Tensor& state, const Tensor& frames, const Tensor& fid
   uint8_t* fp = ring_store(frames, fidx, N, ring_slots);
   const unsigned long long* sb = opt_ptr<const unsigned long long>(step_base, "step_base", at::kLong, 1);
   rc_check(rrl_pong_ring_fill(state.data_ptr<float>(), fp, fidx.data_ptr<int32_t>(), (int)N, (int)ring_slots,
-                              (uint64_t)step, sb, stream()),
+                              (uint64_t)step, sb, cur_stream()),
            "pong_ring_fill");
 }
 
@@ -602,13 +513,13 @@ void pong_ring_fill(const Tensor& state, const Tensor& frames, const Tensor& fid
 void pong_render_hist(const Tensor& hist, const Tensor& obs, int64_t N) {
   check(hist, "hist", at::kFloat, N * 16);
   check(obs, "obs", at::kByte, N * 84 * 84 * 4);
-  rc_check(rrl_pong_render_hist(hist.data_ptr<float>(), obs.data_ptr<uint8_t>(), (int)N, stream()), "pong_render_hist");
+  rc_check(rrl_pong_render_hist(hist.data_ptr<float>(), obs.data_ptr<uint8_t>(), (int)N, cur_stream()), "pong_render_hist");
 }
 
 void pong_render(const Tensor& state, const Tensor& obs, int64_t N) {
   check(state, "state", at::kFloat, N * pong_state_size());
   check(obs, "obs", at::kByte, N * 84 * 84 * 4);  // [N][21][21][64] space-to-depth
-  rc_check(rrl_pong_render(state.data_ptr<float>(), obs.data_ptr<uint8_t>(), (int)N, stream()), "pong_render");
+  rc_check(rrl_pong_render(state.data_ptr<float>(), obs.data_ptr<uint8_t>(), (int)N, cur_stream()), "pong_render");
 }
 
 }  // namespace

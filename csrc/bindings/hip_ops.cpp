@@ -5,65 +5,16 @@
 // tensor (device, dtype, contiguity, shape) BEFORE a launch so that a bad call raises a
 // Python exception instead of faulting the GPU, and launches on the current HIP stream
 // (so everything here is capturable into a hipGraph via torch.cuda.graph).
-#include <ATen/hip/HIPContext.h>
-#include <torch/extension.h>
-
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
-#include <cstdint>
-#include <optional>
 #include <vector>
 
-extern "C" {
-int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D, int A, int H,
-                    const float* mask, const int* act_in, const float* actc_in, int* act_out,
-                    float* actc_out, float* out0, float* out1, float* logits_out, uint64_t seed,
-                    uint64_t step, uint32_t row_offset, const float* gate, float* x_copy, int* act_host,
-                    float* actc_host, int num_cu, void* stream);
-int rrl_mlp_grad_slabs(int B, int num_cu);
-int rrl_set_value_grad_mode(int mode);
-int rrl_set_value_fwd_mode(int mode);
-int rrl_set_value_grad_tune(int tune);
-void rrl_set_value_grad_stamps(void* buf);
-int rrl_mlp_grad(int head, const float* params, const float* X, int B, int D, int A, int H,
-                 const float* mask, const int* act, const float* actc, const float* adv, const float* ret,
-                 const float* logp_old, const float* adv_stats, float inv_B, float clip_eps, float ent_coef,
-                 float* grad_slab, float* loss_slab, int P, const int* nvalid, const float* inv_B_dev, int num_cu, void* stream);
-int rrl_scan_tm_parts(int N);
-int rrl_gae_scan_tm(const float* rew, const float* done, const float* val, const float* tval, float* adv,
-                    float* ret, float* stats_part, float* stats_out, int K, int T, int N, float gamma,
-                    float lam, long long* const* cnt, const long long* inc, int ncnt, void* stream);
-int rrl_scan_flat_blocks(int L);
-int rrl_scan_flat(const float* rew, const float* done, const float* val, const float* boot, float* adv,
-                  float* ret, float* work, float* stats_out, int L, float gamma, float lam, void* stream);
-int rrl_stats_reduce(const float* part, int nparts, float* out, void* stream);
-int rrl_column_sums(const float* part, int rows, int ld, int cols, double* out, void* stream);
-int rrl_adam(float* param, float* m, float* v, const float* grad, const float* slab, int nslab,
-             float* grad_out, int* step, unsigned* ticket, int P, float lr, float beta1, float beta2,
-             float eps, float grad_scale, float weight_decay, int step_add, int step_inc, void* stream);
-int rrl_reduce_slabs(const float* slab, int nslab, int P, float scale, float* out, void* stream);
-int rrl_payload_checksum_blocks(const unsigned long long* words, int nseg, int num_cu);
-int rrl_payload_checksum(const void* const* ptrs, const unsigned long long* words, int nseg,
-                         unsigned long long* part, unsigned long long* out, int num_cu, void* stream);
-int rrl_payload_verify(const unsigned long long* sums, const double* hdr, int ld, int ck_col, int K,
-                       double expected_seq, double lo, double hi, int* status, void* stream);
-int rrl_env_dims(int env, int* D, int* A, int* NS, int* max_steps);
-int rrl_rollout_cont(int env, const float* params, const float* env_consts, int N, int T, int H, float* state,
-                     int* ep_len, float* ep_ret, float* obs_buf, float* act_buf, float* logp_buf, float* rew_buf,
-                     float* done_buf, float* tobs_buf, float* ep_stats, uint64_t seed, uint64_t step0,
-                     int reset_all, int max_steps, int num_cu, void* stream);
-int rrl_rollout_grid(int N, int num_cu);
-int rrl_rollout(int env, const float* params, int N, int T, int H, float* state, int* ep_len, float* ep_ret,
-                float* obs_buf, int* act_buf, float* logp_buf, float* rew_buf, float* done_buf,
-                float* tobs_buf, float* ep_stats, uint64_t seed, uint64_t step0, int reset_all, int max_steps,
-                int num_cu, void* stream);
-}
+#include "api.h"
+#include "check.h"
 
 namespace {
 
-using at::Tensor;
-using OptT = std::optional<Tensor>;
+using namespace rrl;
+using namespace rrl_bind;
 
 int g_cu_limit = 0;  // > 0: size every grid for this many CUs (set_cu_limit)
 
@@ -103,69 +54,40 @@ void destroy_stream(int64_t st) {
   if (st) (void)hipStreamDestroy((hipStream_t)(uintptr_t)st);
 }
 
-void* cur_stream() { return (void*)at::hip::getCurrentHIPStream().stream(); }
-
-void check_dev(const Tensor& t, const char* name, at::ScalarType dt) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.scalar_type() == dt, name, " has dtype ", t.scalar_type(), ", expected ", dt);
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-}
-void check_numel(const Tensor& t, const char* name, int64_t n) {
-  TORCH_CHECK(t.numel() >= n, name, " has ", t.numel(), " elements, need >= ", n);
-}
-const float* fptr(const OptT& t, const char* name, int64_t n) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  check_dev(*t, name, at::kFloat);
-  check_numel(*t, name, n);
-  return t->data_ptr<float>();
-}
-float* fptr_mut(const OptT& t, const char* name, int64_t n) { return const_cast<float*>(fptr(t, name, n)); }
-const int* iptr(const OptT& t, const char* name, int64_t n) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  check_dev(*t, name, at::kInt);
-  check_numel(*t, name, n);
-  return t->data_ptr<int>();
-}
-
 int64_t flat_size(int64_t D, int64_t H, int64_t A, bool log_std) {
   return H * D + H + H * H + H + A * H + A + (log_std ? A : 0);
-}
-
-void check_rc(int rc, const char* what) {
-  TORCH_CHECK(rc == 0, what, " failed with code ", rc, " (", (rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad argument"), ")");
 }
 
 void mlp_forward(int64_t mode, const Tensor& params, const Tensor& X, int64_t A, int64_t H, const OptT& mask,
                  const OptT& act_in, const OptT& actc_in, const OptT& act_out, const OptT& actc_out,
                  const Tensor& out0, const OptT& out1, const OptT& logits_out, int64_t seed, int64_t step,
                  int64_t row_offset, const OptT& gate) {
-  check_dev(params, "params", at::kFloat);
-  check_dev(X, "X", at::kFloat);
+  check(params, "params", at::kFloat);
+  check(X, "X", at::kFloat);
   TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
   const int64_t B = X.size(0), D = X.size(1);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  TORCH_CHECK(mode >= 0 && mode <= 5, "bad mode");
-  const bool gauss = mode == 4 || mode == 5;
-  const int64_t Aeff = mode == 0 ? 1 : A;
+  TORCH_CHECK(mode >= MODE_VALUE && mode <= MODE_GAUSS_EVAL, "bad mode");
+  const bool gauss = mode == MODE_GAUSS_SAMPLE || mode == MODE_GAUSS_EVAL;
+  const int64_t Aeff = mode == MODE_VALUE ? 1 : A;
   check_numel(params, "params", flat_size(D, H, Aeff, gauss));
-  check_dev(out0, "out0", at::kFloat);
-  check_numel(out0, "out0", B);
-  const float* m = fptr(mask, "mask", B * A);
-  const int* ai = iptr(act_in, "act_in", mode == 2 ? B : 0);
-  const float* ci = fptr(actc_in, "actc_in", mode == 5 ? B * A : 0);
-  if (mode == 2) TORCH_CHECK(ai != nullptr, "act_in required for CAT_EVAL");
-  if (mode == 5) TORCH_CHECK(ci != nullptr, "actc_in required for GAUSS_EVAL");
-  int* ao = const_cast<int*>(iptr(act_out, "act_out", mode == 1 ? B : 0));
-  if (mode == 1) TORCH_CHECK(ao != nullptr, "act_out required for CAT_SAMPLE");
-  float* co = fptr_mut(actc_out, "actc_out", mode == 4 ? B * A : 0);
-  if (mode == 4) TORCH_CHECK(co != nullptr, "actc_out required for GAUSS_SAMPLE");
-  float* o1 = fptr_mut(out1, "out1", B);
-  float* lo = fptr_mut(logits_out, "logits_out", B * A);
-  if (mode == 3) TORCH_CHECK(lo != nullptr, "logits_out required for LOGITS");
-  const float* gt = fptr(gate, "gate", B);
-  TORCH_CHECK(gt == nullptr || mode == 0, "gate applies to the VALUE mode only");
+  check(out0, "out0", at::kFloat, B);
+  const float* m = opt_ptr<const float>(mask, "mask", at::kFloat, B * A);
+  const int* ai = opt_ptr<const int>(act_in, "act_in", at::kInt, mode == MODE_CAT_EVAL ? B : 0);
+  const float* ci = opt_ptr<const float>(actc_in, "actc_in", at::kFloat, mode == MODE_GAUSS_EVAL ? B * A : 0);
+  if (mode == MODE_CAT_EVAL) TORCH_CHECK(ai != nullptr, "act_in required for CAT_EVAL");
+  if (mode == MODE_GAUSS_EVAL) TORCH_CHECK(ci != nullptr, "actc_in required for GAUSS_EVAL");
+  int* ao = opt_ptr<int>(act_out, "act_out", at::kInt, mode == MODE_CAT_SAMPLE ? B : 0);
+  if (mode == MODE_CAT_SAMPLE) TORCH_CHECK(ao != nullptr, "act_out required for CAT_SAMPLE");
+  float* co = opt_ptr<float>(actc_out, "actc_out", at::kFloat, mode == MODE_GAUSS_SAMPLE ? B * A : 0);
+  if (mode == MODE_GAUSS_SAMPLE) TORCH_CHECK(co != nullptr, "actc_out required for GAUSS_SAMPLE");
+  float* o1 = opt_ptr<float>(out1, "out1", at::kFloat, B);
+  float* lo = opt_ptr<float>(logits_out, "logits_out", at::kFloat, B * A);
+  if (mode == MODE_LOGITS) TORCH_CHECK(lo != nullptr, "logits_out required for LOGITS");
+  const float* gt = opt_ptr<const float>(gate, "gate", at::kFloat, B);
+  TORCH_CHECK(gt == nullptr || mode == MODE_VALUE, "gate applies to the VALUE mode only");
   const int rc = rrl_mlp_forward((int)mode, params.data_ptr<float>(), X.data_ptr<float>(), (int)B, (int)D, (int)A,
                                  (int)H, m, ai, ci, ao, co, out0.data_ptr<float>(), o1, lo, (uint64_t)seed,
                                  (uint64_t)step, (uint32_t)row_offset, gt, nullptr, nullptr, nullptr, num_cus(),
@@ -179,40 +101,38 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
               const OptT& act, const OptT& actc, const OptT& adv, const OptT& ret, const OptT& logp_old,
               const OptT& adv_stats, double inv_B, double clip_eps, double ent_coef, const Tensor& grad_slab,
               const Tensor& loss_slab, const OptT& nvalid, const OptT& inv_B_dev) {
-  check_dev(params, "params", at::kFloat);
-  check_dev(X, "X", at::kFloat);
+  check(params, "params", at::kFloat);
+  check(X, "X", at::kFloat);
   TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
   const int64_t B = X.size(0), D = X.size(1);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  TORCH_CHECK(head >= 0 && head <= 4, "bad head");
+  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_PG_GAUSS, "bad head");
   TORCH_CHECK(B * std::max<int64_t>(D, A) < (int64_t)INT32_MAX, "batch too large for 32-bit row indexing");
-  const bool gauss = head == 3 || head == 4;
-  const bool cat = head == 0 || head == 2;
-  const int64_t Aeff = head == 1 ? 1 : A;
-  const int64_t P = flat_size(D, H, Aeff, gauss);
+  const bool gauss = head == HEAD_PPO_GAUSS || head == HEAD_PG_GAUSS;
+  const bool cat = head == HEAD_PG_CAT || head == HEAD_PPO_CAT;
+  const bool value = head == HEAD_VALUE_MSE;
+  const int64_t P = flat_size(D, H, value ? 1 : A, gauss);
   check_numel(params, "params", P);
   const int64_t nslab = mlp_grad_slabs(B);
-  check_dev(grad_slab, "grad_slab", at::kFloat);
-  check_numel(grad_slab, "grad_slab", nslab * P);
-  check_dev(loss_slab, "loss_slab", at::kFloat);
-  check_numel(loss_slab, "loss_slab", nslab * 8);
-  const float* m = fptr(mask, "mask", B * A);
-  const int* a = iptr(act, "act", cat ? B : 0);
+  check(grad_slab, "grad_slab", at::kFloat, nslab * P);
+  check(loss_slab, "loss_slab", at::kFloat, nslab * 8);
+  const float* m = opt_ptr<const float>(mask, "mask", at::kFloat, B * A);
+  const int* a = opt_ptr<const int>(act, "act", at::kInt, cat ? B : 0);
   if (cat) TORCH_CHECK(a != nullptr, "act required for categorical heads");
-  const float* ac = fptr(actc, "actc", gauss ? B * A : 0);
+  const float* ac = opt_ptr<const float>(actc, "actc", at::kFloat, gauss ? B * A : 0);
   if (gauss) TORCH_CHECK(ac != nullptr, "actc required for Gaussian heads");
-  const float* ad = fptr(adv, "adv", B);
-  if (head != 1) TORCH_CHECK(ad != nullptr, "adv required for policy heads");
-  const float* rt = fptr(ret, "ret", B);
-  if (head == 1) TORCH_CHECK(rt != nullptr, "ret required for the value head");
-  const float* lpo = fptr(logp_old, "logp_old", B);
-  if (head == 2 || head == 3) TORCH_CHECK(lpo != nullptr, "logp_old required for PPO heads");
-  const float* st = fptr(adv_stats, "adv_stats", 3);
+  const float* ad = opt_ptr<const float>(adv, "adv", at::kFloat, B);
+  if (!value) TORCH_CHECK(ad != nullptr, "adv required for policy heads");
+  const float* rt = opt_ptr<const float>(ret, "ret", at::kFloat, B);
+  if (value) TORCH_CHECK(rt != nullptr, "ret required for the value head");
+  const float* lpo = opt_ptr<const float>(logp_old, "logp_old", at::kFloat, B);
+  if (head == HEAD_PPO_CAT || head == HEAD_PPO_GAUSS) TORCH_CHECK(lpo != nullptr, "logp_old required for PPO heads");
+  const float* st = opt_ptr<const float>(adv_stats, "adv_stats", at::kFloat, 3);
   // device-side batch shape (graph replays with a changing batch): valid rows / 1 / global rows
-  const int* nv = iptr(nvalid, "nvalid", 1);
-  const float* ibd = fptr(inv_B_dev, "inv_B_dev", 1);
+  const int* nv = opt_ptr<const int>(nvalid, "nvalid", at::kInt, 1);
+  const float* ibd = opt_ptr<const float>(inv_B_dev, "inv_B_dev", at::kFloat, 1);
   const int rc = rrl_mlp_grad((int)head, params.data_ptr<float>(), X.data_ptr<float>(), (int)B, (int)D, (int)A,
                               (int)H, m, a, ac, ad, rt, lpo, st, (float)inv_B, (float)clip_eps, (float)ent_coef,
                               grad_slab.data_ptr<float>(), loss_slab.data_ptr<float>(), (int)P, nv, ibd, num_cus(),
@@ -226,21 +146,17 @@ void gae_scan_tm(const Tensor& rew, const Tensor& done, const OptT& val, const O
                  const Tensor& ret, const Tensor& stats_part, const OptT& stats_out, double gamma, double lam,
                  const std::vector<std::tuple<Tensor, int64_t>>& counters) {
   // rew [T, N] or [K, T, N] (K actor blocks of one learner shard); val [K*T*N + K*N]
-  check_dev(rew, "rew", at::kFloat);
+  check(rew, "rew", at::kFloat);
   TORCH_CHECK(rew.dim() == 2 || rew.dim() == 3, "rew must be [T, N] or [K, T, N]");
   const int64_t K = rew.dim() == 3 ? rew.size(0) : 1;
   const int64_t T = rew.size(rew.dim() - 2), N = rew.size(rew.dim() - 1);
-  check_dev(done, "done", at::kFloat);
-  check_numel(done, "done", K * T * N);
-  const float* v = fptr(val, "val", K * (T + 1) * N);
-  const float* tv = fptr(tval, "tval", K * T * N);
-  check_dev(adv, "adv", at::kFloat);
-  check_numel(adv, "adv", K * T * N);
-  check_dev(ret, "ret", at::kFloat);
-  check_numel(ret, "ret", K * T * N);
-  check_dev(stats_part, "stats_part", at::kFloat);
-  check_numel(stats_part, "stats_part", scan_tm_parts(K * N) * 3);
-  float* so = fptr_mut(stats_out, "stats_out", 3);
+  check(done, "done", at::kFloat, K * T * N);
+  const float* v = opt_ptr<const float>(val, "val", at::kFloat, K * (T + 1) * N);
+  const float* tv = opt_ptr<const float>(tval, "tval", at::kFloat, K * T * N);
+  check(adv, "adv", at::kFloat, K * T * N);
+  check(ret, "ret", at::kFloat, K * T * N);
+  check(stats_part, "stats_part", at::kFloat, scan_tm_parts(K * N) * 3);
+  float* so = opt_ptr<float>(stats_out, "stats_out", at::kFloat, 3);
   // device step counters advanced by the same launch (int64 scalars on this device)
   TORCH_CHECK(counters.size() <= 3, "gae_scan_tm: at most 3 counters");
   long long* cnt[3] = {nullptr, nullptr, nullptr};
@@ -261,19 +177,15 @@ int64_t scan_flat_blocks(int64_t L) { return rrl_scan_flat_blocks((int)L); }
 
 void scan_flat(const Tensor& rew, const Tensor& done, const OptT& val, const OptT& boot, const Tensor& adv,
                const Tensor& ret, const Tensor& work, const OptT& stats_out, double gamma, double lam) {
-  check_dev(rew, "rew", at::kFloat);
+  check(rew, "rew", at::kFloat);
   const int64_t L = rew.numel();
-  check_dev(done, "done", at::kFloat);
-  check_numel(done, "done", L);
-  const float* v = fptr(val, "val", L);
-  const float* b = fptr(boot, "boot", L);
-  check_dev(adv, "adv", at::kFloat);
-  check_numel(adv, "adv", L);
-  check_dev(ret, "ret", at::kFloat);
-  check_numel(ret, "ret", L);
-  check_dev(work, "work", at::kFloat);
-  check_numel(work, "work", scan_flat_blocks(L) * 9);
-  float* so = fptr_mut(stats_out, "stats_out", 3);
+  check(done, "done", at::kFloat, L);
+  const float* v = opt_ptr<const float>(val, "val", at::kFloat, L);
+  const float* b = opt_ptr<const float>(boot, "boot", at::kFloat, L);
+  check(adv, "adv", at::kFloat, L);
+  check(ret, "ret", at::kFloat, L);
+  check(work, "work", at::kFloat, scan_flat_blocks(L) * 9);
+  float* so = opt_ptr<float>(stats_out, "stats_out", at::kFloat, 3);
   const int rc = rrl_scan_flat(rew.data_ptr<float>(), done.data_ptr<float>(), v, b, adv.data_ptr<float>(),
                                ret.data_ptr<float>(), work.data_ptr<float>(), so, (int)L, (float)gamma, (float)lam,
                                cur_stream());
@@ -281,16 +193,15 @@ void scan_flat(const Tensor& rew, const Tensor& done, const OptT& val, const Opt
 }
 
 void stats_reduce(const Tensor& part, const Tensor& out) {
-  check_dev(part, "part", at::kFloat);
+  check(part, "part", at::kFloat);
   TORCH_CHECK(part.numel() % 3 == 0, "part must be [n, 3]");
-  check_dev(out, "out", at::kFloat);
-  check_numel(out, "out", 3);
+  check(out, "out", at::kFloat, 3);
   check_rc(rrl_stats_reduce(part.data_ptr<float>(), (int)(part.numel() / 3), out.data_ptr<float>(), cur_stream()),
            "stats_reduce");
 }
 
 void column_sums(const Tensor& part, int64_t cols, const Tensor& out) {
-  check_dev(part, "part", at::kFloat);
+  check(part, "part", at::kFloat);
   TORCH_CHECK(part.dim() == 2 && part.is_contiguous(), "column_sums: part must be a contiguous [rows, ld] tensor");
   TORCH_CHECK(cols >= 1 && cols <= 8 && cols <= part.size(1), "column_sums: 1 <= cols <= min(8, ld)");
   TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kDouble && out.numel() >= cols && out.is_contiguous(),
@@ -303,25 +214,23 @@ void column_sums(const Tensor& part, int64_t cols, const Tensor& out) {
 void adam(const Tensor& param, const Tensor& m, const Tensor& v, const OptT& grad, const OptT& slab,
           const OptT& grad_out, const Tensor& step, const Tensor& ticket, double lr, double beta1, double beta2,
           double eps, double grad_scale, double weight_decay, int64_t step_add, int64_t step_inc) {
-  check_dev(param, "param", at::kFloat);
+  check(param, "param", at::kFloat);
   const int64_t P = param.numel();
-  check_dev(m, "m", at::kFloat);
-  check_numel(m, "m", P);
-  check_dev(v, "v", at::kFloat);
-  check_numel(v, "v", P);
-  const float* g = fptr(grad, "grad", P);
+  check(m, "m", at::kFloat, P);
+  check(v, "v", at::kFloat, P);
+  const float* g = opt_ptr<const float>(grad, "grad", at::kFloat, P);
   const float* s = nullptr;
   int64_t nslab = 0;
   if (slab.has_value() && slab->defined()) {
-    check_dev(*slab, "slab", at::kFloat);
+    check(*slab, "slab", at::kFloat);
     TORCH_CHECK(slab->dim() == 2 && slab->size(1) == P, "slab must be [nslab, P]");
     nslab = slab->size(0);
     s = slab->data_ptr<float>();
   }
   TORCH_CHECK((g != nullptr) != (s != nullptr), "exactly one of grad / slab must be given");
-  float* go = fptr_mut(grad_out, "grad_out", P);
-  check_dev(step, "step", at::kInt);
-  check_dev(ticket, "ticket", at::kInt);
+  float* go = opt_ptr<float>(grad_out, "grad_out", at::kFloat, P);
+  check(step, "step", at::kInt);
+  check(ticket, "ticket", at::kInt);
   const int rc = rrl_adam(param.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), g, s, (int)nslab, go,
                           step.data_ptr<int>(), reinterpret_cast<unsigned*>(ticket.data_ptr<int>()), (int)P, (float)lr,
                           (float)beta1, (float)beta2, (float)eps, (float)grad_scale, (float)weight_decay,
@@ -330,10 +239,9 @@ void adam(const Tensor& param, const Tensor& m, const Tensor& v, const OptT& gra
 }
 
 void reduce_slabs(const Tensor& slab, double scale, const Tensor& out) {
-  check_dev(slab, "slab", at::kFloat);
+  check(slab, "slab", at::kFloat);
   TORCH_CHECK(slab.dim() == 2, "slab must be [nslab, P]");
-  check_dev(out, "out", at::kFloat);
-  check_numel(out, "out", slab.size(1));
+  check(out, "out", at::kFloat, slab.size(1));
   check_rc(rrl_reduce_slabs(slab.data_ptr<float>(), (int)slab.size(0), (int)slab.size(1), (float)scale,
                             out.data_ptr<float>(), cur_stream()),
            "reduce_slabs");
@@ -376,7 +284,7 @@ void payload_verify(const Tensor& sums, const Tensor& hdr, int64_t ck_col, int64
               ld, "] for checksum column ", ck_col);
   TORCH_CHECK(sums.is_cuda() && sums.scalar_type() == at::kLong && sums.is_contiguous() && sums.numel() == 2 * K,
               "payload_verify: sums must be a contiguous int64 [K, 2] device tensor");
-  check_dev(status, "status", at::kInt);
+  check(status, "status", at::kInt);
   TORCH_CHECK(status.numel() == K, "payload_verify: status must have K elements");
   check_rc(rrl_payload_verify(reinterpret_cast<const unsigned long long*>(sums.data_ptr<int64_t>()),
                               hdr.data_ptr<double>(), (int)ld, (int)ck_col, (int)K, (double)expected_seq,
@@ -392,6 +300,22 @@ std::tuple<int64_t, int64_t, int64_t, int64_t> env_dims(int64_t env) {
 
 int64_t rollout_grid(int64_t N) { return rrl_rollout_grid((int)N, num_cus()); }
 
+// The buffers rollout() and rollout_cont() have in common, for T steps of N envs with D observation
+// and NS state floats each; returns tobs_buf's pointer (null when absent).
+float* check_rollout_bufs(int64_t T, int64_t N, int64_t D, int64_t NS, const Tensor& state, const Tensor& ep_len,
+                          const Tensor& ep_ret, const Tensor& obs_buf, const Tensor& logp_buf, const Tensor& rew_buf,
+                          const Tensor& done_buf, const Tensor& ep_stats, const OptT& tobs_buf) {
+  check(state, "state", at::kFloat, N * NS);
+  check(ep_len, "ep_len", at::kInt, N);
+  check(ep_ret, "ep_ret", at::kFloat, N);
+  check(obs_buf, "obs_buf", at::kFloat, (T + 1) * N * D);
+  check(logp_buf, "logp_buf", at::kFloat, T * N);
+  check(rew_buf, "rew_buf", at::kFloat, T * N);
+  check(done_buf, "done_buf", at::kFloat, T * N);
+  check(ep_stats, "ep_stats", at::kFloat, rollout_grid(N) * 8);
+  return opt_ptr<float>(tobs_buf, "tobs_buf", at::kFloat, T * N * D);
+}
+
 void rollout(int64_t env, const Tensor& params, int64_t H, const Tensor& state, const Tensor& ep_len,
              const Tensor& ep_ret, const Tensor& obs_buf, const Tensor& act_buf, const Tensor& logp_buf,
              const Tensor& rew_buf, const Tensor& done_buf, const OptT& tobs_buf, const Tensor& ep_stats,
@@ -399,28 +323,12 @@ void rollout(int64_t env, const Tensor& params, int64_t H, const Tensor& state, 
   auto [D, A, NS, ms] = env_dims(env);
   (void)ms;
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  check_dev(params, "params", at::kFloat);
-  check_numel(params, "params", flat_size(D, H, A, false));
-  check_dev(act_buf, "act_buf", at::kInt);
+  check(params, "params", at::kFloat, flat_size(D, H, A, false));
+  check(act_buf, "act_buf", at::kInt);
   TORCH_CHECK(act_buf.dim() == 2, "act_buf must be [T, N]");
   const int64_t T = act_buf.size(0), N = act_buf.size(1);
-  check_dev(state, "state", at::kFloat);
-  check_numel(state, "state", N * NS);
-  check_dev(ep_len, "ep_len", at::kInt);
-  check_numel(ep_len, "ep_len", N);
-  check_dev(ep_ret, "ep_ret", at::kFloat);
-  check_numel(ep_ret, "ep_ret", N);
-  check_dev(obs_buf, "obs_buf", at::kFloat);
-  check_numel(obs_buf, "obs_buf", (T + 1) * N * D);
-  check_dev(logp_buf, "logp_buf", at::kFloat);
-  check_numel(logp_buf, "logp_buf", T * N);
-  check_dev(rew_buf, "rew_buf", at::kFloat);
-  check_numel(rew_buf, "rew_buf", T * N);
-  check_dev(done_buf, "done_buf", at::kFloat);
-  check_numel(done_buf, "done_buf", T * N);
-  check_dev(ep_stats, "ep_stats", at::kFloat);
-  check_numel(ep_stats, "ep_stats", rollout_grid(N) * 8);
-  float* tob = fptr_mut(tobs_buf, "tobs_buf", T * N * D);
+  float* tob = check_rollout_bufs(T, N, D, NS, state, ep_len, ep_ret, obs_buf, logp_buf, rew_buf, done_buf, ep_stats,
+                                  tobs_buf);
   const int rc = rrl_rollout((int)env, params.data_ptr<float>(), (int)N, (int)T, (int)H, state.data_ptr<float>(),
                              ep_len.data_ptr<int>(), ep_ret.data_ptr<float>(), obs_buf.data_ptr<float>(),
                              act_buf.data_ptr<int>(), logp_buf.data_ptr<float>(), rew_buf.data_ptr<float>(),
@@ -436,32 +344,15 @@ void rollout_cont(int64_t env, const Tensor& params, const Tensor& env_consts, i
                   const Tensor& ep_stats, int64_t seed, int64_t step0, bool reset_all, int64_t max_steps) {
   auto [D, A, NS, ms] = env_dims(env);
   (void)ms;
-  TORCH_CHECK(env == 4, "rollout_cont supports the continuous device env 4 (HalfCheetahSynth)");
+  TORCH_CHECK(env == ENV_HALFCHEETAH, "rollout_cont supports the continuous device env 4 (HalfCheetahSynth)");
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  check_dev(params, "params", at::kFloat);
-  check_numel(params, "params", flat_size(D, H, A, true));
-  check_dev(env_consts, "env_consts", at::kFloat);
-  check_numel(env_consts, "env_consts", 17 * 17 + 17 * 6);
-  check_dev(act_buf, "act_buf", at::kFloat);
+  check(params, "params", at::kFloat, flat_size(D, H, A, true));
+  check(env_consts, "env_consts", at::kFloat, 17 * 17 + 17 * 6);
+  check(act_buf, "act_buf", at::kFloat);
   TORCH_CHECK(act_buf.dim() == 3 && act_buf.size(2) == A, "act_buf must be [T, N, A]");
   const int64_t T = act_buf.size(0), N = act_buf.size(1);
-  check_dev(state, "state", at::kFloat);
-  check_numel(state, "state", N * NS);
-  check_dev(ep_len, "ep_len", at::kInt);
-  check_numel(ep_len, "ep_len", N);
-  check_dev(ep_ret, "ep_ret", at::kFloat);
-  check_numel(ep_ret, "ep_ret", N);
-  check_dev(obs_buf, "obs_buf", at::kFloat);
-  check_numel(obs_buf, "obs_buf", (T + 1) * N * D);
-  check_dev(logp_buf, "logp_buf", at::kFloat);
-  check_numel(logp_buf, "logp_buf", T * N);
-  check_dev(rew_buf, "rew_buf", at::kFloat);
-  check_numel(rew_buf, "rew_buf", T * N);
-  check_dev(done_buf, "done_buf", at::kFloat);
-  check_numel(done_buf, "done_buf", T * N);
-  check_dev(ep_stats, "ep_stats", at::kFloat);
-  check_numel(ep_stats, "ep_stats", rollout_grid(N) * 8);
-  float* tob = fptr_mut(tobs_buf, "tobs_buf", T * N * D);
+  float* tob = check_rollout_bufs(T, N, D, NS, state, ep_len, ep_ret, obs_buf, logp_buf, rew_buf, done_buf, ep_stats,
+                                  tobs_buf);
   check_rc(rrl_rollout_cont((int)env, params.data_ptr<float>(), env_consts.data_ptr<float>(), (int)N, (int)T, (int)H,
                             state.data_ptr<float>(), ep_len.data_ptr<int>(), ep_ret.data_ptr<float>(),
                             obs_buf.data_ptr<float>(), act_buf.data_ptr<float>(), logp_buf.data_ptr<float>(),
@@ -522,6 +413,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rollout_grid", &rollout_grid);
   m.def("rollout", &rollout);
   m.def("rollout_cont", &rollout_cont);
+  // the enumerators of api.h by name: the Python tables (ops/mlp.py, DEVICE_ENVS) are tested against these
+#define RRL_ENUM(e) pybind11::arg(#e) = (int)rrl::e
+  m.attr("FWD_MODES") = pybind11::dict(RRL_ENUM(MODE_VALUE), RRL_ENUM(MODE_CAT_SAMPLE), RRL_ENUM(MODE_CAT_EVAL),
+                                       RRL_ENUM(MODE_LOGITS), RRL_ENUM(MODE_GAUSS_SAMPLE), RRL_ENUM(MODE_GAUSS_EVAL));
+  m.attr("GRAD_HEADS") = pybind11::dict(RRL_ENUM(HEAD_PG_CAT), RRL_ENUM(HEAD_VALUE_MSE), RRL_ENUM(HEAD_PPO_CAT),
+                                        RRL_ENUM(HEAD_PPO_GAUSS), RRL_ENUM(HEAD_PG_GAUSS));
+  m.attr("ENV_IDS") = pybind11::dict(RRL_ENUM(ENV_CARTPOLE), RRL_ENUM(ENV_MOUNTAINCAR), RRL_ENUM(ENV_ACROBOT),
+                                     RRL_ENUM(ENV_LUNARLANDER), RRL_ENUM(ENV_HALFCHEETAH));
+#undef RRL_ENUM
   register_cnn_ops(m);
   register_rollout_ops(m);
 }

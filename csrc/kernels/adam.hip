@@ -9,6 +9,7 @@
 // step_add = k and step_inc = 0 (no ticket at all) for k < K - 1 and step_inc = K on the last
 // one: the ticket's 271-way serialised device-scope atomic (~3 us at the end of every update,
 // MI355X_MICROARCH.md fanin) is paid once per loop instead of once per update.
+#include "api.h"
 #include "common.h"
 
 namespace rrl {

@@ -1,0 +1,180 @@
+// The C ABI of the gfx950 kernels: every extern "C" entry point of csrc/kernels/*.hip and the
+// integer vocabularies that cross it.  This is the only place a rrl_* prototype is written: the
+// .hip file that defines an entry point includes it (a definition that disagrees is a compile
+// error) and so does every caller (csrc/bindings, csrc/runtime).  Plain C++: no HIP or torch
+// include; a stream is a hipStream_t passed as void*.  Unless a comment says otherwise an entry
+// point returns 0, a hipError_t (> 0) or a negative code for arguments it does not support.
+#pragma once
+#include <cstdint>
+
+namespace rrl {
+
+enum FwdMode : int {
+  MODE_VALUE = 0,
+  MODE_CAT_SAMPLE = 1,
+  MODE_CAT_EVAL = 2,
+  MODE_LOGITS = 3,
+  MODE_GAUSS_SAMPLE = 4,
+  MODE_GAUSS_EVAL = 5,
+};
+
+enum GradHead : int {
+  HEAD_PG_CAT = 0,     // REINFORCE: loss = -mean(logp(a) * adv)
+  HEAD_VALUE_MSE = 1,  // baseline: loss = mean((v - ret)^2)
+  HEAD_PPO_CAT = 2,    // PPO clipped surrogate, categorical
+  HEAD_PPO_GAUSS = 3,  // PPO clipped surrogate, diagonal Gaussian
+  HEAD_PG_GAUSS = 4,   // REINFORCE / A2C with a Gaussian policy
+};
+
+enum EnvId : int { ENV_CARTPOLE = 0, ENV_MOUNTAINCAR = 1, ENV_ACROBOT = 2, ENV_LUNARLANDER = 3, ENV_HALFCHEETAH = 4 };
+
+}  // namespace rrl
+
+extern "C" {
+
+// ---- mlp_forward.hip
+// mode: a FwdMode
+int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D, int A, int H, const float* mask,
+                    const int* act_in, const float* actc_in, int* act_out, float* actc_out, float* out0,
+                    float* out1, float* logits_out, uint64_t seed, uint64_t step, uint32_t row_offset,
+                    const float* gate, float* x_copy, int* act_host, float* actc_host, int num_cu, void* stream);
+// 1 = bf16x6 weight-stationary split kernel, 0 = fp32 MFMA; returns the previous mode (-1 queries)
+int rrl_set_value_fwd_mode(int mode);
+
+// ---- mlp_grad.hip
+// head: a GradHead
+int rrl_mlp_grad(int head, const float* params, const float* X, int B, int D, int A, int H, const float* mask,
+                 const int* act, const float* actc, const float* adv, const float* ret, const float* logp_old,
+                 const float* adv_stats, float inv_B, float clip_eps, float ent_coef, float* grad_slab,
+                 float* loss_slab, int P, const int* nvalid, const float* inv_B_dev, int num_cu, void* stream);
+// number of partial-gradient slabs (== grid size) rrl_mlp_grad uses
+int rrl_mlp_grad_slabs(int B, int num_cu);
+// 1 = bf16x6 weight-stationary kernels, 0 = fp32 MFMA; returns the previous mode (-1 queries)
+int rrl_set_value_grad_mode(int mode);
+
+// ---- value_grad.hip
+void rrl_set_value_grad_stamps(void* buf);
+int rrl_set_value_grad_tune(int t);  // returns the previous variant
+
+// ---- scan.hip
+int rrl_scan_tm_parts(int N);
+// stats_part: rrl_scan_tm_parts(K * N) x 3 floats; cnt / inc: ncnt <= 3 device counters advanced by the launch
+int rrl_gae_scan_tm(const float* rew, const float* done, const float* val, const float* tval, float* adv,
+                    float* ret, float* stats_part, float* stats_out, int K, int T, int N, float gamma, float lam,
+                    long long* const* cnt, const long long* inc, int ncnt, void* stream);
+int rrl_scan_flat_blocks(int L);
+// work: rrl_scan_flat_blocks(L) x 9 floats
+int rrl_scan_flat(const float* rew, const float* done, const float* val, const float* boot, float* adv, float* ret,
+                  float* work, float* stats_out, int L, float gamma, float lam, void* stream);
+int rrl_stats_reduce(const float* part, int nparts, float* out, void* stream);
+int rrl_column_sums(const float* part, int rows, int ld, int cols, double* out, void* stream);
+
+// ---- adam.hip
+// t = *step + step_add + 1; the counter advances by step_inc
+int rrl_adam(float* param, float* m, float* v, const float* grad, const float* slab, int nslab, float* grad_out,
+             int* step, unsigned* ticket, int P, float lr, float beta1, float beta2, float eps, float grad_scale,
+             float weight_decay, int step_add, int step_inc, void* stream);
+int rrl_reduce_slabs(const float* slab, int nslab, int P, float scale, float* out, void* stream);
+
+// ---- checksum.hip
+int rrl_payload_checksum_blocks(const unsigned long long* words, int nseg, int num_cu);
+// part: rrl_payload_checksum_blocks() x 2 words of device workspace; out: two 64-bit words on the device
+int rrl_payload_checksum(const void* const* ptrs, const unsigned long long* words, int nseg,
+                         unsigned long long* part, unsigned long long* out, int num_cu, void* stream);
+// status[k] bits: 1 checksum mismatch, 2 seq != expected, 4 version outside [lo, hi]
+int rrl_payload_verify(const unsigned long long* sums, const double* hdr, int ld, int ck_col, int K,
+                       double expected_seq, double lo, double hi, int* status, void* stream);
+
+// ---- rollout.hip
+// env: an EnvId; nonzero for an unknown one
+int rrl_env_dims(int env, int* D, int* A, int* NS, int* max_steps);
+int rrl_rollout_grid(int N, int num_cu);
+int rrl_rollout(int env, const float* params, int N, int T, int H, float* state, int* ep_len, float* ep_ret,
+                float* obs_buf, int* act_buf, float* logp_buf, float* rew_buf, float* done_buf, float* tobs_buf,
+                float* ep_stats, uint64_t seed, uint64_t step0, int reset_all, int max_steps, int num_cu,
+                void* stream);
+// continuous-action envs (ENV_HALFCHEETAH)
+int rrl_rollout_cont(int env, const float* params, const float* env_consts, int N, int T, int H, float* state,
+                     int* ep_len, float* ep_ret, float* obs_buf, float* act_buf, float* logp_buf, float* rew_buf,
+                     float* done_buf, float* tobs_buf, float* ep_stats, uint64_t seed, uint64_t step0,
+                     int reset_all, int max_steps, int num_cu, void* stream);
+
+// ---- cnn.hip (bf16 tensors as uint16_t)
+int rrl_conv_fwd(const void* x, int x_u8, const uint16_t* w, const float* b, uint16_t* y, int N, int H, int W,
+                 int C, int KH, int KW, int S, int Cout, int relu, float* work, long long work_elems, void* stream);
+int rrl_gemm_dgrad(const uint16_t* dy, const uint16_t* w, const uint16_t* mask, uint16_t* out, int M, int Cout,
+                   int K, void* stream);
+// -1 (nothing launched) for a geometry without an implicit-dgrad kernel
+int rrl_conv_dgrad(const uint16_t* dy, const uint16_t* w, const uint16_t* xact, uint16_t* dx, int N, int H, int W,
+                   int C, int KH, int KW, int S, int Cout, void* stream);
+int rrl_col2im_mask(const uint16_t* dcol, const uint16_t* xact, uint16_t* dx, int N, int H, int W, int C, int KH,
+                    int KW, int S, void* stream);
+int rrl_conv_wgrad(const uint16_t* dy, const void* x, int x_u8, float* part, float* bias_part, int splits, int N,
+                   int H, int W, int C, int KH, int KW, int S, int Cout, void* stream);
+// number of splits actually used for a reduction of length R
+int rrl_gemm_splits(int R, int splits);
+int rrl_sum_splits_multi(const float* const* parts, const int* splits, const long long* ns, float* const* outs,
+                         int count, void* stream);
+int rrl_sum_splits(const float* part, int splits, long long n, float* out, void* stream);
+int rrl_colsum(const uint16_t* y, int M, int C, float* part, int splits, void* stream);
+int rrl_sumsq(const float* x, long long n, float* work, int work_n, float* out, void* stream);
+// returns the number of partials written (> 0), or minus a hipError_t
+int rrl_sumsq_partial(const float* x, long long n, float* work, int work_n, void* stream);
+int rrl_adam_clip(float* p, float* m, float* v, const float* g, uint16_t* shadow, long long n, const float* norm_sq,
+                  float max_norm, float lr, float b1, float b2, float eps, int step, const long long* step_dev,
+                  int norm_parts, void* stream);
+int rrl_counter_add_n(long long* const* c, const long long* inc, int n, void* stream);
+int rrl_counter_add(long long* c, long long inc, void* stream);
+int rrl_to_bf16(const float* x, uint16_t* y, long long n, void* stream);
+// mode 0: rollout (sample act / logp / value), 1: training (dh, dhead, stats)
+int rrl_a2c_head(int mode, const uint16_t* h, const float* head_params, int B, int A, int32_t* act, float* logp,
+                 float* value, float* logits_out, unsigned long long seed, unsigned long long step,
+                 const unsigned long long* step_base, int row_offset, const int32_t* act_in, const float* adv,
+                 const float* ret, float inv_B, float vf_coef, float ent_coef, uint16_t* dh, float* dhead,
+                 float* stats, int grid, const float* part, int splits, const float* fc_b, uint16_t* h_out,
+                 void* stream);
+int rrl_head_wgrad(const uint16_t* h, const float* dhead, int B, int A, float* part, int nblk, void* stream);
+
+// ---- fc.hip
+// both *_part: return the number of splits used (> 0), negative on failure
+int rrl_fc_nt_part(const uint16_t* a, const uint16_t* b, float* part, int M, int N, int K, int splits, void* stream);
+int rrl_fc_nt_mask(const uint16_t* a, const uint16_t* b, const uint16_t* mask, uint16_t* out, int M, int N, int K,
+                   void* stream);
+int rrl_fc_tn_part(const uint16_t* x, const uint16_t* y, float* part, int R, int I, int J, int splits,
+                   const uint16_t* ones, float* bias_part, void* stream);
+int rrl_transpose_bf16(const uint16_t* in, uint16_t* out, int R, int C, void* stream);
+
+// ---- cnn_fused.hip
+int rrl_conv_stack_fwd(const uint8_t* x, const float* hist, const uint8_t* frames, const int32_t* fidx,
+                       const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2, const uint16_t* w3,
+                       const float* b3, uint16_t* y1, uint16_t* y2, uint16_t* y3, int N, int max_grid, void* stream);
+int rrl_conv3_bwd(const uint16_t* dy, const uint16_t* w, const uint16_t* xact, uint16_t* dx, float* part,
+                  float* bias_part, int N, int grid, int variant, void* stream);
+int rrl_conv2_bwd(const uint16_t* dy, const uint16_t* w, const uint16_t* xact, uint16_t* dx, float* part,
+                  float* bias_part, int N, int grid, int staged, void* stream);
+int rrl_conv1_wgrad8(const uint8_t* x, const float* hist, const uint8_t* frames, const int32_t* fidx,
+                     const uint16_t* dy, float* part, float* bias_part, int N, int grid, int T, void* stream);
+
+// ---- pong.hip
+int rrl_pong_state_size();  // floats of state per env
+int rrl_pong_step(float* state, const int32_t* act, float* rew, float* done, float* fin_ret, float* fin_len,
+                  float* ep_acc, int N, unsigned long long seed, unsigned long long step,
+                  const unsigned long long* step_base, int max_steps, int reset_all, float* hist_out, void* stream);
+// frames != nullptr: the frame-ring form (frames [R][N][7056], fidx [N][4]; obs unused)
+int rrl_pong_step_render(float* state, const int32_t* act, float* rew, float* done, float* fin_ret, float* fin_len,
+                         float* ep_acc, uint8_t* obs, int N, unsigned long long seed, unsigned long long step,
+                         const unsigned long long* step_base, int max_steps, int reset_all, uint8_t* frames,
+                         int32_t* fidx, int R, void* stream);
+int rrl_pong_ring_fill(float* state, uint8_t* frames, int32_t* fidx, int N, int R, unsigned long long step,
+                       const unsigned long long* step_base, void* stream);
+int rrl_pong_render_hist(const float* hist, uint8_t* obs, int N, void* stream);
+int rrl_pong_render(const float* state, uint8_t* obs, int N, void* stream);
+int rrl_pong_head_step_render(const float* part, int splits, const float* fc_b, const float* head_params, int A,
+                              uint16_t* h_out, int32_t* act, float* logp, float* value,
+                              unsigned long long sample_seed, unsigned long long sample_step,
+                              const unsigned long long* sample_base, float* state, float* rew, float* done,
+                              float* fin_ret, float* fin_len, float* ep_acc, uint8_t* obs, int N,
+                              unsigned long long seed, unsigned long long step, const unsigned long long* step_base,
+                              int max_steps, uint8_t* frames, int32_t* fidx, int R, void* stream);
+
+}  // extern "C"

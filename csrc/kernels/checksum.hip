@@ -18,6 +18,7 @@
 // one-workgroup finishing launch on the same stream sums the partials into the two result words
 // (integer adds commute: bit-deterministic for every grid).  No atomics: 2 x 2048 adds to the
 // same two words serialise at ~10 ns each and took 38 us for a 21 MB payload, ten times the read.
+#include "api.h"
 #include "common.h"
 
 namespace rrl {

@@ -12,6 +12,7 @@
 //             dX = col2im(dXc) * (X > 0)            gather form, no atomics
 //   wgrad     dW = dY^T . im2col(X)                 both operands via transposed reads,
 //                                                   split over batch x spatial -> fp32 partials
+#include "api.h"
 #include "gemm_bf16.h"
 #include "heads.h"
 #include "a2c_head.h"

@@ -26,6 +26,7 @@
 //   store frame n_j (prefetched into registers) -> LDS; prefetch frame n_{j+1}      | B0 .. B1
 //   copy out a2(n_{j-1}) and a3(n_{j-2}); conv1(n_j) -> A1                          | B1 .. B2
 //   copy out a1(n_j); A: conv2(n_j) -> A2[j & 1]; B: conv3(n_{j-1}) -> A3          | B2 .. B0
+#include "api.h"
 #include "gemm_bf16.h"
 #include "pong_render.h"
 

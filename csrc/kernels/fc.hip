@@ -34,6 +34,7 @@
 
 #include <type_traits>
 
+#include "api.h"
 #include "gemm_bf16.h"
 
 namespace rrl {

@@ -2,15 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace rrl {
+#include "api.h"  // GradHead
 
-enum GradHead : int {
-  HEAD_PG_CAT = 0,     // REINFORCE: loss = -mean(logp(a) * adv)
-  HEAD_VALUE_MSE = 1,  // baseline: loss = mean((v - ret)^2)
-  HEAD_PPO_CAT = 2,    // PPO clipped surrogate, categorical
-  HEAD_PPO_GAUSS = 3,  // PPO clipped surrogate, diagonal Gaussian
-  HEAD_PG_GAUSS = 4,   // REINFORCE / A2C with a Gaussian policy
-};
+namespace rrl {
 
 struct GradArgs {
   const float* params;

@@ -9,20 +9,12 @@
 //   MODE_LOGITS     : logits[b][A] (masked)        (debug / oracle checks)
 //   MODE_GAUSS_SAMPLE / MODE_GAUSS_EVAL: continuous policy (the reference's incomplete
 //                     ContinuousPolicyNetwork, kernel.py:49-75, completed).
+#include "api.h"
 #include "common.h"
 #include "grad_args.h"
 #include "heads.h"
 
 namespace rrl {
-
-enum FwdMode : int {
-  MODE_VALUE = 0,
-  MODE_CAT_SAMPLE = 1,
-  MODE_CAT_EVAL = 2,
-  MODE_LOGITS = 3,
-  MODE_GAUSS_SAMPLE = 4,
-  MODE_GAUSS_EVAL = 5,
-};
 
 struct FwdArgs {
   const float* params;
@@ -195,8 +187,6 @@ static int dispatch_mode(int mode, const FwdArgs& a, int grid, hipStream_t s) {
   }
   return -1;
 }
-
-extern "C" int rrl_set_value_grad_mode(int mode);  // mlp_grad.hip (-1 queries)
 
 // Value forward on the bf16x6 weight-stationary kernel (value_grad.hip FWD instance, ~0.6x the
 // fp32-MFMA kernel's time at H = 128) -- 1 -- or the fp32-MFMA kernel below -- 0.  The split

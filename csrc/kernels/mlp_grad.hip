@@ -18,6 +18,7 @@
 //
 // Each workgroup writes one partial-gradient slab (flat parameter order); the
 // reduce+Adam kernel (adam.hip) sums the slabs, so the result is deterministic.
+#include "api.h"
 #include "common.h"
 #include "heads.h"
 #include "grad_args.h"

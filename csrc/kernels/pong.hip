@@ -6,6 +6,7 @@
 // One thread per env steps the physics (pong_step_kernel); a second kernel renders the
 // 4-frame stack straight into the uint8 NHWC observation tensor the conv stack reads
 // (channel f = frame f, oldest first), so observations never touch the host.
+#include "api.h"
 #include "common.h"
 #include "pong_render.h"
 #include "a2c_head.h"

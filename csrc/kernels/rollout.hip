@@ -7,6 +7,7 @@
 // agent_zmq.rs:458-571) for the on-GPU actor.  Each wave owns 16 envs; every lane
 // of an env column keeps a replica of that env's state in registers, so the whole
 // step needs no cross-lane traffic except the two head reductions.
+#include "api.h"
 #include "common.h"
 #include "heads.h"
 #include "envs.h"
@@ -533,8 +534,6 @@ __global__ __launch_bounds__(256, 2) void rollout_cont_kernel(RolloutContArgs p)
 }  // namespace rrl
 
 using namespace rrl;
-
-enum EnvId : int { ENV_CARTPOLE = 0, ENV_MOUNTAINCAR = 1, ENV_ACROBOT = 2, ENV_LUNARLANDER = 3, ENV_HALFCHEETAH = 4 };
 
 extern "C" int rrl_env_dims(int env, int* D, int* A, int* NS, int* max_steps) {
   switch (env) {

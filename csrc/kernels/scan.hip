@@ -15,6 +15,7 @@
 //     over its own link), with the K x N bootstrap values after all of them;
 //   * flat [L] buffers of concatenated variable-length paths (the agent/trajectory API):
 //     a 3-phase parallel affine scan (thread chunk -> block scan -> block carries).
+#include "api.h"
 #include "common.h"
 
 namespace rrl {

@@ -44,6 +44,7 @@
 // form is bitwise reproducible.
 #include <type_traits>
 
+#include "api.h"
 #include "common.h"
 #include "grad_args.h"
 #include "heads.h"

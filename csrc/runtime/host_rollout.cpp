@@ -5,18 +5,11 @@
 #include <stdexcept>
 #include <string>
 
-extern "C" int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D, int A, int H,
-                               const float* mask, const int* act_in, const float* actc_in, int* act_out,
-                               float* actc_out, float* out0, float* out1, float* logits_out, uint64_t seed,
-                               uint64_t step, uint32_t row_offset, const float* gate, float* x_copy, int* act_host,
-                               float* actc_host, int num_cu, void* stream);
+#include "api.h"
 
 namespace rrl {
 
 namespace {
-
-constexpr int kModeCatSample = 1;
-constexpr int kModeGaussSample = 4;
 
 using Clock = std::chrono::steady_clock;
 double us_since(Clock::time_point t0) {
@@ -107,7 +100,7 @@ int HostRollout::run(const float* params, int H, int T, const RolloutBuffers& b,
       }
       const auto t1 = Clock::now();
       const size_t r = row_t + lo;
-      rc = rrl_mlp_forward(cont_ ? kModeGaussSample : kModeCatSample, params, obs_dev + r * D, nh, D, A, H, nullptr,
+      rc = rrl_mlp_forward(cont_ ? MODE_GAUSS_SAMPLE : MODE_CAT_SAMPLE, params, obs_dev + r * D, nh, D, A, H, nullptr,
                            nullptr, nullptr, cont_ ? nullptr : (int*)b.d_act + r,
                            cont_ ? (float*)b.d_act + r * A : nullptr, b.d_logp + r, nullptr, nullptr, seed,
                            step0 + (uint64_t)t, (uint32_t)lo, nullptr, b.d_obs + r * D,

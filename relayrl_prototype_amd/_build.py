@@ -3,8 +3,9 @@
 Two shared objects are produced next to this file:
 
 * ``_hip_ops<EXT>``  -- the gfx950 HIP kernels (``csrc/kernels/*.hip``, compiled by
-  ``hipcc --offload-arch=gfx950`` with a C ABI) linked with the PyTorch binding
-  ``csrc/bindings/hip_ops.cpp`` (host compiler, PyTorch-ROCm headers).
+  ``hipcc --offload-arch=gfx950`` with a C ABI, declared once in ``csrc/kernels/api.h``
+  for both sides) linked with the PyTorch binding ``csrc/bindings/hip_ops.cpp`` (host
+  compiler, PyTorch-ROCm headers).
 * ``_native<EXT>``   -- the host runtime in C++ (``csrc/host/*.cpp``): safetensors /
   trajectory codec, ZMTP transport, vectorised CPU environments; pybind11 only.
 
@@ -116,13 +117,16 @@ def build_hip(verbose=False, force=False) -> str:
     # host runtime linked into this module: the host-env rollout driver (csrc/runtime) and the
     # env pools it steps from C++ (csrc/host/vecenv.cpp, a private copy: hidden symbols)
     hdir, rdir = os.path.join(CSRC, "host"), os.path.join(CSRC, "runtime")
-    rt_headers = sorted(glob.glob(os.path.join(hdir, "*.h"))) + sorted(glob.glob(os.path.join(rdir, "*.h")))
+    # the runtime and the bindings call the kernels through csrc/kernels/api.h: its headers count too
+    rt_headers = (sorted(glob.glob(os.path.join(hdir, "*.h"))) + sorted(glob.glob(os.path.join(rdir, "*.h")))
+                  + headers + sorted(glob.glob(os.path.join(CSRC, "bindings", "*.h"))))
     for s in sorted(glob.glob(os.path.join(rdir, "*.cpp"))) + [os.path.join(hdir, "vecenv.cpp")]:
         o = os.path.join(odir, "rt_" + os.path.basename(s) + ".o")
         objs.append(o)
         if force or _newer(o, [s] + rt_headers):
             jobs.append([CXX, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-pthread",
-                         "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", hdir, "-I", rdir, "-c", s, "-o", o])
+                         "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", hdir, "-I", rdir, "-I", kdir,
+                         "-c", s, "-o", o])
     tinc, tcf, tld = _torch_flags()
     bindings = [binding] + sorted(b for b in glob.glob(os.path.join(CSRC, "bindings", "*_ops.cpp")) if b != binding)
     for bsrc in bindings:
@@ -130,7 +134,7 @@ def build_hip(verbose=False, force=False) -> str:
         objs.append(bo)
         if force or _newer(bo, [bsrc] + rt_headers):
             cmd = [CXX, "-O2", "-std=c++17", "-fPIC", "-DTORCH_EXTENSION_NAME=_hip_ops",
-                   "-DTORCH_API_INCLUDE_EXTENSION_H", "-I/opt/rocm/include", "-I", hdir, "-I", rdir] + tcf
+                   "-DTORCH_API_INCLUDE_EXTENSION_H", "-I/opt/rocm/include", "-I", hdir, "-I", rdir, "-I", kdir] + tcf
             for i in tinc + _py_includes():
                 cmd += ["-I", i]
             cmd += ["-c", bsrc, "-o", bo]

@@ -240,3 +240,18 @@ def test_scan_flat(cuda, L, baseline):
                               None if boot is None else boot.to(cuda), 0.99, 0.95)
     torch.testing.assert_close(a_g.cpu(), a_r, rtol=1e-3, atol=1e-3)
     torch.testing.assert_close(r_g.cpu(), r_r, rtol=1e-3, atol=1e-3)
+
+
+def test_python_enums_equal_the_kernel_header(cuda):
+    """FwdMode / GradHead / DEVICE_ENVS are hand-kept copies of csrc/kernels/api.h's enums (the CPU
+    oracle paths use them without the extension): they must equal the enumerators the extension
+    exports, name for name.  Launches nothing."""
+    from relayrl_prototype_amd import ops
+    from relayrl_prototype_amd.runtime.vec_trainer import DEVICE_ENVS
+
+    h = ops.hip()
+    assert {"MODE_" + m.name: int(m) for m in FwdMode} == dict(h.FWD_MODES)
+    assert {"HEAD_" + m.name: int(m) for m in GradHead} == dict(h.GRAD_HEADS)
+    # "LunarLanderSynth-v0" <-> ENV_LUNARLANDER: the gym id without its version and Synth suffix
+    envs = {"ENV_" + k.split("-")[0].replace("Synth", "").upper(): v for k, v in DEVICE_ENVS.items()}
+    assert len(envs) == len(DEVICE_ENVS) and envs == dict(h.ENV_IDS)
