@@ -173,6 +173,38 @@ void gae_scan_tm(const Tensor& rew, const Tensor& done, const OptT& val, const O
   check_rc(rc, "gae_scan_tm");
 }
 
+// V-trace on the layout of gae_scan_tm; part holds scan_tm_parts(K * N) x 5 floats (scan.hip).
+void vtrace_scan_tm(const Tensor& rew, const Tensor& done, const Tensor& val, const OptT& tval,
+                    const Tensor& logp_mu, const Tensor& logp_pi, const Tensor& adv, const Tensor& ret,
+                    const Tensor& part, const OptT& stats_out, const OptT& is_out, double gamma, double lam,
+                    double rho_bar, double c_bar, double pg_rho_bar) {
+  check(rew, "rew", at::kFloat);
+  TORCH_CHECK(rew.dim() == 2 || rew.dim() == 3, "rew must be [T, N] or [K, T, N]");
+  const int64_t K = rew.dim() == 3 ? rew.size(0) : 1;
+  const int64_t T = rew.size(rew.dim() - 2), N = rew.size(rew.dim() - 1);
+  TORCH_CHECK(K >= 1 && T >= 1 && N >= 1 && K * N <= (int64_t)INT32_MAX, "vtrace_scan_tm: empty or oversized batch [",
+              K, ", ", T, ", ", N, "]");
+  check(done, "done", at::kFloat, K * T * N);
+  check(val, "val", at::kFloat, K * (T + 1) * N);
+  const float* tv = opt_ptr<const float>(tval, "tval", at::kFloat, K * T * N);
+  check(logp_mu, "logp_mu", at::kFloat);
+  check(logp_pi, "logp_pi", at::kFloat);
+  TORCH_CHECK(logp_mu.sizes() == rew.sizes() && logp_pi.sizes() == rew.sizes(),
+              "logp_mu / logp_pi must have the shape of rew");
+  check(adv, "adv", at::kFloat, K * T * N);
+  check(ret, "ret", at::kFloat, K * T * N);
+  check(part, "stats_part", at::kFloat, scan_tm_parts(K * N) * 5);
+  float* so = opt_ptr<float>(stats_out, "stats_out", at::kFloat, 3);
+  float* io = opt_ptr<float>(is_out, "is_out", at::kFloat, 2);
+  TORCH_CHECK(rho_bar > 0 && c_bar > 0 && pg_rho_bar > 0, "vtrace_scan_tm: the clip thresholds must be positive");
+  const int rc = rrl_vtrace_scan_tm(rew.data_ptr<float>(), done.data_ptr<float>(), val.data_ptr<float>(), tv,
+                                    logp_mu.data_ptr<float>(), logp_pi.data_ptr<float>(), adv.data_ptr<float>(),
+                                    ret.data_ptr<float>(), part.data_ptr<float>(), so, io, (int)K, (int)T, (int)N,
+                                    (float)gamma, (float)lam, (float)rho_bar, (float)c_bar, (float)pg_rho_bar,
+                                    cur_stream());
+  check_rc(rc, "vtrace_scan_tm");
+}
+
 int64_t scan_flat_blocks(int64_t L) { return rrl_scan_flat_blocks((int)L); }
 
 void scan_flat(const Tensor& rew, const Tensor& done, const OptT& val, const OptT& boot, const Tensor& adv,
@@ -396,6 +428,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("tval"), pybind11::arg("adv"), pybind11::arg("ret"), pybind11::arg("stats_part"),
         pybind11::arg("stats_out"), pybind11::arg("gamma"), pybind11::arg("lam"),
         pybind11::arg("counters") = std::vector<std::tuple<Tensor, int64_t>>{});
+  m.def("vtrace_scan_tm", &vtrace_scan_tm, pybind11::arg("rew"), pybind11::arg("done"), pybind11::arg("val"),
+        pybind11::arg("tval"), pybind11::arg("logp_mu"), pybind11::arg("logp_pi"), pybind11::arg("adv"),
+        pybind11::arg("ret"), pybind11::arg("stats_part"), pybind11::arg("stats_out"), pybind11::arg("is_out"),
+        pybind11::arg("gamma"), pybind11::arg("lam"), pybind11::arg("rho_bar"), pybind11::arg("c_bar"),
+        pybind11::arg("pg_rho_bar"));
   m.def("scan_flat_blocks", &scan_flat_blocks);
   m.def("scan_flat", &scan_flat);
   m.def("stats_reduce", &stats_reduce);

@@ -62,6 +62,13 @@ int rrl_scan_tm_parts(int N);
 int rrl_gae_scan_tm(const float* rew, const float* done, const float* val, const float* tval, float* adv,
                     float* ret, float* stats_part, float* stats_out, int K, int T, int N, float gamma, float lam,
                     long long* const* cnt, const long long* inc, int ncnt, void* stream);
+// V-trace on the same layout.  part: rrl_scan_tm_parts(K * N) x 5 floats ([n][3] advantage statistics, then
+// [n][2] importance-weight sums); stats_out[3] / is_out[2] (sum min(rho_bar, ratio), sum |logp_pi - logp_mu|)
+// may be null.  -1: null val / logp_*, a threshold <= 0 or an empty batch
+int rrl_vtrace_scan_tm(const float* rew, const float* done, const float* val, const float* tval,
+                       const float* logp_mu, const float* logp_pi, float* adv, float* ret, float* part,
+                       float* stats_out, float* is_out, int K, int T, int N, float gamma, float lam, float rho_bar,
+                       float c_bar, float pg_rho_bar, void* stream);
 int rrl_scan_flat_blocks(int L);
 // work: rrl_scan_flat_blocks(L) x 9 floats
 int rrl_scan_flat(const float* rew, const float* done, const float* val, const float* boot, float* adv, float* ret,

@@ -15,6 +15,8 @@
 //     over its own link), with the K x N bootstrap values after all of them;
 //   * flat [L] buffers of concatenated variable-length paths (the agent/trajectory API):
 //     a 3-phase parallel affine scan (thread chunk -> block scan -> block carries).
+// The time-major layout also has a V-trace form (vtrace_scan_tm_kernel) for rollouts made with
+// weights older than the learner's: the actor-learner engine's correction="vtrace".
 #include "api.h"
 #include "common.h"
 
@@ -121,6 +123,111 @@ __global__ __launch_bounds__(256) void stats_reduce_kernel(const float* part, in
     float v = 0.f;
     for (int k = 0; k < (int)(blockDim.x >> 6); ++k) v += red[threadIdx.x][k];
     out[threadIdx.x] = v;
+  }
+}
+
+// V-trace (Espeholt et al. 2018, IMPALA) on the same [K][T][N] layout, launch shape and done
+// codes as gae_scan_tm_kernel: the off-policy correction of the lag-1 actor-learner path.  Per
+// column, for t = T-1 .. 0, with acc = v_{t+1} - V_{t+1} (0 past a path end):
+//   ratio  = exp(logp_pi_t - logp_mu_t)
+//   rho    = min(rho_bar, ratio);  c = lam * min(c_bar, ratio);  rho_pg = min(pg_rho_bar, ratio)
+//   v_next = nd * V_{t+1} + vb                        (nd, vb as in the GAE kernel)
+//   adv_t  = rho_pg * (r_t + gamma * (v_next + nd * acc) - V_t)
+//   acc    = rho * (r_t + gamma * v_next - V_t) + gamma * c * nd * acc
+//   ret_t  = V_t + acc                                (the V-trace target v_t)
+struct VtraceTM {
+  const float* rew;      // [K][T][N]
+  const float* done;     // [K][T][N]  (0 running / 1 terminal / 2 truncated)
+  const float* val;      // [K*T*N + K*N]: V of every step, then V(s_T) of each column
+  const float* tval;     // [K][T][N] V(pre-reset obs), read where done == 2, or null
+  const float* logp_mu;  // [K][T][N] behaviour policy (the rollout's)
+  const float* logp_pi;  // [K][T][N] current policy, same actions
+  float* adv;            // [K][T][N]
+  float* ret;            // [K][T][N]
+  float* part;           // [nblocks][3] adv sum / sumsq / count, then [nblocks][2] sum rho / sum |log ratio|
+  int T, N, K;
+  float gamma, lam, rho_bar, c_bar, pg_rho_bar;
+};
+
+__global__ __launch_bounds__(256) void vtrace_scan_tm_kernel(VtraceTM p) {
+  const int col = blockIdx.x * blockDim.x + threadIdx.x;  // column = block k, env n
+  float sum[5] = {0.f, 0.f, 0.f, 0.f, 0.f};               // adv, adv^2, count, rho, |log ratio|
+  if (col < p.K * p.N) {
+    const size_t N = (size_t)p.N;
+    const int k = col / p.N;
+    const size_t base = (size_t)k * p.T * N + (col - k * p.N);
+    float v_prev = p.val[(size_t)p.K * p.T * N + col];
+    float acc = 0.f;
+    for (int t = p.T - 1; t >= 0; --t) {
+      const size_t idx = base + (size_t)t * N;
+      const float r = p.rew[idx], d = p.done[idx], v = p.val[idx];
+      const float lr = p.logp_pi[idx] - p.logp_mu[idx];
+      const float nd = d == 0.f ? 1.f : 0.f;
+      const float vb = (d > 1.5f && p.tval != nullptr) ? p.tval[idx] : 0.f;  // truncation bootstrap
+      const float ratio = expf(lr);
+      const float rho = fminf(p.rho_bar, ratio);
+      const float c = p.lam * fminf(p.c_bar, ratio);
+      const float v_next = nd * v_prev + vb;
+      const float a = fminf(p.pg_rho_bar, ratio) * (r + p.gamma * (v_next + nd * acc) - v);
+      acc = rho * (r + p.gamma * v_next - v) + p.gamma * c * nd * acc;
+      p.adv[idx] = a;
+      p.ret[idx] = v + acc;
+      sum[0] += a;
+      sum[1] += a * a;
+      sum[3] += rho;
+      sum[4] += fabsf(lr);
+      v_prev = v;
+    }
+    sum[2] = (float)p.T;
+  }
+  __shared__ float red[5][4];
+  const int w = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const float v = wave_sum(sum[q]);
+    if ((threadIdx.x & 63) == 0) red[q][w] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    const int q = threadIdx.x;
+    float v = 0.f;
+    for (int j = 0; j < (int)(blockDim.x >> 6); ++j) v += red[q][j];
+    float* dst = q < 3 ? p.part + (size_t)blockIdx.x * 3 + q
+                       : p.part + (size_t)gridDim.x * 3 + (size_t)blockIdx.x * 2 + (q - 3);
+    *dst = v;
+  }
+}
+
+// Deterministic final reduction of the V-trace partials (single block, the order of
+// stats_reduce_kernel): stats_out[3] and is_out[2], either may be null.
+__global__ __launch_bounds__(256) void vtrace_reduce_kernel(const float* part, int nparts, float* stats_out,
+                                                            float* is_out) {
+  __shared__ float red[5][4];
+  const float* ispart = part + (size_t)nparts * 3;
+  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int k = threadIdx.x; k < nparts; k += blockDim.x) {
+    acc[0] += part[k * 3 + 0];
+    acc[1] += part[k * 3 + 1];
+    acc[2] += part[k * 3 + 2];
+    acc[3] += ispart[k * 2 + 0];
+    acc[4] += ispart[k * 2 + 1];
+  }
+  const int w = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const float v = wave_sum(acc[q]);
+    if ((threadIdx.x & 63) == 0) red[q][w] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    const int q = threadIdx.x;
+    float v = 0.f;
+    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) v += red[q][k];
+    if (q < 3) {
+      if (stats_out != nullptr) stats_out[q] = v;
+    } else if (is_out != nullptr) {
+      is_out[q - 3] = v;
+    }
   }
 }
 
@@ -318,6 +425,23 @@ extern "C" int rrl_gae_scan_tm(const float* rew, const float* done, const float*
   }
   hipLaunchKernelGGL(gae_scan_tm_kernel, dim3(nb), dim3(256), 0, s, p);
   if (stats_out) hipLaunchKernelGGL(stats_reduce_kernel, dim3(1), dim3(256), 0, s, stats_part, nb, stats_out);
+  return (int)hipGetLastError();
+}
+
+// part: rrl_scan_tm_parts(K * N) x 5 floats
+extern "C" int rrl_vtrace_scan_tm(const float* rew, const float* done, const float* val, const float* tval,
+                                  const float* logp_mu, const float* logp_pi, float* adv, float* ret, float* part,
+                                  float* stats_out, float* is_out, int K, int T, int N, float gamma, float lam,
+                                  float rho_bar, float c_bar, float pg_rho_bar, void* stream) {
+  if (val == nullptr || logp_mu == nullptr || logp_pi == nullptr) return -1;
+  if (!(rho_bar > 0.f) || !(c_bar > 0.f) || !(pg_rho_bar > 0.f)) return -1;
+  if (K < 1 || T < 1 || N < 1 || (long long)K * N > 0x7fffffffLL) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = rrl_scan_tm_parts(K * N);
+  VtraceTM p{rew, done, val, tval, logp_mu, logp_pi, adv, ret, part, T, N, K, gamma, lam, rho_bar, c_bar, pg_rho_bar};
+  hipLaunchKernelGGL(vtrace_scan_tm_kernel, dim3(nb), dim3(256), 0, s, p);
+  if (stats_out || is_out)
+    hipLaunchKernelGGL(vtrace_reduce_kernel, dim3(1), dim3(256), 0, s, (const float*)part, nb, stats_out, is_out);
   return (int)hipGetLastError();
 }
 

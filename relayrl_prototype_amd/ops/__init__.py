@@ -64,6 +64,7 @@ from .mlp import (  # noqa: E402
     adam_step,
     reduce_slabs,
     gae_scan_tm,
+    vtrace_scan_tm,
     scan_flat,
 )
 from .integrity import payload_checksum, payload_verify  # noqa: E402
@@ -85,5 +86,6 @@ __all__ = [
     "adam_step",
     "reduce_slabs",
     "gae_scan_tm",
+    "vtrace_scan_tm",
     "scan_flat",
 ]

@@ -254,6 +254,43 @@ def gae_scan_tm(rew, done, val, gamma, lam, adv=None, ret=None, stats_part=None,
     return adv, ret, stats_out
 
 
+def vtrace_scan_tm(rew, done, val, logp_mu, logp_pi, gamma, lam, rho_bar=1.0, c_bar=1.0, pg_rho_bar=1.0, adv=None,
+                   ret=None, stats_part=None, stats_out=None, is_out=None, tval=None):
+    """Time-major V-trace scan (Espeholt et al. 2018) -> (adv, ret, stats[3], is_stats[2]) on the
+    layout and done codes of ``gae_scan_tm``; a value function is required.
+
+    ``logp_mu`` / ``logp_pi``: log-probs of the taken actions under the behaviour policy (the
+    rollout's) and the current one, shaped like ``rew``.  ``ret`` is the V-trace value target,
+    ``adv`` the clipped-ratio-weighted policy-gradient advantage, ``stats`` its sum / sum of
+    squares / count (the layout of the GAE statistics), ``is_stats`` = (sum min(rho_bar, ratio),
+    sum |logp_pi - logp_mu|).  ``stats_part`` (GPU): scan_tm_parts(K * N) x 5 floats of workspace."""
+    if val is None:
+        raise ValueError("vtrace_scan_tm needs a value function (val)")
+    if not (rho_bar > 0 and c_bar > 0 and pg_rho_bar > 0):
+        raise ValueError("vtrace_scan_tm: the clip thresholds must be positive")
+    h = _hip_for(rew)
+    if h is None:
+        a, r, s, i = ref.vtrace_scan_tm_ref(rew, done, val, logp_mu, logp_pi, gamma, lam, rho_bar, c_bar, pg_rho_bar,
+                                            tval)
+        for dst, src in ((adv, a), (ret, r), (stats_out, s), (is_out, i)):
+            if dst is not None:
+                dst.copy_(src.reshape(dst.shape))
+        return a, r, s, i
+    K = rew.shape[0] if rew.dim() == 3 else 1
+    N = rew.shape[-1]
+    dev = rew.device
+    adv = torch.empty(rew.shape, device=dev) if adv is None else adv
+    ret = torch.empty(rew.shape, device=dev) if ret is None else ret
+    if stats_part is None:
+        stats_part = torch.empty(int(h.scan_tm_parts(K * N)) * 5, device=dev)
+    stats_out = torch.empty(3, device=dev) if stats_out is None else stats_out
+    is_out = torch.empty(2, device=dev) if is_out is None else is_out
+    h.vtrace_scan_tm(rew.contiguous(), done.contiguous(), val.contiguous(), _f32(tval), logp_mu.contiguous(),
+                     logp_pi.contiguous(), adv, ret, stats_part, stats_out, is_out, float(gamma), float(lam),
+                     float(rho_bar), float(c_bar), float(pg_rho_bar))
+    return adv, ret, stats_out, is_out
+
+
 def scan_flat(rew, done, val, boot, gamma, lam):
     """Flat concatenated-paths scan (finish_path semantics) -> (adv, ret, stats[3])."""
     h = _hip_for(rew)

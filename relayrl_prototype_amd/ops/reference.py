@@ -224,6 +224,48 @@ def gae_scan_tm_ref(rew, done, val, gamma, lam, tval=None):
 
 
 @torch.no_grad()
+def vtrace_scan_tm_ref(rew, done, val, logp_mu, logp_pi, gamma, lam, rho_bar, c_bar, pg_rho_bar, tval=None):
+    """V-trace (Espeholt et al. 2018) on the layout and done codes of ``gae_scan_tm_ref`` ->
+    (adv, ret, stats[3], is_stats[2]), computed in the dtype of the inputs.
+
+    ``ret`` is the V-trace target v_t, ``adv`` the policy-gradient advantage
+    min(pg_rho_bar, ratio) * (r_t + gamma * v_{t+1} - V_t); ``is_stats`` = (sum min(rho_bar, ratio),
+    sum |logp_pi - logp_mu|).  On-policy with thresholds >= 1, ``ret`` = V + GAE(lam)."""
+    if rew.dim() == 3:
+        K, T, N = rew.shape
+        tm = lambda x: x.reshape(K, T, N).permute(1, 0, 2).reshape(T, K * N)  # noqa: E731
+        vf = val.reshape(-1)
+        v = torch.cat([tm(vf[:K * T * N]), vf[K * T * N:K * T * N + K * N].reshape(1, K * N)])
+        a, r, s, i = vtrace_scan_tm_ref(tm(rew), tm(done), v, tm(logp_mu), tm(logp_pi), gamma, lam, rho_bar, c_bar,
+                                        pg_rho_bar, None if tval is None else tm(tval))
+        back = lambda x: x.reshape(T, K, N).permute(1, 0, 2).contiguous()  # noqa: E731
+        return back(a), back(r), s, i
+    T, N = rew.shape
+    val = val.reshape(T + 1, N)
+    adv = torch.zeros_like(rew)
+    ret = torch.zeros_like(rew)
+    zero = torch.zeros(N, dtype=rew.dtype, device=rew.device)
+    acc = zero.clone()
+    v_prev = val[T].clone()
+    log_ratio = logp_pi - logp_mu
+    ratio = torch.exp(log_ratio)
+    rho = torch.clamp(ratio, max=rho_bar)
+    c = lam * torch.clamp(ratio, max=c_bar)
+    rho_pg = torch.clamp(ratio, max=pg_rho_bar)
+    for t in range(T - 1, -1, -1):
+        nd = (done[t] == 0).to(rew.dtype)
+        vb = torch.where(done[t] > 1.5, tval[t], zero) if tval is not None else zero
+        v_next = nd * v_prev + vb
+        adv[t] = rho_pg[t] * (rew[t] + gamma * (v_next + nd * acc) - val[t])
+        acc = rho[t] * (rew[t] + gamma * v_next - val[t]) + gamma * c[t] * nd * acc
+        ret[t] = val[t] + acc
+        v_prev = val[t]
+    stats = torch.stack([adv.sum(), (adv * adv).sum(), torch.tensor(float(T * N), dtype=rew.dtype, device=rew.device)])
+    is_stats = torch.stack([rho.sum(), log_ratio.abs().sum()])
+    return adv, ret, stats, is_stats
+
+
+@torch.no_grad()
 def scan_flat_ref(rew, done, val, boot, gamma, lam):
     """Per-path finish_path semantics over a flat buffer (replay_buffer.py:48-79)."""
     r = rew.detach().cpu().double().numpy()

@@ -23,7 +23,18 @@ table.  Every rollout carries a header: sequence number (heartbeat), episode sta
 and the version + checksum of the weights it was rolled out with.
 
 ``max_lag = 1`` overlaps an actor's rollout of epoch k+1 with the learners' update on
-epoch k (IMPALA-style lag-1 pipelining).  Weights arrive in a BACK buffer; the actor
+epoch k (IMPALA's pipelining, at a fixed lag of one update).  By default only the pipelining is
+IMPALA's: the learner treats the lagged rollout as on-policy (GAE scan, plain policy-gradient
+head).  ``correction="vtrace"`` adds IMPALA's off-policy correction (Espeholt et al. 2018): the
+learner evaluates log pi(a|s) of the received actions under its current weights (one forward,
+phase PolicyEval), and the V-trace scan (ops.vtrace_scan_tm, docs/KERNELS.md) turns it and the
+header-verified behaviour ``logp`` into clipped importance weights for the value targets and the
+policy-gradient advantages (``vtrace_rho_bar`` / ``vtrace_c_bar`` / ``vtrace_pg_rho_bar``).  Not
+IMPALA's: the lag is bounded and uniform (no asynchronous actor queue), there is no recurrent
+state, and the value net is trained by the ``train_vf_iters`` regression loop on the V-trace
+targets instead of one joint loss.  It needs a value function, is refused with ``algo="ppo"`` (its
+own ratio) and with agent rows, and ``metrics()`` then reports ``MeanRho`` and
+``MeanAbsLogRatio`` (0 on-policy) of the newest batch.  Weights arrive in a BACK buffer; the actor
 copies back -> front on its compute stream only after the receive completed and only
 after the previous rollout kernel was queued, and posts the next receive after that
 copy, so a rollout never reads a half-written policy.  Learners send from a snapshot of
@@ -63,7 +74,7 @@ from ..parallel.comm import Comm, collective_timeout
 from ..ops import integrity as integ
 from ..utils.faults import maybe_stall_at, rollout_fault
 from ..utils.tracing import PhaseTimer
-from .rollout_learn import RolloutLearner
+from .rollout_learn import CORRECTIONS, RolloutLearner
 
 # header (float64): seq, n_episodes, sum_ret, sumsq_ret, max_ret, min_ret, sum_len, version, checksum, wsum,
 # then the payload checksum (s1, s2) as raw 64-bit integers
@@ -105,6 +116,10 @@ class ActorLearnerConfig:
     stall_factor: float = 20.0
     phase_timing: bool = False     # HIP-event phases: Rollout, Gather, Learn, AllReduce, WeightSend, ...
     integrity: str = "off"         # rollout checksum + seq + version check on the device: off | lagged | strict
+    correction: str = "none"       # off-policy correction of the learner's update: none | vtrace
+    vtrace_rho_bar: float = 1.0    # V-trace clip thresholds: value-target weights (rho), trace weights (c),
+    vtrace_c_bar: float = 1.0      # policy-gradient weights
+    vtrace_pg_rho_bar: float = 1.0
 
     def to_dict(self):
         return asdict(self)
@@ -253,6 +268,17 @@ class ActorLearner:
             raise ValueError("max_lag must be 0 or 1")
         if cfg.integrity not in INTEGRITY_MODES:
             raise ValueError(f"integrity={cfg.integrity!r}: expected one of {INTEGRITY_MODES}")
+        if cfg.correction not in CORRECTIONS:
+            raise ValueError(f"correction={cfg.correction!r}: expected one of {CORRECTIONS}")
+        if cfg.correction == "vtrace":
+            # every rank refuses (an actor-only rank builds no RolloutLearner, which checks the same)
+            if cfg.algo.lower() == "ppo":
+                raise ValueError("correction='vtrace' does not combine with algo='ppo': the PPO surrogate already "
+                                 "carries its own importance ratio against the rollout's log-probs")
+            if not (cfg.with_baseline or cfg.algo.lower() == "a2c"):
+                raise ValueError("correction='vtrace' needs a value function (with_baseline=True)")
+            if not (cfg.vtrace_rho_bar > 0 and cfg.vtrace_c_bar > 0 and cfg.vtrace_pg_rho_bar > 0):
+                raise ValueError("vtrace_rho_bar, vtrace_c_bar and vtrace_pg_rho_bar must be positive")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
@@ -307,7 +333,9 @@ class ActorLearner:
             self.b_done = torch.zeros(K, T, N, device=dev)
             self.b_tobs = torch.zeros(K, T, N, D, device=dev) if need_tobs else None
             self.b_hdr = torch.zeros(K, HDR, dtype=torch.float64, device=dev)
-            self.rl = RolloutLearner(self.learner, T, N, cfg.gamma, cfg.lam, self.lcomm, self.timer, blocks=K)
+            self.rl = RolloutLearner(self.learner, T, N, cfg.gamma, cfg.lam, self.lcomm, self.timer, blocks=K,
+                                     correction=cfg.correction, rho_bar=cfg.vtrace_rho_bar, c_bar=cfg.vtrace_c_bar,
+                                     pg_rho_bar=cfg.vtrace_pg_rho_bar)
             self.wsend = torch.zeros_like(self.learner.pi.params)  # snapshot the P2P sends read
             self.front = self.learner.pi.params
             self.integrity_checked = 0
@@ -641,6 +669,17 @@ class ActorLearner:
             out["ActorSeqs"] = h[:, 0].tolist()
             out["ActorVersions"] = [int(x) for x in h[:, 7].tolist()]
             out.update(self.learner.summarize())
+            if self.cfg.correction == "vtrace":
+                # of the newest batch, over the whole learner group: mean clipped value-target weight and
+                # mean |log pi - log mu| (0 on-policy); the only host read of these sums
+                rows = float(self.topo.K * self.cfg.rollout_len * self.cfg.num_envs)
+                vec = torch.cat([self.rl.is_stats.double(), torch.tensor([rows], dtype=torch.float64,
+                                                                          device=self.rl.is_stats.device)])
+                if self.lcomm.backend != "nccl":
+                    vec = vec.cpu()
+                self.lcomm.all_reduce_sum_(vec)
+                s_rho, s_abs, n = vec.tolist()
+                out["MeanRho"], out["MeanAbsLogRatio"] = s_rho / n, s_abs / n
         if self.is_learner and self.cfg.integrity != "off":
             out["IntegrityChecked"] = self.integrity_checked        # slots verified (and read back) so far
             out["IntegrityMismatches"] = self.integrity_mismatches

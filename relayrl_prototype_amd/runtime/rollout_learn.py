@@ -7,19 +7,43 @@ from typing import Optional
 import torch
 
 from ..algorithms.learner import PGLearner
-from ..ops import FwdMode, gae_scan_tm, mlp_forward, scan_flat
+from ..ops import FwdMode, gae_scan_tm, mlp_forward, scan_flat, vtrace_scan_tm
 from ..parallel.comm import Comm
 from ..utils.tracing import PhaseTimer
+
+CORRECTIONS = ("none", "vtrace")
 
 
 class RolloutLearner:
     """Owns the HBM-resident scan buffers and drives a PGLearner on time-major rollouts."""
 
     def __init__(self, learner: PGLearner, T: int, N: int, gamma: float, lam: float, comm: Optional[Comm] = None,
-                 timer: Optional[PhaseTimer] = None, blocks: int = 1):
+                 timer: Optional[PhaseTimer] = None, blocks: int = 1, correction: str = "none",
+                 rho_bar: float = 1.0, c_bar: float = 1.0, pg_rho_bar: float = 1.0,
+                 agent_rows_enabled: bool = False):
         """``blocks`` = K actor rollouts per learner shard (runtime/actor_learner.py): the
         shard's batch is K time-major [T, N] blocks back to back, then the K x N final
-        observations (obs rows [K*T*N + K*N]); K = 1 is the plain [T+1, N] layout."""
+        observations (obs rows [K*T*N + K*N]); K = 1 is the plain [T+1, N] layout.
+
+        ``correction="vtrace"``: the rollout's ``logp`` is the behaviour policy's; the current
+        policy's log-probs of the same actions are evaluated once per epoch (phase PolicyEval)
+        and the V-trace scan (ops.vtrace_scan_tm, clip thresholds ``rho_bar`` / ``c_bar`` /
+        ``pg_rho_bar``) replaces the GAE scan.  Its advantages, value targets and advantage
+        statistics feed ``PGLearner.optimize`` unchanged."""
+        if correction not in CORRECTIONS:
+            raise ValueError(f"correction={correction!r}: expected one of {CORRECTIONS}")
+        self.correction = correction
+        self.rho_bar, self.c_bar, self.pg_rho_bar = float(rho_bar), float(c_bar), float(pg_rho_bar)
+        if correction == "vtrace":
+            if learner.algo == "ppo":
+                raise ValueError("correction='vtrace' does not combine with algo='ppo': the PPO surrogate already "
+                                 "carries its own importance ratio against the rollout's log-probs")
+            if learner.vf is None:
+                raise ValueError("correction='vtrace' needs a value function (with_baseline=True): the V-trace "
+                                 "targets correct V, there is nothing to correct without one")
+            if not (self.rho_bar > 0 and self.c_bar > 0 and self.pg_rho_bar > 0):
+                raise ValueError(f"the V-trace clip thresholds must be positive, got rho_bar={rho_bar}, "
+                                 f"c_bar={c_bar}, pg_rho_bar={pg_rho_bar}")
         self.learner = learner
         self.timer = timer or PhaseTimer(learner.device, enabled=False)
         self.T, self.N, self.K = T, N, int(blocks)
@@ -43,15 +67,40 @@ class RolloutLearner:
         # agent rows on a capturable learner: ONE padded batch [B + agent_cap] whose valid row
         # count (nvalid) and loss scale (1 / global rows, from the all-reduced statistics) live
         # on the device, so epochs with uploads replay a captured graph too
-        self.agent_rows_enabled = False
+        self._agent_rows_enabled = False
+        self.agent_rows_enabled = agent_rows_enabled  # a ValueError under correction="vtrace"
         self.agent_cap = 0
         self._pad = None
         self._nvalid = None
         self._inv_dev = None
+        vtrace = correction == "vtrace"
         if dev.type == "cuda":
             from ..ops import hip
 
-            self.stats_part = torch.zeros(hip().scan_tm_parts(K * N), 3, device=dev)
+            nparts = hip().scan_tm_parts(K * N)
+            # V-trace: [nparts][3], then [nparts][2] partial sums of the importance-weight statistics
+            self.stats_part = torch.zeros(nparts * 5, device=dev) if vtrace else torch.zeros(nparts, 3, device=dev)
+        # V-trace: log pi(a|s) under the current weights, and (sum min(rho_bar, ratio),
+        # sum |logp_pi - logp_mu|) of the newest batch (read in ActorLearner.metrics only)
+        self.logp_pi = self.is_stats = self._pi_out = None
+        if vtrace:
+            B = K * T * N
+            self.logp_pi = torch.zeros(shape, device=dev)
+            self.is_stats = torch.zeros(2, device=dev)
+            self._pi_out = {"logp": self.logp_pi.view(-1), "entropy": torch.zeros(B, device=dev)}
+            if not learner.discrete:
+                self._pi_out["mean"] = torch.zeros(B, learner.act_dim, device=dev)
+
+    @property
+    def agent_rows_enabled(self) -> bool:
+        return self._agent_rows_enabled
+
+    @agent_rows_enabled.setter
+    def agent_rows_enabled(self, on: bool):
+        if on and self.correction == "vtrace":
+            raise ValueError("correction='vtrace' does not support agent rows: folding uploads needs a V-trace "
+                             "form of the flat segmented scan")
+        self._agent_rows_enabled = bool(on)
 
     def learn(self, obs, act, rew, done, logp, mask=None, tobs=None):
         """obs [T+1, N, D] (or flat [K*T*N + K*N, D]); act [T, N] int32 or [T, N, A];
@@ -77,14 +126,27 @@ class RolloutLearner:
                     # only the 16-row tiles holding a truncation are evaluated (gate = done codes)
                     mlp_forward(FwdMode.VALUE, lr.vf.params, tobs.reshape(B, D), 1, lr.hidden,
                                 out={"v": self.tval.view(-1)}, gate=done.reshape(-1))
+        vtrace = self.correction == "vtrace"
+        if vtrace:
+            with tm.phase("PolicyEval"):
+                mlp_forward(FwdMode.CAT_EVAL if lr.discrete else FwdMode.GAUSS_EVAL, lr.pi.params, obs_b, lr.act_dim,
+                            lr.hidden, mask=None if mask is None else mask.reshape(B, -1),
+                            act_in=act.reshape(B) if lr.discrete else None,
+                            actc_in=None if lr.discrete else act.reshape(B, -1), out=self._pi_out)
         with tm.phase("Scan"):
-            adv, ret, stats = gae_scan_tm(rew, done, self.val, self.gamma, self.lam, adv=self.adv, ret=self.ret,
-                                          stats_part=self.stats_part, stats_out=self.adv_stats,
-                                          tval=self.tval if tobs is not None else None)
-            if not rew.is_cuda:
-                self.adv.view(-1).copy_(adv.reshape(-1))
-                self.ret.view(-1).copy_(ret.reshape(-1))
-                self.adv_stats.copy_(stats)
+            if vtrace:
+                vtrace_scan_tm(rew, done, self.val, logp.reshape(rew.shape), self.logp_pi.view(rew.shape), self.gamma,
+                               self.lam, self.rho_bar, self.c_bar, self.pg_rho_bar, adv=self.adv, ret=self.ret,
+                               stats_part=self.stats_part, stats_out=self.adv_stats, is_out=self.is_stats,
+                               tval=self.tval if tobs is not None else None)
+            else:
+                adv, ret, stats = gae_scan_tm(rew, done, self.val, self.gamma, self.lam, adv=self.adv, ret=self.ret,
+                                              stats_part=self.stats_part, stats_out=self.adv_stats,
+                                              tval=self.tval if tobs is not None else None)
+                if not rew.is_cuda:
+                    self.adv.view(-1).copy_(adv.reshape(-1))
+                    self.ret.view(-1).copy_(ret.reshape(-1))
+                    self.adv_stats.copy_(stats)
             extra, self.pending_rows = self.pending_rows, None
             self.last_agent_rows = 0
             folded = None
