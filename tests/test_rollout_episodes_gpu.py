@@ -21,28 +21,11 @@ from relayrl_prototype_amd.ops import MLPSpec, hip
 from relayrl_prototype_amd.ops import reference as ref
 
 import rollout_oracle as ro
+from guarded import INT_SENTINEL, Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-INT_SENTINEL = -7
 DEV = "cuda:0"
-
-
-class Guarded:
-    """A contiguous tensor with GUARD sentinel elements on both sides (NaN, or -7 for ints)."""
-
-    def __init__(self, shape, dtype=torch.float32, fill=None):
-        n = math.prod(shape)
-        sentinel = float("nan") if dtype.is_floating_point else INT_SENTINEL
-        self.big = torch.full((n + 2 * GUARD,), sentinel, dtype=dtype, device=DEV)
-        self.t = self.big[GUARD:GUARD + n].view(shape)
-        if fill is not None:  # else the payload starts as sentinels too: an unwritten cell shows
-            self.t.copy_(torch.as_tensor(np.broadcast_to(np.asarray(fill), shape).copy()).to(dtype))
-
-    def guards_intact(self):
-        g = torch.cat([self.big[:GUARD], self.big[-GUARD:]])
-        return bool(torch.isnan(g).all()) if self.big.dtype.is_floating_point else bool((g == INT_SENTINEL).all())
 
 
 @contextmanager
