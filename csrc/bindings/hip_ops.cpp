@@ -394,6 +394,87 @@ void rollout_cont(int64_t env, const Tensor& params, const Tensor& env_consts, i
            "rollout_cont");
 }
 
+// A tensor of evaluate(): checked like check(), with exactly n elements.
+void check_exact(const Tensor& t, const char* name, at::ScalarType dt, int64_t n) {
+  check(t, name, dt);
+  TORCH_CHECK(t.numel() == n, name, " has ", t.numel(), " elements, expected ", n);
+}
+
+struct EvalShape {
+  int64_t E, N, Tc;
+};
+
+// The outputs evaluate() and evaluate_cont() have in common: ep_* are [E, N]; the trace tensors come
+// together or not at all, [Tc, N, ...] with act_dt / A_cols for tr_act (A_cols 0: [Tc, N]).
+EvalShape check_eval_bufs(int64_t D, const Tensor& ep_ret, const Tensor& ep_len, const Tensor& ep_code,
+                          const OptT& tr_obs, const OptT& tr_act, const OptT& tr_rew, const OptT& tr_done,
+                          at::ScalarType act_dt, int64_t A_cols, int64_t max_steps) {
+  check(ep_ret, "ep_ret", at::kFloat);
+  TORCH_CHECK(ep_ret.dim() == 2 && ep_ret.size(0) >= 1 && ep_ret.size(1) >= 1, "ep_ret must be [E, N], E, N >= 1");
+  EvalShape sh{ep_ret.size(0), ep_ret.size(1), 0};
+  TORCH_CHECK(sh.N < (int64_t(1) << 31) - 16, "too many envs");
+  check_exact(ep_len, "ep_len", at::kInt, sh.E * sh.N);
+  check_exact(ep_code, "ep_code", at::kInt, sh.E * sh.N);
+  TORCH_CHECK(max_steps >= 1, "max_steps must be >= 1");
+  TORCH_CHECK(sh.E * max_steps < (int64_t(1) << 31), "E * max_steps must stay below 2^31");
+  auto has = [](const OptT& t) { return t.has_value() && t->defined(); };
+  const int given = has(tr_obs) + has(tr_act) + has(tr_rew) + has(tr_done);
+  TORCH_CHECK(given == 0 || given == 4, "the trace tensors tr_obs, tr_act, tr_rew, tr_done are given together");
+  if (given == 4) {
+    check(*tr_rew, "tr_rew", at::kFloat);
+    TORCH_CHECK(tr_rew->dim() == 2 && tr_rew->size(0) >= 1 && tr_rew->size(1) == sh.N, "tr_rew must be [Tc, N]");
+    sh.Tc = tr_rew->size(0);
+    check_exact(*tr_done, "tr_done", at::kFloat, sh.Tc * sh.N);
+    check_exact(*tr_obs, "tr_obs", at::kFloat, sh.Tc * sh.N * D);
+    check_exact(*tr_act, "tr_act", act_dt, sh.Tc * sh.N * (A_cols > 0 ? A_cols : 1));
+  }
+  return sh;
+}
+
+// Fused policy evaluation (evaluate.hip): every env runs E complete episodes under fixed weights.
+void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
+              const Tensor& ep_code, const OptT& tr_obs, const OptT& tr_act, const OptT& tr_rew, const OptT& tr_done,
+              int64_t seed, int64_t step0, bool greedy, int64_t max_steps) {
+  auto [D, A, NS, ms] = env_dims(env);
+  (void)NS;
+  (void)ms;
+  TORCH_CHECK(env != ENV_HALFCHEETAH, "evaluate takes the discrete device envs; use evaluate_cont for env 4");
+  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
+  check_exact(params, "params", at::kFloat, flat_size(D, H, A, false));
+  const EvalShape sh = check_eval_bufs(D, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done, at::kInt, 0,
+                                       max_steps);
+  const bool tr = sh.Tc > 0;
+  check_rc(rrl_evaluate((int)env, params.data_ptr<float>(), (int)sh.N, (int)sh.E, (int)sh.Tc, (int)H,
+                        ep_ret.data_ptr<float>(), ep_len.data_ptr<int>(), ep_code.data_ptr<int>(),
+                        tr ? tr_obs->data_ptr<float>() : nullptr, tr ? tr_act->data_ptr<int>() : nullptr,
+                        tr ? tr_rew->data_ptr<float>() : nullptr, tr ? tr_done->data_ptr<float>() : nullptr,
+                        (uint64_t)seed, (uint64_t)step0, greedy ? 1 : 0, (int)max_steps, num_cus(), cur_stream()),
+           "evaluate");
+}
+
+void evaluate_cont(int64_t env, const Tensor& params, const Tensor& env_consts, int64_t H, const Tensor& ep_ret,
+                   const Tensor& ep_len, const Tensor& ep_code, const OptT& tr_obs, const OptT& tr_act,
+                   const OptT& tr_rew, const OptT& tr_done, int64_t seed, int64_t step0, bool greedy,
+                   int64_t max_steps) {
+  auto [D, A, NS, ms] = env_dims(env);
+  (void)NS;
+  (void)ms;
+  TORCH_CHECK(env == ENV_HALFCHEETAH, "evaluate_cont supports the continuous device env 4 (HalfCheetahSynth)");
+  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
+  check_exact(params, "params", at::kFloat, flat_size(D, H, A, true));
+  check_exact(env_consts, "env_consts", at::kFloat, 17 * 17 + 17 * 6);
+  const EvalShape sh = check_eval_bufs(D, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done, at::kFloat, A,
+                                       max_steps);
+  const bool tr = sh.Tc > 0;
+  check_rc(rrl_evaluate_cont((int)env, params.data_ptr<float>(), env_consts.data_ptr<float>(), (int)sh.N, (int)sh.E,
+                             (int)sh.Tc, (int)H, ep_ret.data_ptr<float>(), ep_len.data_ptr<int>(),
+                             ep_code.data_ptr<int>(), tr ? tr_obs->data_ptr<float>() : nullptr,
+                             tr ? tr_act->data_ptr<float>() : nullptr, tr ? tr_rew->data_ptr<float>() : nullptr,
+                             tr ? tr_done->data_ptr<float>() : nullptr, (uint64_t)seed, (uint64_t)step0,
+                             greedy ? 1 : 0, (int)max_steps, num_cus(), cur_stream()),
+           "evaluate_cont");
+}
+
 }  // namespace
 
 void register_cnn_ops(pybind11::module_& m);      // cnn_ops.cpp
@@ -450,6 +531,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rollout_grid", &rollout_grid);
   m.def("rollout", &rollout);
   m.def("rollout_cont", &rollout_cont);
+  m.def("evaluate", &evaluate, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("H"),
+        pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"), pybind11::arg("tr_obs"),
+        pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"), pybind11::arg("seed"),
+        pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"));
+  m.def("evaluate_cont", &evaluate_cont, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("env_consts"),
+        pybind11::arg("H"), pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"),
+        pybind11::arg("tr_obs"), pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"),
+        pybind11::arg("seed"), pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"));
   // the enumerators of api.h by name: the Python tables (ops/mlp.py, DEVICE_ENVS) are tested against these
 #define RRL_ENUM(e) pybind11::arg(#e) = (int)rrl::e
   m.attr("FWD_MODES") = pybind11::dict(RRL_ENUM(MODE_VALUE), RRL_ENUM(MODE_CAT_SAMPLE), RRL_ENUM(MODE_CAT_EVAL),

@@ -106,6 +106,20 @@ int rrl_rollout_cont(int env, const float* params, const float* env_consts, int 
                      float* done_buf, float* tobs_buf, float* ep_stats, uint64_t seed, uint64_t step0,
                      int reset_all, int max_steps, int num_cu, void* stream);
 
+// ---- evaluate.hip
+// Every env runs E complete episodes (greedy: argmax / mu instead of the rollout kernels' draws) into
+// ep_ret / ep_len / ep_code [E][N] (code 1 terminal, 2 time limit).  tr_*: optional trace of the first Tc
+// steps, all four pointers or none (then Tc may be 0).  -2: N, E, Tc or max_steps below 1, or
+// E * max_steps >= 2^31; -3: unsupported H or env
+int rrl_evaluate(int env, const float* params, int N, int E, int Tc, int H, float* ep_ret, int* ep_len,
+                 int* ep_code, float* tr_obs, int* tr_act, float* tr_rew, float* tr_done, uint64_t seed,
+                 uint64_t step0, int greedy, int max_steps, int num_cu, void* stream);
+// continuous-action envs (ENV_HALFCHEETAH); tr_act is [Tc][N][A]
+int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int N, int E, int Tc, int H,
+                      float* ep_ret, int* ep_len, int* ep_code, float* tr_obs, float* tr_act, float* tr_rew,
+                      float* tr_done, uint64_t seed, uint64_t step0, int greedy, int max_steps, int num_cu,
+                      void* stream);
+
 // ---- cnn.hip (bf16 tensors as uint16_t)
 int rrl_conv_fwd(const void* x, int x_u8, const uint16_t* w, const float* b, uint16_t* y, int N, int H, int W,
                  int C, int KH, int KW, int S, int Cout, int relu, float* work, long long work_elems, void* stream);

@@ -216,6 +216,15 @@ class TrainingServer:
             return None
         return self.engine.train(**kw)
 
+    def evaluate(self, episodes: int = 1, num_envs: Optional[int] = None, greedy: bool = True):
+        """Score the engine's current policy: ``num_envs`` device envs x ``episodes`` whole episodes
+        each, greedy unless told otherwise -> EvalResult (runtime/evaluate.py).  For the in-process
+        ``vec`` engine; the others raise NotImplementedError."""
+        if self.engine is None:
+            raise NotImplementedError("evaluate() is not implemented for a server that learns from agent uploads: "
+                                      "it needs the in-process vec engine (engine=\"vec\")")
+        return self.algorithm.evaluate(episodes=episodes, num_envs=num_envs, greedy=greedy)
+
     # ------------------------------------------------------------------ extras
     def wait_idle(self, timeout: float = 60.0) -> bool:
         """Block until every submitted trajectory has been processed."""

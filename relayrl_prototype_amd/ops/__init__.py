@@ -68,10 +68,13 @@ from .mlp import (  # noqa: E402
     scan_flat,
 )
 from .integrity import payload_checksum, payload_verify  # noqa: E402
+from .evaluate import EvalTrace, evaluate_policy_op  # noqa: E402
 
 __all__ = [
     "payload_checksum",
     "payload_verify",
+    "EvalTrace",
+    "evaluate_policy_op",
     "hip",
     "hip_available",
     "use_hip",

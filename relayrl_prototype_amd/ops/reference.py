@@ -113,6 +113,30 @@ def mlp_forward_ref(mode, params, X, A, H, mask=None, act_in=None, actc_in=None,
     return res
 
 
+def greedy_from_logits(logits: torch.Tensor):
+    """(argmax action, gap between the two largest logits).  A tie takes the lowest index, like
+    rrl::argmax_first, and has gap 0; one action alone has an infinite gap."""
+    top = logits.max(dim=-1, keepdim=True).values
+    A = logits.shape[-1]
+    idx = torch.arange(A, device=logits.device).expand_as(logits)
+    act = torch.where(logits == top, idx, torch.full_like(idx, A)).min(dim=-1).values
+    if A == 1:
+        return act, torch.full(logits.shape[:-1], float("inf"), dtype=logits.dtype, device=logits.device)
+    two = torch.topk(logits, 2, dim=-1).values
+    return act, two[..., 0] - two[..., 1]
+
+
+@torch.no_grad()
+def greedy_actions_ref(params, obs, A, H, dtype=torch.float64):
+    """The greedy action of the categorical policy at ``obs`` [..., D] and the gap between its two
+    largest logits, computed in ``dtype``: what evaluate.hip's ``greedy = 1`` is held to wherever the
+    gap exceeds the kernel's logit error."""
+    D = obs.shape[-1]
+    logits, _ = trunk(params.to(dtype), obs.reshape(-1, D).to(dtype), D, H, A)
+    act, gap = greedy_from_logits(logits)
+    return act.reshape(obs.shape[:-1]), gap.reshape(obs.shape[:-1])
+
+
 def normalize_adv(adv, adv_stats):
     if adv_stats is None:
         return adv

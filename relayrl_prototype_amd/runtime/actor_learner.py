@@ -649,6 +649,11 @@ class ActorLearner:
         (n, s, _, _), _, _ = self._episode_vec()
         return n, s
 
+    def evaluate(self, *args, **kw):
+        from .evaluate import not_supported
+
+        not_supported("the actor-learner trainer (the weights live on the learner ranks)")
+
     def metrics(self) -> dict:
         """Collective over every rank (episode statistics) and the learner group (losses);
         the episode columns are identical on every rank."""

@@ -331,6 +331,11 @@ class EngineAlgorithm(AlgorithmAbstract):
             lg.log_tabular(k, float(v))
         lg.dump_tabular()
 
+    def evaluate(self, episodes: int = 1, num_envs: Optional[int] = None, greedy: bool = True):
+        """Score the current policy on whole episodes (VecTrainer.evaluate); the other engines'
+        trainers raise NotImplementedError."""
+        return self.trainer.evaluate(episodes=episodes, num_envs=num_envs, greedy=greedy)
+
     def episode_sums(self, m: Optional[Dict[str, Any]] = None):
         """(finished episodes, their return sum) of the last epoch, global over ranks."""
         if m is None and hasattr(self.trainer, "episode_sums"):
@@ -635,6 +640,11 @@ class RemoteEngineAlgorithm(AlgorithmAbstract):
 
     def train_model(self) -> None:
         raise RuntimeError("the ranks train in the child process; use TrainingServer.train()")
+
+    def evaluate(self, *args, **kw):
+        from .evaluate import not_supported
+
+        not_supported("the remote multi-rank engine (its trainers live in the child process)")
 
     def log_epoch(self) -> None:
         pass

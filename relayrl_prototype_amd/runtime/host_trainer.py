@@ -473,6 +473,11 @@ class HostVecTrainer:
             if self.overlap:
                 self.actor_params.copy_(self.learner.pi.params)
 
+    def evaluate(self, *args, **kw):
+        from .evaluate import not_supported
+
+        not_supported("the host-env trainer (its envs step on the CPU)")
+
     def metrics(self) -> dict:
         tot = {"n": 0.0, "sum": 0.0, "sumsq": 0.0, "max": -1e300, "min": 1e300, "sum_len": 0.0}
         for e in self.envs:

@@ -206,7 +206,8 @@ def _agree_resume(tr, comm, path: str) -> int:
 def run_preset(name: str, epochs: int, out_dir: str = "runs", overrides: Optional[Dict] = None,
                checkpoint_every: int = 0, resume: Optional[str] = None, log_every: int = 1,
                on_metrics: Optional[Callable[[Dict], None]] = None, auto_resume: bool = False,
-               elastic: bool = False) -> Dict:
+               elastic: bool = False, eval_every: int = 0, eval_episodes: int = 1,
+               eval_envs: Optional[int] = None) -> Dict:
     """Run one rank of a preset until ``epochs`` epochs are done; returns the last metrics
     (rank 0).  Checkpoints are per rank (each rank owns its env streams); with
     ``auto_resume`` a (re)started rank continues from its own latest checkpoint, which is
@@ -216,7 +217,11 @@ def run_preset(name: str, epochs: int, out_dir: str = "runs", overrides: Optiona
     leads to a re-form of the process group without it (parallel/elastic.py), the trainer is
     rebuilt on the smaller group from its in-memory state (learner state broadcast from the
     new rank 0) and the failed epoch is retried.  An evicted rank returns
-    ``{"Evicted": True}``."""
+    ``{"Evicted": True}``.
+
+    ``eval_every`` = K > 0: after every K-th epoch rank 0 scores the current policy on
+    ``eval_envs`` envs x ``eval_episodes`` whole greedy episodes (VecTrainer.evaluate) and every
+    logged row carries the ``Eval*`` columns of the latest evaluation (NaN before the first)."""
     import torch
 
     from ..parallel.comm import Comm, dist_env, init_distributed
@@ -245,6 +250,10 @@ def run_preset(name: str, epochs: int, out_dir: str = "runs", overrides: Optiona
         torch.cuda.set_device(dev)
     else:
         dev = torch.device("cpu")
+    if eval_every > 0 and preset.kind != "vec":
+        from .evaluate import not_supported
+
+        not_supported(f"the {preset.kind} preset {name!r} (--eval-every)")
     tr = _make_trainer(preset, comm, dev, overrides)
     start = 0
     if auto_resume and resume is None:
@@ -267,6 +276,7 @@ def run_preset(name: str, epochs: int, out_dir: str = "runs", overrides: Optiona
     from ..utils.faults import set_context
 
     completed = False
+    eval_cols = dict.fromkeys(EVAL_COLUMNS, float("nan")) if eval_every > 0 else None
     snap = EpochSnapshot() if eg is not None else None
     dump = os.environ.get("RRL_ELASTIC_DUMP") if eg is not None else None
     try:
@@ -338,10 +348,14 @@ def run_preset(name: str, epochs: int, out_dir: str = "runs", overrides: Optiona
                     kw = setup_logger_kwargs(f"relayrl-{name}", seed=int(overrides.get("seed", 0)), data_dir=out_dir)
                     logger = EpochLogger(**kw, quiet=True)
                 continue
+            if eval_cols is not None and ep % eval_every == 0 and comm.rank == 0:
+                eval_cols = eval_columns(tr.evaluate(episodes=eval_episodes, num_envs=eval_envs, greedy=True))
             if m is not None:
                 el = time.perf_counter() - t0
                 if comm.rank == 0 and m:
                     m = dict(m)
+                    if eval_cols is not None:
+                        m.update(eval_cols)
                     m["Time"] = el
                     if "EnvSteps" in m and el > 0:
                         m["EnvStepsPerSec"] = m["EnvSteps"] / el
@@ -375,6 +389,16 @@ def run_preset(name: str, epochs: int, out_dir: str = "runs", overrides: Optiona
         last["FinalWorld"] = comm.world
         eg.close()
     return last
+
+
+EVAL_COLUMNS = ("EvalAverageEpRet", "EvalStdEpRet", "EvalMinEpRet", "EvalMaxEpRet", "EvalEpLen", "EvalEpisodes")
+
+
+def eval_columns(res) -> Dict:
+    """The progress.txt columns of one evaluation (an EvalResult)."""
+    s = res.stats()
+    return {"EvalAverageEpRet": s["mean_return"], "EvalStdEpRet": s["std_return"], "EvalMinEpRet": s["min_return"],
+            "EvalMaxEpRet": s["max_return"], "EvalEpLen": s["mean_length"], "EvalEpisodes": float(s["episodes"])}
 
 
 def _dump_state(d: str, fname: str, tr) -> None:
@@ -456,8 +480,41 @@ def spawn_ranks(argv, gpus: int, max_restarts: int = 0) -> int:
     return subprocess.call(cmd, env=env)
 
 
-def main(argv=None) -> int:
-    argv = list(sys.argv[1:] if argv is None else argv)
+def spread_episodes(episodes: int, num_envs: int) -> tuple:
+    """(episodes per env, envs) for ``episodes`` in total on at most ``num_envs`` envs: whole episodes
+    per env, the fewest envs that reach the request (100 on <= 64 envs = 2 x 50)."""
+    per_env = -(-episodes // min(num_envs, episodes))
+    return per_env, -(-episodes // per_env)
+
+
+def run_evaluate(checkpoint: str, episodes: int = 100, num_envs: int = 1024, stochastic: bool = False,
+                 seed: int = 0, max_episode_steps: Optional[int] = None) -> Dict:
+    """Score the policy of a VecTrainer checkpoint directory (utils/checkpoint.py): the env, the
+    hidden size and the weights come from the checkpoint; ``episodes`` is the total, spread over
+    at most ``num_envs`` envs (rounded up to whole episodes per env).  Returns the EvalResult
+    fields plus what was evaluated."""
+    from ..utils.checkpoint import load_checkpoint
+    from .evaluate import evaluate_policy
+
+    st = load_checkpoint(checkpoint)
+    tr = st.get("trainer", st)
+    try:
+        cfg, params = tr["cfg"], tr["learner"]["pi"]["params"]
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"{checkpoint} is not a VecTrainer checkpoint (missing {e})") from None
+    if episodes < 1 or num_envs < 1:
+        raise ValueError("--episodes and --num-envs must be >= 1")
+    per_env, n = spread_episodes(int(episodes), int(num_envs))
+    limit = max_episode_steps or cfg.get("max_episode_steps")
+    res = evaluate_policy(cfg["env"], params, int(cfg["hidden"]), per_env, n, greedy=not stochastic, seed=seed,
+                          max_episode_steps=int(limit) if limit else None)
+    out = res.to_dict()
+    out.update(env=cfg["env"], hidden=int(cfg["hidden"]), num_envs=n, episodes_per_env=per_env,
+               checkpoint_epoch=int(tr.get("epoch", st.get("epoch", 0))))
+    return out
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m relayrl_prototype_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
     t = sub.add_parser("train", help="run a training preset (one process per GPU)")
@@ -472,6 +529,17 @@ def main(argv=None) -> int:
     t.add_argument("--max-restarts", type=int, default=0, help="torchrun group restarts after a rank failure")
     t.add_argument("--elastic", action="store_true",
                    help="survivors of a stalled rank re-form the group without it and continue")
+    t.add_argument("--eval-every", type=int, default=0,
+                   help="every K-th epoch rank 0 scores the policy on whole greedy episodes (0: never)")
+    t.add_argument("--eval-episodes", type=int, default=1, help="episodes per evaluation env")
+    t.add_argument("--eval-envs", type=int, default=None, help="evaluation envs (default: the trainer's num_envs)")
+    v = sub.add_parser("evaluate", help="score the policy of a VecTrainer checkpoint on whole episodes")
+    v.add_argument("--checkpoint", required=True, help="checkpoint directory (tensors.safetensors + state.json)")
+    v.add_argument("--episodes", type=int, default=100)
+    v.add_argument("--num-envs", type=int, default=1024)
+    v.add_argument("--stochastic", action="store_true", help="sample actions like training instead of the greedy one")
+    v.add_argument("--seed", type=int, default=0)
+    v.add_argument("--max-episode-steps", type=int, default=None)
     e = sub.add_parser("engine", help="one rank of a TrainingServer device engine (runtime/engine.py)")
     e.add_argument("--spec", required=True)
     e.add_argument("--env-dir", default=".")
@@ -491,7 +559,12 @@ def main(argv=None) -> int:
     b.add_argument("--force", action="store_true")
     p = sub.add_parser("plot", help="plot progress.txt runs")
     p.add_argument("rest", nargs=argparse.REMAINDER)
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    a = build_parser().parse_args(argv)
     if a.cmd == "presets":
         for k, v in PRESETS.items():
             print(f"{k:34s} [{v.kind}] {v.baseline_config}")
@@ -507,6 +580,10 @@ def main(argv=None) -> int:
         spec = EngineSpec.from_json(open(a.spec).read())
         return run_engine_rank(spec, a.env_dir, a.epochs, a.target_return, a.window, a.max_seconds, a.log_every,
                                a.publish_every, a.t_start_wall, a.result, a.relay_up, a.relay_down, a.version0)
+    if a.cmd == "evaluate":
+        print(json.dumps(run_evaluate(a.checkpoint, a.episodes, a.num_envs, a.stochastic, a.seed,
+                                      a.max_episode_steps)), flush=True)
+        return 0
     if a.cmd == "plot":
         from ..utils.plot import main as plot_main
 
@@ -524,7 +601,7 @@ def main(argv=None) -> int:
             pass
         ov[k] = v
     m = run_preset(a.preset, a.epochs, a.out, ov, a.checkpoint_every, a.resume, auto_resume=a.auto_resume,
-                   elastic=a.elastic)
+                   elastic=a.elastic, eval_every=a.eval_every, eval_episodes=a.eval_episodes, eval_envs=a.eval_envs)
     if m:
         print(json.dumps({k: v for k, v in m.items() if isinstance(v, (int, float, str))}), flush=True)
     return 0

@@ -296,6 +296,11 @@ class PixelA2CTrainer:
         self._last_stats = stats
         return stats
 
+    def evaluate(self, *args, **kw):
+        from .evaluate import not_supported
+
+        not_supported("the pixel (PongSynth A2C) trainer")
+
     def metrics(self):
         s = (self.env.episode_stats() if self.on_gpu else self.ep_sum).tolist()
         st = self._last_stats.sum(0).tolist() if hasattr(self, "_last_stats") else [0, 0, 0, 1]

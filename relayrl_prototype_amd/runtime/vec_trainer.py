@@ -136,6 +136,9 @@ class VecTrainer:
             self.comm.timer = self.timer  # AllReduce phase (gradient + statistics all-reduces)
         self.rl = RolloutLearner(self.learner, T, N, cfg.gamma, cfg.lam, self.comm, self.timer)
         self.env_seed = (cfg.seed * 0x9E3779B97F4A7C15 + rank * 0x632BE59BD9B4E019) & 0x7FFFFFFFFFFFFFFF
+        # evaluate() draws from a stream of its own: another key, and a counter that advances with every call
+        self.eval_seed = (self.env_seed ^ 0x5851F42D4C957F2D) & 0x7FFFFFFFFFFFFFFF
+        self.eval_step0 = 0
         # time-major SoA rollout buffers (HBM resident)
         self.obs = torch.zeros(T + 1, N, D, device=dev)
         if self.continuous:
@@ -181,6 +184,24 @@ class VecTrainer:
         self.rl.learn(self.obs, self.act, self.rew, self.done, self.logp, tobs=self.tobs)
         self.epoch += 1
         self.env_steps += self.B
+
+    # ------------------------------------------------------------------ evaluation
+    def evaluate(self, episodes: int = 1, num_envs: Optional[int] = None, greedy: bool = True):
+        """Score the current ``pi.params``: ``num_envs`` (default: the trainer's) fresh envs x ``episodes``
+        complete episodes each, greedy unless told otherwise (runtime/evaluate.py).  Rank-local, no
+        collectives; it reads the weights and touches none of the training state, buffers or
+        ``ep_stats``.  Its Philox stream is its own (``eval_seed``), and ``eval_step0`` moves past the
+        steps a call can consume, so two evaluations never repeat resets."""
+        from .evaluate import EvalResult
+        from ..ops import evaluate_policy_op
+
+        E, N = int(episodes), int(num_envs or self.cfg.num_envs)
+        step0 = self.eval_step0
+        ep_ret, ep_len, ep_code, _ = evaluate_policy_op(
+            self.env_id, self.pi.params, self.cfg.hidden, E, N, greedy=greedy, seed=self.eval_seed, step0=step0,
+            max_steps=self.max_steps, env_consts=self.env_consts if self.continuous else None)
+        self.eval_step0 += E * self.max_steps
+        return EvalResult(ep_ret, ep_len, ep_code, greedy, self.eval_seed, step0)
 
     # ------------------------------------------------------------------ metrics
     def metrics(self) -> dict:
