@@ -498,6 +498,67 @@ void pong_head_step(const Tensor& part, int64_t splits, const Tensor& fc_b, cons
            "pong_head_step");
 }
 
+// One policy-evaluation step (pong.hip): pong_head_step with the greedy (or sampled) action, no
+// stores for a backward pass, and the episode slots ep_ret / ep_len / ep_code [E][N] of the envs
+// that have finished fewer than E episodes (ep_cnt [N]); the others are frozen.  The step counters
+// are host values.  trace: tr_act [N] int32, tr_logits [N][A], tr_rew [N], tr_done [N]: all or none.
+void pong_eval_step(const Tensor& part, int64_t splits, const Tensor& fc_b, const Tensor& head_params, int64_t A,
+                    bool greedy, int64_t sample_seed, int64_t sample_step, const Tensor& state, const Tensor& rew,
+                    const Tensor& done, const Tensor& fin_ret, const Tensor& fin_len, const OptT& obs, int64_t N,
+                    int64_t seed, int64_t step, int64_t max_steps, int64_t E, const Tensor& ep_cnt, const Tensor& ep_ret,
+                    const Tensor& ep_len, const Tensor& ep_code, const Tensor& remaining, const OptT& frames,
+                    const OptT& fidx, int64_t ring_slots, const OptT& tr_act, const OptT& tr_logits, const OptT& tr_rew,
+                    const OptT& tr_done) {
+  constexpr int64_t F = 512;
+  TORCH_CHECK(A >= 1 && A <= 8 && splits >= 1 && N >= 1, "pong_eval_step: 1 <= A <= 8, splits >= 1, N >= 1");
+  TORCH_CHECK(E >= 1 && max_steps >= 1 && E * max_steps < (int64_t(1) << 31),
+              "pong_eval_step: E >= 1, max_steps >= 1 and E * max_steps < 2^31");
+  check(part, "part", at::kFloat, splits * N * F);
+  check(fc_b, "fc_b", at::kFloat, F);
+  check(head_params, "head_params", at::kFloat, A * F + A + F + 1);
+  check(state, "state", at::kFloat, N * pong_state_size());
+  check(rew, "rew", at::kFloat, N);
+  check(done, "done", at::kFloat, N);
+  check(fin_ret, "fin_ret", at::kFloat, N);
+  check(fin_len, "fin_len", at::kFloat, N);
+  check(ep_cnt, "ep_cnt", at::kInt, N);
+  check(remaining, "remaining", at::kInt, 1);
+  // the slots are indexed [k][N]: a tensor of another row length would be written across its rows
+  const auto slots = [&](const Tensor& t, const char* name, at::ScalarType dt) {
+    check(t, name, dt, E * N);
+    TORCH_CHECK(t.dim() == 2 && t.size(0) >= E && t.size(1) == N, name, " must be [E][N] = [", E, "][", N, "], got ",
+                t.sizes());
+  };
+  slots(ep_ret, "ep_ret", at::kFloat);
+  slots(ep_len, "ep_len", at::kInt);
+  slots(ep_code, "ep_code", at::kInt);
+  const int ntr = int(tr_act.has_value() && tr_act->defined()) + int(tr_logits.has_value() && tr_logits->defined()) +
+                  int(tr_rew.has_value() && tr_rew->defined()) + int(tr_done.has_value() && tr_done->defined());
+  TORCH_CHECK(ntr == 0 || ntr == 4, "pong_eval_step: tr_act, tr_logits, tr_rew and tr_done go together (all or none)");
+  int32_t* ta = opt_ptr<int32_t>(tr_act, "tr_act", at::kInt, N);
+  float* tl = opt_ptr<float>(tr_logits, "tr_logits", at::kFloat, N * A);
+  float* tr = opt_ptr<float>(tr_rew, "tr_rew", at::kFloat, N);
+  float* td = opt_ptr<float>(tr_done, "tr_done", at::kFloat, N);
+  uint8_t* fp = nullptr;
+  uint8_t* op = nullptr;
+  if (frames.has_value() && frames->defined()) {
+    fp = ring_store(frames, fidx, N, ring_slots);
+  } else {
+    TORCH_CHECK(obs.has_value() && obs->defined(), "pong_eval_step: obs or frames + fidx is required");
+    check(*obs, "obs", at::kByte, N * 84 * 84 * 4);
+    op = obs->data_ptr<uint8_t>();
+  }
+  rc_check(rrl_pong_eval_step(part.data_ptr<float>(), (int)splits, fc_b.data_ptr<float>(), head_params.data_ptr<float>(),
+                              (int)A, greedy ? 1 : 0, (uint64_t)sample_seed, (uint64_t)sample_step,
+                              state.data_ptr<float>(), rew.data_ptr<float>(), done.data_ptr<float>(),
+                              fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), op, (int)N, (uint64_t)seed,
+                              (uint64_t)step, (int)max_steps, fp, fp ? fidx->data_ptr<int32_t>() : nullptr,
+                              (int)ring_slots, (int)E, ep_cnt.data_ptr<int32_t>(), ep_ret.data_ptr<float>(),
+                              ep_len.data_ptr<int32_t>(), ep_code.data_ptr<int32_t>(), remaining.data_ptr<int32_t>(), ta,
+                              tl, tr, td, cur_stream()),
+           "pong_eval_step");
+}
+
 // The frame ring rebuilt from the env state (a restore): frames of steps st - 3 .. st, fidx [N][4]
 void pong_ring_fill(const Tensor& state, const Tensor& frames, const Tensor& fidx, int64_t N, int64_t ring_slots,
                     int64_t step, const OptT& step_base) {
@@ -595,6 +656,16 @@ void register_cnn_ops(pybind11::module_& m) {
         pybind11::arg("N"), pybind11::arg("seed"), pybind11::arg("step"), pybind11::arg("step_base"),
         pybind11::arg("max_steps"), pybind11::arg("frames") = pybind11::none(), pybind11::arg("fidx") = pybind11::none(),
         pybind11::arg("ring_slots") = 0);
+  m.def("pong_eval_step", &pong_eval_step, pybind11::arg("part"), pybind11::arg("splits"), pybind11::arg("fc_b"),
+        pybind11::arg("head_params"), pybind11::arg("A"), pybind11::arg("greedy"), pybind11::arg("sample_seed"),
+        pybind11::arg("sample_step"), pybind11::arg("state"), pybind11::arg("rew"), pybind11::arg("done"),
+        pybind11::arg("fin_ret"), pybind11::arg("fin_len"), pybind11::arg("obs"), pybind11::arg("N"),
+        pybind11::arg("seed"), pybind11::arg("step"), pybind11::arg("max_steps"), pybind11::arg("E"),
+        pybind11::arg("ep_cnt"), pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"),
+        pybind11::arg("remaining"), pybind11::arg("frames") = pybind11::none(), pybind11::arg("fidx") = pybind11::none(),
+        pybind11::arg("ring_slots") = 0, pybind11::arg("tr_act") = pybind11::none(),
+        pybind11::arg("tr_logits") = pybind11::none(), pybind11::arg("tr_rew") = pybind11::none(),
+        pybind11::arg("tr_done") = pybind11::none());
   m.def("pong_ring_fill", &pong_ring_fill, pybind11::arg("state"), pybind11::arg("frames"), pybind11::arg("fidx"),
         pybind11::arg("N"), pybind11::arg("ring_slots"), pybind11::arg("step"), pybind11::arg("step_base") = pybind11::none());
   m.def("pong_render", &pong_render);

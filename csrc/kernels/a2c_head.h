@@ -68,14 +68,32 @@ __device__ __forceinline__ void head_sum_part(float (&v)[8], const float* pr, si
   }
 }
 
+// Lowest index among the maximal logits (the tie rule of evaluate.hip's argmax_first).
+RRL_DEV int head_argmax_first(int A, const float (&logits)[kMaxAct]) {
+  int pick = 0;
+  float best = logits[0];
+#pragma unroll
+  for (int o = 1; o < kMaxAct; ++o)
+    if (o < A && logits[o] > best) {
+      best = logits[o];
+      pick = o;
+    }
+  return pick;
+}
+
 // Rollout mode, one wave per row, head weights STREAMED from global (L2) per output instead of
 // held in registers (the fused Pong kernel runs at <= 64 VGPRs): h = bf16(relu(fc_b + sum_z
 // part[z][row])) stored to h_out, then the same logits / value / sample arithmetic, in the same
 // order, as a2c_head_kernel<false, AMAX> -- so the two paths agree bitwise.  Lane 0 writes
 // act / logp / value and returns the action; other lanes return -1.
 // (WV / WP: where the value / policy weight rows are read -- a.w_v / a.w, or an LDS copy)
-template <int AMAX>
-RRL_DEV int a2c_rollout_row_streamed(const HeadArgs& a, int row, int lane, const float* WV, const float* WP) {
+// EVAL (policy evaluation, pong.hip's pong_eval_step_kernel): nothing is stored for a backward
+// pass -- no h_out, no value, no act / logp -- the logits go to lg_out[A] when given, and
+// greedy != 0 takes the lowest index among the maximal logits instead of the draw.  The logits
+// and the draw are the same expressions in the same order, so they stay bitwise the rollout's.
+template <int AMAX, bool EVAL = false>
+RRL_DEV int a2c_rollout_row_streamed(const HeadArgs& a, int row, int lane, const float* WV, const float* WP,
+                                     int greedy = 0, float* lg_out = nullptr) {
   const int A = a.A, F = kHeadF;
   const float4 b0 = *reinterpret_cast<const float4*>(a.fc_b + 8 * lane);
   const float4 b1 = *reinterpret_cast<const float4*>(a.fc_b + 8 * lane + 4);
@@ -91,7 +109,7 @@ RRL_DEV int a2c_rollout_row_streamed(const HeadArgs& a, int row, int lane, const
 #pragma unroll
   for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
   const uint4 hv = pack_bf16x8(v);
-  *reinterpret_cast<uint4*>(a.h_out + (size_t)row * F + 8 * lane) = hv;
+  if constexpr (!EVAL) *reinterpret_cast<uint4*>(a.h_out + (size_t)row * F + 8 * lane) = hv;
   const uint32_t hw[4] = {hv.x, hv.y, hv.z, hv.w};
   float x[8];
 #pragma unroll
@@ -102,15 +120,16 @@ RRL_DEV int a2c_rollout_row_streamed(const HeadArgs& a, int row, int lane, const
   float logits[kMaxAct];
 #pragma unroll
   for (int o = 0; o < kMaxAct; ++o) logits[o] = -INFINITY;
-  float vsum = 0.f;
-  {
+  float value = 0.f;
+  if constexpr (!EVAL) {
+    float vsum = 0.f;
     const float4 w0 = *reinterpret_cast<const float4*>(WV + 8 * lane);
     const float4 w1 = *reinterpret_cast<const float4*>(WV + 8 * lane + 4);
     const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
 #pragma unroll
     for (int i = 0; i < 8; ++i) vsum += wv[i] * x[i];
+    value = wave_sum(vsum) + a.b_v[0];
   }
-  const float value = wave_sum(vsum) + a.b_v[0];
 #pragma unroll
   for (int o = 0; o < AMAX; ++o) {
     if (o < A) {
@@ -122,6 +141,27 @@ RRL_DEV int a2c_rollout_row_streamed(const HeadArgs& a, int row, int lane, const
       for (int i = 0; i < 8; ++i) s += wp[i] * x[i];
       logits[o] = wave_sum(s) + a.bias[o];
     }
+  }
+  if constexpr (EVAL) {
+    int pick = -1;
+    if (lane == 0) {
+      if (lg_out) {
+#pragma unroll
+        for (int o = 0; o < AMAX; ++o)
+          if (o < A) lg_out[o] = logits[o];
+      }
+      if (greedy) {
+        pick = head_argmax_first(A, logits);
+      } else {
+        const CatStats cs = cat_stats(A, logits);
+        unsigned long long st = ((unsigned long long)a.step_hi << 32) | a.step_lo;
+        if (a.step_base) st += *a.step_base;
+        const uint4 r = philox4x32(make_uint4((uint32_t)(row + a.row_offset), (uint32_t)st, (uint32_t)(st >> 32), 0x50u),
+                                   make_uint2(a.seed_lo, a.seed_hi));
+        pick = cat_sample(A, logits, cs.lse, u01(r.x));
+      }
+    }
+    return pick;
   }
   const CatStats cs = cat_stats(A, logits);
   int pick = -1;

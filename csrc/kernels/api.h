@@ -197,5 +197,18 @@ int rrl_pong_head_step_render(const float* part, int splits, const float* fc_b, 
                               float* fin_ret, float* fin_len, float* ep_acc, uint8_t* obs, int N,
                               unsigned long long seed, unsigned long long step, const unsigned long long* step_base,
                               int max_steps, uint8_t* frames, int32_t* fidx, int R, void* stream);
+// One policy-evaluation step: the head (greedy != 0: lowest index among the maximal logits, else the
+// rollout's draw) + env step at the host counter `step` + render (frames + fidx, or obs) of every env
+// with ep_cnt[e] < E; the others are frozen and nothing of theirs is written.  A finished episode
+// fills slot ep_cnt[e] of ep_ret / ep_len / ep_code [E][N] (code 1: a score reached 21, 2: the time
+// limit) and the env's E-th one decrements *remaining.  tr_act / tr_rew / tr_done [N], tr_logits
+// [N][A]: all four or none.  -1: a null or inconsistent argument; -2: E or max_steps below 1, or
+// E * max_steps >= 2^31; -3: A > 8
+int rrl_pong_eval_step(const float* part, int splits, const float* fc_b, const float* head_params, int A, int greedy,
+                       unsigned long long sample_seed, unsigned long long sample_step, float* state, float* rew,
+                       float* done, float* fin_ret, float* fin_len, uint8_t* obs, int N, unsigned long long seed,
+                       unsigned long long step, int max_steps, uint8_t* frames, int32_t* fidx, int R, int E,
+                       int32_t* ep_cnt, float* ep_ret, int32_t* ep_len, int32_t* ep_code, int32_t* remaining,
+                       int32_t* tr_act, float* tr_logits, float* tr_rew, float* tr_done, void* stream);
 
 }  // extern "C"

@@ -52,10 +52,16 @@ RRL_DEV void reset_env(float* s, uint4 r) {
 // One env's step (frame-skip 4); state row written back.  Shared by pong_step_kernel (one
 // thread per env) and pong_step_render_kernel (one workgroup per env).
 // s: the env's state row, in registers (pong_step_env) or in LDS (pong_step_render_kernel).
+// end (policy evaluation): how the step ended the episode and the finished episode's totals.
+struct PongEnd {
+  int cause;  // 0 still running, 1 a score reached 21 (also exactly at the time limit), 2 the time limit alone
+  float ret, len;
+};
+
 RRL_DEV void pong_step_state(int e, float* s, int a, float* __restrict__ rew,
                              float* __restrict__ done, float* __restrict__ fin_ret, float* __restrict__ fin_len,
                              float* __restrict__ ep_acc, uint2 key, uint32_t step_lo, uint32_t step_hi, int max_steps,
-                             int reset_all, const unsigned long long* __restrict__ step_base) {
+                             int reset_all, const unsigned long long* __restrict__ step_base, PongEnd* end = nullptr) {
   if (step_base) {  // device step counter (graph replays): the host value is an offset
     const unsigned long long st = (((unsigned long long)step_hi << 32) | step_lo) + *step_base;
     step_lo = (uint32_t)st;
@@ -110,6 +116,11 @@ RRL_DEV void pong_step_state(int e, float* s, int a, float* __restrict__ rew,
     done[e] = over ? 1.f : 0.f;
     fin_ret[e] = over ? s[P_RET] : 0.f;
     fin_len[e] = over ? s[P_T] : 0.f;
+    if (end) {
+      end->cause = !over ? 0 : ((s[P_SA] >= 21.f || s[P_SO] >= 21.f) ? 1 : 2);
+      end->ret = s[P_RET];
+      end->len = s[P_T];
+    }
     if (over && ep_acc) {  // per-env running episode statistics: count, sum ret, sum len, sum ret^2
       float* acc = ep_acc + 4 * (size_t)e;
       acc[0] += 1.f;
@@ -357,6 +368,78 @@ __global__ void __launch_bounds__(256, 8) pong_head_step_render_kernel(
   for (int q = threadIdx.x; q < kChunks; q += 256)
     *reinterpret_cast<uint4*>(o + (size_t)q * 16) = pong_render_chunk_rows(hist, rows, q);
 }
+
+// Policy evaluation's bookkeeping (rrl_pong_eval_step): every env plays E whole episodes, slot k of
+// ep_ret / ep_len / ep_code [E][N] is its k-th, ep_cnt[N] how many it has finished, *remaining the
+// envs that have not finished E yet.  tr_*: the step's trace rows, all four or none.
+struct EvalOut {
+  int32_t* ep_cnt;
+  float* ep_ret;
+  int32_t* ep_len;
+  int32_t* ep_code;
+  int32_t* remaining;
+  int E, greedy;
+  int32_t* tr_act;    // [N]
+  float* tr_logits;   // [N][A]
+  float* tr_rew;      // [N]
+  float* tr_done;     // [N]
+};
+
+// One evaluation step: pong_head_step_render_kernel with the greedy (or the rollout's sampled)
+// action, nothing stored for a backward pass, and the per-env episode slots.  An env that has
+// finished its E episodes is FROZEN: its workgroup leaves before the first barrier (ep_cnt[e] is
+// uniform over the workgroup and only thread 0 writes it, after the barriers) and writes nothing,
+// so its state, frames, fidx row and trace rows stay what its last step left.
+template <int AMAX, bool RING>
+__global__ void __launch_bounds__(256, 8) pong_eval_step_kernel(
+    HeadArgs ha, EvalOut ev, float* __restrict__ state, float* __restrict__ rew, float* __restrict__ done,
+    float* __restrict__ fin_ret, float* __restrict__ fin_len, uint8_t* __restrict__ obs, uint2 key, uint32_t step_lo,
+    uint32_t step_hi, int max_steps, RingOut ro) {
+  constexpr int kChunks = kPongHW * kPongHW * 4 / 16;
+  __shared__ float ss[kPongState];
+  __shared__ uint32_t rows[kPongHW];
+  __shared__ int pick_s;
+  const int e = blockIdx.x, t = threadIdx.x, N = gridDim.x;
+  const int k = ev.ep_cnt[e];
+  if (k >= ev.E) return;
+  if (t < kPongState) ss[t] = state[(size_t)e * kPongState + t];
+  if (t < 64) {
+    const int pick = a2c_rollout_row_streamed<AMAX, true>(ha, e, t, ha.w_v, ha.w, ev.greedy,
+                                                          ev.tr_logits ? ev.tr_logits + (size_t)e * ha.A : nullptr);
+    if (t == 0) pick_s = pick;
+  }
+  __syncthreads();
+  if (t == 0) {
+    PongEnd end;
+    pong_step_state(e, ss, pick_s, rew, done, fin_ret, fin_len, nullptr, key, step_lo, step_hi, max_steps, 0, nullptr,
+                    &end);
+    if (ev.tr_act) {
+      ev.tr_act[e] = pick_s;
+      ev.tr_rew[e] = rew[e];
+      ev.tr_done[e] = end.cause ? 1.f : 0.f;
+    }
+    if (end.cause) {
+      const size_t slot = (size_t)k * N + e;
+      ev.ep_ret[slot] = end.ret;
+      ev.ep_len[slot] = (int32_t)end.len;
+      ev.ep_code[slot] = end.cause;
+      ev.ep_cnt[e] = k + 1;
+      if (k + 1 == ev.E) atomicSub(ev.remaining, 1);
+    }
+  }
+  __syncthreads();
+  if (t < kPongState) state[(size_t)e * kPongState + t] = ss[t];
+  if constexpr (RING) {
+    pong_ring_write(ro, e, N, ss, rows, pong_abs_step(step_lo, step_hi, nullptr));
+    return;
+  }
+  const float* hist = ss + P_HIST;
+  if (t < kPongHW) rows[t] = pong_row_flags(hist, t);
+  __syncthreads();
+  uint8_t* o = obs + (size_t)e * kChunks * 16;
+  for (int q = threadIdx.x; q < kChunks; q += 256)
+    *reinterpret_cast<uint4*>(o + (size_t)q * 16) = pong_render_chunk_rows(hist, rows, q);
+}
 }  // namespace rrl
 
 using namespace rrl;
@@ -472,6 +555,50 @@ int rrl_pong_head_step_render(const float* part, int splits, const float* fc_b, 
     hipLaunchKernelGGL((pong_head_step_render_kernel<8, false>), dim3(N), dim3(256), 0, (hipStream_t)stream_, a, state, rew, done,
                        fin_ret, fin_len, ep_acc, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, step_base, ro);
   }
+  return (int)hipGetLastError();
+}
+
+// One policy-evaluation step of N envs (pong_eval_step_kernel): head (greedy: lowest index among
+// the maximal logits; else the rollout's draw at sample_step) + env step at the host counter
+// `step` + render, for the envs with ep_cnt[e] < E; a finished episode fills slot ep_cnt[e] of
+// ep_ret / ep_len / ep_code [E][N] and the env's E-th one decrements *remaining.
+int rrl_pong_eval_step(const float* part, int splits, const float* fc_b, const float* head_params, int A, int greedy,
+                       unsigned long long sample_seed, unsigned long long sample_step, float* state, float* rew,
+                       float* done, float* fin_ret, float* fin_len, uint8_t* obs, int N, unsigned long long seed,
+                       unsigned long long step, int max_steps, uint8_t* frames, int32_t* fidx, int R, int E,
+                       int32_t* ep_cnt, float* ep_ret, int32_t* ep_len, int32_t* ep_code, int32_t* remaining,
+                       int32_t* tr_act, float* tr_logits, float* tr_rew, float* tr_done, void* stream_) {
+  if (N < 1 || A < 1 || splits < 1 || !part || !fc_b || !head_params || !state || !rew || !done || !fin_ret || !fin_len)
+    return -1;
+  if (frames ? (!fidx || R < 5) : !obs) return -1;
+  if (!ep_cnt || !ep_ret || !ep_len || !ep_code || !remaining) return -1;
+  const int ntr = (tr_act != nullptr) + (tr_logits != nullptr) + (tr_rew != nullptr) + (tr_done != nullptr);
+  if (ntr != 0 && ntr != 4) return -1;
+  if (E < 1 || max_steps < 1 || (long long)E * max_steps >= (1ll << 31)) return -2;
+  if (A > 8) return -3;
+  const RingOut ro{frames, fidx, R};
+  HeadArgs a = {};
+  a.part = part;
+  a.splits = splits;
+  a.fc_b = fc_b;
+  a.w = head_params;
+  a.bias = head_params + A * kHeadF;
+  a.w_v = a.bias + A;
+  a.b_v = a.w_v + kHeadF;
+  a.B = N;
+  a.A = A;
+  a.seed_lo = (uint32_t)sample_seed;
+  a.seed_hi = (uint32_t)(sample_seed >> 32);
+  a.step_lo = (uint32_t)sample_step;
+  a.step_hi = (uint32_t)(sample_step >> 32);
+  const EvalOut ev{ep_cnt, ep_ret, ep_len, ep_code, remaining, E, greedy ? 1 : 0, tr_act, tr_logits, tr_rew, tr_done};
+  const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
+  if (frames)
+    hipLaunchKernelGGL((pong_eval_step_kernel<8, true>), dim3(N), dim3(256), 0, (hipStream_t)stream_, a, ev, state, rew, done,
+                       fin_ret, fin_len, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, ro);
+  else
+    hipLaunchKernelGGL((pong_eval_step_kernel<8, false>), dim3(N), dim3(256), 0, (hipStream_t)stream_, a, ev, state, rew, done,
+                       fin_ret, fin_len, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, ro);
   return (int)hipGetLastError();
 }
 

@@ -219,7 +219,7 @@ class TrainingServer:
     def evaluate(self, episodes: int = 1, num_envs: Optional[int] = None, greedy: bool = True):
         """Score the engine's current policy: ``num_envs`` device envs x ``episodes`` whole episodes
         each, greedy unless told otherwise -> EvalResult (runtime/evaluate.py).  For the in-process
-        ``vec`` engine; the others raise NotImplementedError."""
+        ``vec`` and ``pixel`` engines; the others raise NotImplementedError."""
         if self.engine is None:
             raise NotImplementedError("evaluate() is not implemented for a server that learns from agent uploads: "
                                       "it needs the in-process vec engine (engine=\"vec\")")

@@ -315,6 +315,30 @@ class DevicePong:
             self.advance(1)
         return rew, done
 
+    def eval_step(self, part, splits: int, fc_b, head_params, A: int, sample_seed: int, sample_step: int, step: int,
+                  obs_out, episodes: int, ep_cnt, ep_ret, ep_len, ep_code, remaining, greedy: bool = True, ring=None,
+                  trace=None, rew_out=None, done_out=None):
+        """One policy-evaluation step (pong.hip ``pong_eval_step_kernel``): ``step_head`` with the
+        greedy action (lowest index among the maximal logits; ``greedy=False``: the action
+        ``DeviceNatureCNN.act`` samples at ``sample_step``), no hidden-unit / logp / value stores, and
+        whole-episode bookkeeping: an env's k-th finished episode goes to ``ep_ret`` / ``ep_len`` /
+        ``ep_code`` ``[k, env]`` (code 1: a score reached 21, 2: the time limit), ``ep_cnt`` [N] counts
+        them, and an env that has finished ``episodes`` of them is frozen -- nothing of it is written
+        any more -- after taking 1 off the device counter ``remaining`` (int32, started at N).  ``step``
+        is the env's Philox step counter as a host value: the device counter ``step_t`` is neither
+        read nor advanced.  ``trace``: (act [N] int32, logits [N, A], rew [N], done [N]) rows of this
+        step, written for the envs that stepped.  There is no CPU fallback."""
+        rew = self.rew if rew_out is None else rew_out
+        done = self.done if done_out is None else done_out
+        rk = {} if ring is None else {"frames": ring.frames, "fidx": obs_out, "ring_slots": ring.R}
+        if trace is not None:
+            rk.update(zip(("tr_act", "tr_logits", "tr_rew", "tr_done"), trace))
+        self.h.pong_eval_step(part, int(splits), fc_b, head_params, int(A), bool(greedy), int(sample_seed),
+                              int(sample_step), self.state, rew, done, self.fin_ret, self.fin_len,
+                              None if ring is not None else obs_out, self.N, self.seed, int(step), self.max_steps,
+                              int(episodes), ep_cnt, ep_ret, ep_len, ep_code, remaining, **rk)
+        return rew, done
+
     def step(self, act: torch.Tensor, obs_out: torch.Tensor = None, rew_out=None, done_out=None, offset: int = None,
              hist_out: torch.Tensor = None, ring=None):
         """One env step.  Without ``offset`` the device counter is advanced after the step;

@@ -332,8 +332,8 @@ class EngineAlgorithm(AlgorithmAbstract):
         lg.dump_tabular()
 
     def evaluate(self, episodes: int = 1, num_envs: Optional[int] = None, greedy: bool = True):
-        """Score the current policy on whole episodes (VecTrainer.evaluate); the other engines'
-        trainers raise NotImplementedError."""
+        """Score the current policy on whole episodes (VecTrainer.evaluate, PixelA2CTrainer.evaluate);
+        the other engines' trainers raise NotImplementedError."""
         return self.trainer.evaluate(episodes=episodes, num_envs=num_envs, greedy=greedy)
 
     def episode_sums(self, m: Optional[Dict[str, Any]] = None):

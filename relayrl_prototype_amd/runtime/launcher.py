@@ -220,8 +220,9 @@ def run_preset(name: str, epochs: int, out_dir: str = "runs", overrides: Optiona
     ``{"Evicted": True}``.
 
     ``eval_every`` = K > 0: after every K-th epoch rank 0 scores the current policy on
-    ``eval_envs`` envs x ``eval_episodes`` whole greedy episodes (VecTrainer.evaluate) and every
-    logged row carries the ``Eval*`` columns of the latest evaluation (NaN before the first)."""
+    ``eval_envs`` envs x ``eval_episodes`` whole greedy episodes (VecTrainer.evaluate, or
+    PixelA2CTrainer.evaluate for the pixel presets; other kinds are refused) and every logged row
+    carries the ``Eval*`` columns of the latest evaluation (NaN before the first)."""
     import torch
 
     from ..parallel.comm import Comm, dist_env, init_distributed
@@ -250,7 +251,7 @@ def run_preset(name: str, epochs: int, out_dir: str = "runs", overrides: Optiona
         torch.cuda.set_device(dev)
     else:
         dev = torch.device("cpu")
-    if eval_every > 0 and preset.kind != "vec":
+    if eval_every > 0 and preset.kind not in ("vec", "pixel"):
         from .evaluate import not_supported
 
         not_supported(f"the {preset.kind} preset {name!r} (--eval-every)")
@@ -489,28 +490,72 @@ def spread_episodes(episodes: int, num_envs: int) -> tuple:
 
 def run_evaluate(checkpoint: str, episodes: int = 100, num_envs: int = 1024, stochastic: bool = False,
                  seed: int = 0, max_episode_steps: Optional[int] = None) -> Dict:
-    """Score the policy of a VecTrainer checkpoint directory (utils/checkpoint.py): the env, the
-    hidden size and the weights come from the checkpoint; ``episodes`` is the total, spread over
-    at most ``num_envs`` envs (rounded up to whole episodes per env).  Returns the EvalResult
-    fields plus what was evaluated."""
+    """Score the policy of a VecTrainer or pixel (PongSynth A2C) trainer checkpoint directory
+    (utils/checkpoint.py): the env, the model shape and the weights come from the checkpoint;
+    ``episodes`` is the total, spread over at most ``num_envs`` envs (rounded up to whole episodes
+    per env).  Returns the EvalResult fields plus what was evaluated (``hidden`` only for a
+    VecTrainer checkpoint)."""
     from ..utils.checkpoint import load_checkpoint
+
+    return evaluate_checkpoint_state(load_checkpoint(checkpoint), checkpoint, episodes, num_envs, stochastic, seed,
+                                     max_episode_steps)
+
+
+def is_pixel_checkpoint(tr) -> bool:
+    """A PixelA2CTrainer.state_dict() of the GPU path: its ``model`` entry and a PongSynth-v0 config."""
+    try:
+        return "model" in tr and tr["cfg"]["env"] == "PongSynth-v0"
+    except (KeyError, TypeError):
+        return False
+
+
+def evaluate_checkpoint_state(st, checkpoint: str = "<state>", episodes: int = 100, num_envs: int = 1024,
+                              stochastic: bool = False, seed: int = 0,
+                              max_episode_steps: Optional[int] = None) -> Dict:
+    """``run_evaluate`` on an already loaded checkpoint dict ``st``."""
     from .evaluate import evaluate_policy
 
-    st = load_checkpoint(checkpoint)
-    tr = st.get("trainer", st)
-    try:
-        cfg, params = tr["cfg"], tr["learner"]["pi"]["params"]
-    except (KeyError, TypeError) as e:
-        raise ValueError(f"{checkpoint} is not a VecTrainer checkpoint (missing {e})") from None
+    tr = st.get("trainer", st) if isinstance(st, dict) else st
+    pixel = is_pixel_checkpoint(tr)
+    if not pixel:
+        try:
+            cfg, params = tr["cfg"], tr["learner"]["pi"]["params"]
+        except (KeyError, TypeError) as e:
+            raise ValueError(f"{checkpoint} is not a VecTrainer checkpoint (missing {e}) nor a pixel (PongSynth A2C) "
+                             "trainer's") from None
     if episodes < 1 or num_envs < 1:
         raise ValueError("--episodes and --num-envs must be >= 1")
     per_env, n = spread_episodes(int(episodes), int(num_envs))
+    if pixel:
+        return _evaluate_pixel_checkpoint(st, tr, per_env, n, stochastic, seed, max_episode_steps)
     limit = max_episode_steps or cfg.get("max_episode_steps")
     res = evaluate_policy(cfg["env"], params, int(cfg["hidden"]), per_env, n, greedy=not stochastic, seed=seed,
                           max_episode_steps=int(limit) if limit else None)
     out = res.to_dict()
     out.update(env=cfg["env"], hidden=int(cfg["hidden"]), num_envs=n, episodes_per_env=per_env,
                checkpoint_epoch=int(tr.get("epoch", st.get("epoch", 0))))
+    return out
+
+
+def _evaluate_pixel_checkpoint(st, tr, per_env: int, n: int, stochastic: bool, seed: int,
+                               max_episode_steps: Optional[int]) -> Dict:
+    """A pixel trainer's weights in a DeviceNatureCNN of their own (``max_batch = n``), scored by
+    ``evaluate_pixel_policy``."""
+    import torch
+
+    from ..models.nature_cnn import CNNSpec, DeviceNatureCNN
+    from .evaluate import evaluate_pixel_policy
+
+    cfg = tr["cfg"]
+    if not torch.cuda.is_available():
+        raise RuntimeError("evaluating a pixel (PongSynth A2C) checkpoint needs a GPU: it runs the fused HIP kernels")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    model = DeviceNatureCNN(CNNSpec(act_dim=6), dev, max_batch=n, params=tr["model"]["params"])
+    limit = max_episode_steps or cfg.get("max_episode_steps") or 27000 // 4
+    res = evaluate_pixel_policy(model, per_env, n, greedy=not stochastic, seed=seed, max_episode_steps=int(limit))
+    out = res.to_dict()
+    out.update(env=cfg["env"], num_envs=n, episodes_per_env=per_env,
+               checkpoint_epoch=int(tr.get("updates", st.get("epoch", 0) if isinstance(st, dict) else 0)))
     return out
 
 
@@ -530,10 +575,11 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--elastic", action="store_true",
                    help="survivors of a stalled rank re-form the group without it and continue")
     t.add_argument("--eval-every", type=int, default=0,
-                   help="every K-th epoch rank 0 scores the policy on whole greedy episodes (0: never)")
+                   help="every K-th epoch rank 0 scores the policy on whole greedy episodes (0: never; the "
+                        "vec and pixel presets)")
     t.add_argument("--eval-episodes", type=int, default=1, help="episodes per evaluation env")
     t.add_argument("--eval-envs", type=int, default=None, help="evaluation envs (default: the trainer's num_envs)")
-    v = sub.add_parser("evaluate", help="score the policy of a VecTrainer checkpoint on whole episodes")
+    v = sub.add_parser("evaluate", help="score the policy of a VecTrainer or pixel (PongSynth A2C) checkpoint on whole episodes")
     v.add_argument("--checkpoint", required=True, help="checkpoint directory (tensors.safetensors + state.json)")
     v.add_argument("--episodes", type=int, default=100)
     v.add_argument("--num-envs", type=int, default=1024)

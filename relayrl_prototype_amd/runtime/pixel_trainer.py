@@ -77,6 +77,9 @@ class PixelA2CTrainer:
         rank = self.comm.rank
         env_seed = (cfg.seed * 1000003 + rank * 7919 + 17) & 0x7FFFFFFFFFFFFFFF
         self.sample_seed = (cfg.seed * 2654435761 + rank * 97 + 5) & 0x7FFFFFFFFFFFFFFF
+        # evaluate() draws from a stream of its own: another key, and a counter that advances with every call
+        self.eval_seed = (env_seed ^ 0x5851F42D4C957F2D) & 0x7FFFFFFFFFFFFFFF
+        self.eval_step0 = 0
         dev = self.device
         import os
 
@@ -296,10 +299,30 @@ class PixelA2CTrainer:
         self._last_stats = stats
         return stats
 
-    def evaluate(self, *args, **kw):
-        from .evaluate import not_supported
+    def evaluate(self, episodes: int = 1, num_envs: Optional[int] = None, greedy: bool = True):
+        """Score the current weights: ``num_envs`` (default and at most the trainer's) fresh envs x
+        ``episodes`` whole episodes each, greedy unless told otherwise (runtime/evaluate.py
+        ``evaluate_pixel_policy``).  Rank-local, no collectives.  It runs through the trainer's own
+        model in the bootstrap scratch rows ``T * N ..`` and an env, frame ring and Philox stream
+        (``eval_seed``, an ``eval_step0`` that moves past the steps a call can consume) of its own:
+        parameters, Adam state, the training envs and their counters, observation buffers, the
+        stored activations of the rollout rows and the captured graphs are left as they are.  The
+        CPU oracle path has no fused kernels and refuses."""
+        if not getattr(self, "on_gpu", False):
+            from .evaluate import not_supported
 
-        not_supported("the pixel (PongSynth A2C) trainer")
+            not_supported("the pixel (PongSynth A2C) trainer's CPU oracle path")
+        from .evaluate import evaluate_pixel_policy
+
+        cfg = self.cfg
+        E, N = int(episodes), int(num_envs or cfg.num_envs)
+        if N > cfg.num_envs:
+            raise ValueError(f"evaluate: num_envs {N} exceeds the trainer's {cfg.num_envs} (its scratch rows)")
+        step0 = self.eval_step0
+        res = evaluate_pixel_policy(self.model, E, N, greedy=greedy, seed=self.eval_seed, step0=step0,
+                                    max_episode_steps=cfg.max_episode_steps, row0=cfg.rollout_len * cfg.num_envs)
+        self.eval_step0 += E * cfg.max_episode_steps + 1
+        return res
 
     def metrics(self):
         s = (self.env.episode_stats() if self.on_gpu else self.ep_sum).tolist()
