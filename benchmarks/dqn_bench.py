@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""DQN throughput on one MI355X at the shape of the ``cartpole-dqn`` preset (1,024 envs x 4 steps,
+batch 1,024, 4 updates per epoch, H = 128, eager launches).
+
+One JSON line:
+
+* ``env_steps_per_s`` / ``grad_steps_per_s``: ``DQNTrainer.train_epoch()`` end to end (wall clock
+  around ``--epochs`` epochs after ``--warmup``, the ring filled and learning under way);
+* ``*_us``: microseconds per launch of the three kernels from HIP events around ``--iters`` back-to-back
+  launches each (median of ``--reps`` windows): ``dqn_rollout``, ``dqn_targets``, ``mlp_grad(Q_TD)``.
+  Launches are eager, so a figure is bounded below by the host's issue interval: a spread of a few
+  hundredths of a microsecond between windows says the kernel, not the host, set it;
+* ``mlp_grad_pg_cat_us``: ``mlp_grad(PG_CAT)`` at the same B, D, H and A on the fp32-MFMA kernel Q_TD
+  uses (the value-grad mode switched to 0 for the reading): the two share everything but the head.
+
+    python benchmarks/dqn_bench.py --out profiles/dqn_bench.jsonl
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch
+
+
+def event_us(fn, iters, reps):
+    """Median over ``reps`` windows of the mean microseconds of ``iters`` back-to-back calls."""
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(1e3 * a.elapsed_time(b) / iters)
+    return round(statistics.median(out), 3), round(min(out), 3), round(max(out), 3)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--epochs", type=int, default=2000)
+    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--tag", default="")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("dqn_bench needs a GPU: a CPU timing says nothing about the MI355X")
+    from relayrl_prototype_amd.ops import GradHead, dqn_rollout, dqn_targets, mlp_grad, set_value_grad_mode
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    cfg = DQNConfig(**PRESETS["cartpole-dqn"].overrides)
+    tr = DQNTrainer(cfg, device=dev)
+    for _ in range(a.warmup):
+        tr.train_epoch()
+    assert tr.updates > 0, "the warm-up must reach learning_starts"
+    torch.cuda.synchronize()
+    u0, t0 = tr.updates, time.perf_counter()
+    for _ in range(a.epochs):
+        tr.train_epoch()
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    N, T, B = cfg.num_envs, cfg.rollout_len, cfg.batch_size
+    rec = dict(bench="dqn", preset="cartpole-dqn", env=cfg.env, num_envs=N, rollout_len=T, batch_size=B,
+               hidden=cfg.hidden, updates_per_epoch=cfg.updates_per_epoch, epochs=a.epochs,
+               env_steps_per_s=round(a.epochs * N * T / el, 1), grad_steps_per_s=round((tr.updates - u0) / el, 1),
+               epoch_us=round(1e6 * el / a.epochs, 2))
+
+    filled = min(tr.slots_written, cfg.buffer_slots) * N
+
+    def rollout():  # the same slot and step every time: timing only
+        dqn_rollout(tr.env_id, tr.q.params, cfg.hidden, T, 0, tr.ring, tr.state, tr.ep_len, tr.ep_ret, tr.ep_stats,
+                    seed=tr.env_seed, step0=0, epsilon=0.1, reset_all=False, max_steps=tr.max_steps)
+
+    def targets():
+        dqn_targets(tr.q.params, tr.target, cfg.hidden, tr.A, tr.ring, filled, cfg.gamma, cfg.double_q, tr.sample_seed,
+                    7, B, out=(tr.Xb, tr.act_b, tr.y, None))
+
+    def grad_q():
+        mlp_grad(GradHead.Q_TD, tr.q.params, tr.Xb, tr.A, cfg.hidden, act=tr.act_b, ret=tr.y, clip_eps=cfg.huber_delta,
+                 grad_slab=tr.slab, loss_slab=tr.loss)
+
+    adv = torch.randn(B, device=dev)
+
+    def grad_pg():
+        mlp_grad(GradHead.PG_CAT, tr.q.params, tr.Xb, tr.A, cfg.hidden, act=tr.act_b, adv=adv, grad_slab=tr.slab,
+                 loss_slab=tr.loss)
+
+    old = set_value_grad_mode(0)  # PG_CAT on the fp32-MFMA kernel, like Q_TD
+    try:
+        for name, fn in (("dqn_rollout", rollout), ("dqn_targets", targets), ("mlp_grad_q_td", grad_q),
+                         ("mlp_grad_pg_cat", grad_pg)):
+            fn()
+            torch.cuda.synchronize()
+            med, lo, hi = event_us(fn, a.iters, a.reps)
+            rec[name + "_us"] = med
+            rec[name + "_us_range"] = [lo, hi]
+    finally:
+        set_value_grad_mode(old)
+    rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

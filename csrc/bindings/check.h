@@ -17,6 +17,9 @@ using OptT = std::optional<Tensor>;
 // Launches go to the current HIP stream (capturable into a hipGraph via torch.cuda.graph).
 inline void* cur_stream() { return (void*)at::hip::getCurrentHIPStream().stream(); }
 
+// CUs the grids of this process are sized for (hip_ops.cpp: the device's, or set_cu_limit's).
+int grid_cus();
+
 // On its own where the minimum is known only after other arguments have been checked.
 inline void check_numel(const Tensor& t, const char* name, int64_t min_numel) {
   TORCH_CHECK(t.numel() >= min_numel, name, " has ", t.numel(), " elements, need >= ", min_numel);

@@ -1,0 +1,101 @@
+// Bindings of the DQN kernels (csrc/kernels/dqn.hip): the epsilon-greedy actor that fills the replay
+// ring and the sample + gather + TD-target kernel.  Every tensor is validated before a launch.
+#include <tuple>
+
+#include "api.h"
+#include "check.h"
+
+namespace {
+
+using namespace rrl;
+using namespace rrl_bind;
+
+int64_t dqn_rollout_grid(int64_t N) { return rrl_dqn_rollout_grid((int)N, grid_cus()); }
+
+// The ring is obs / nobs [C, N, D], act / rew / done [C, N]; returns (C, N).
+std::tuple<int64_t, int64_t> check_ring(int64_t D, const Tensor& obs, const Tensor& nobs, const Tensor& act,
+                                        const Tensor& rew, const Tensor& done) {
+  check(act, "ring act", at::kInt);
+  TORCH_CHECK(act.dim() == 2 && act.size(0) >= 1 && act.size(1) >= 1, "ring act must be [C, N]");
+  const int64_t C = act.size(0), N = act.size(1);
+  TORCH_CHECK(C * N * std::max<int64_t>(D, 1) < (int64_t)INT32_MAX, "replay ring too large for 32-bit rows");
+  check(obs, "ring obs", at::kFloat, C * N * D);
+  check(nobs, "ring nobs", at::kFloat, C * N * D);
+  check(rew, "ring rew", at::kFloat, C * N);
+  check(done, "ring done", at::kFloat, C * N);
+  TORCH_CHECK(obs.numel() == C * N * D && nobs.numel() == C * N * D && rew.numel() == C * N && done.numel() == C * N,
+              "ring tensors disagree on [C, N, D]");
+  return {C, N};
+}
+
+// Returns the kernel's code for a launch that would wrap (-4, nothing written); raises for anything else.
+int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
+                    const Tensor& ep_len, const Tensor& ep_ret, const Tensor& obs, const Tensor& nobs,
+                    const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& ep_stats, int64_t seed,
+                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps) {
+  int D = 0, A = 0, NS = 0, ms = 0;
+  TORCH_CHECK(rrl_env_dims((int)env, &D, &A, &NS, &ms) == 0, "unknown device env id ", env);
+  TORCH_CHECK(env != ENV_HALFCHEETAH, "dqn_rollout takes the discrete device envs");
+  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
+  TORCH_CHECK(T >= 1 && max_steps >= 1, "T and max_steps must be >= 1");
+  check(params, "params", at::kFloat, (int64_t)H * D + H + H * H + H + (int64_t)A * H + A);
+  auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
+  check(state, "state", at::kFloat, N * NS);
+  check(ep_len, "ep_len", at::kInt, N);
+  check(ep_ret, "ep_ret", at::kFloat, N);
+  check(ep_stats, "ep_stats", at::kFloat, dqn_rollout_grid(N) * 8);
+  TORCH_CHECK(slot0 >= 0 && slot0 < (int64_t)INT32_MAX && T < (int64_t)INT32_MAX, "slot0 / T out of range");
+  const int rc = rrl_dqn_rollout((int)env, params.data_ptr<float>(), (int)N, (int)T, (int)H, (int)C, (int)slot0,
+                                 state.data_ptr<float>(), ep_len.data_ptr<int>(), ep_ret.data_ptr<float>(),
+                                 obs.data_ptr<float>(), nobs.data_ptr<float>(), act.data_ptr<int>(),
+                                 rew.data_ptr<float>(), done.data_ptr<float>(), ep_stats.data_ptr<float>(),
+                                 (uint64_t)seed, (uint64_t)step0, (float)epsilon, reset_all ? 1 : 0, (int)max_steps,
+                                 grid_cus(), cur_stream());
+  if (rc == -4) return rc;
+  check_rc(rc, "dqn_rollout");
+  return 0;
+}
+
+void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
+                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
+                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
+                 const OptT& idx) {
+  TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
+  const int64_t D = obs.size(2);
+  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
+  TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
+  TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
+  auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
+  TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
+  const int64_t P = H * D + H + H * H + H + A * H + A;
+  check(target, "target", at::kFloat, P);
+  const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
+  TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
+  check(y, "y", at::kFloat);
+  const int64_t B = y.numel();
+  TORCH_CHECK(B >= 1 && B * D < (int64_t)INT32_MAX, "batch size out of range");
+  check(Xb, "Xb", at::kFloat, B * D);
+  check(act_b, "act_b", at::kInt, B);
+  int* ix = opt_ptr<int>(idx, "idx", at::kInt, B);
+  check_rc(rrl_dqn_targets(on, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
+                           act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(), (long long)filled,
+                           (int)B, (int)D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0, (uint64_t)sample_key,
+                           (uint64_t)update, Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(), ix,
+                           grid_cus(), cur_stream()),
+           "dqn_targets");
+}
+
+}  // namespace
+
+void register_dqn_ops(pybind11::module_& m) {
+  namespace py = pybind11;
+  m.def("dqn_rollout_grid", &dqn_rollout_grid);
+  m.def("dqn_rollout", &dqn_rollout, py::arg("env"), py::arg("params"), py::arg("H"), py::arg("T"), py::arg("slot0"),
+        py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"), py::arg("act"),
+        py::arg("rew"), py::arg("done"), py::arg("ep_stats"), py::arg("seed"), py::arg("step0"), py::arg("epsilon"),
+        py::arg("reset_all"), py::arg("max_steps"));
+  m.def("dqn_targets", &dqn_targets, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"), py::arg("obs"),
+        py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"), py::arg("gamma"),
+        py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"),
+        py::arg("idx"));
+}

@@ -108,25 +108,26 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_PG_GAUSS, "bad head");
+  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_TD, "bad head");
   TORCH_CHECK(B * std::max<int64_t>(D, A) < (int64_t)INT32_MAX, "batch too large for 32-bit row indexing");
   const bool gauss = head == HEAD_PPO_GAUSS || head == HEAD_PG_GAUSS;
   const bool cat = head == HEAD_PG_CAT || head == HEAD_PPO_CAT;
   const bool value = head == HEAD_VALUE_MSE;
+  const bool qtd = head == HEAD_Q_TD;  // reads act + ret; no advantages
   const int64_t P = flat_size(D, H, value ? 1 : A, gauss);
   check_numel(params, "params", P);
   const int64_t nslab = mlp_grad_slabs(B);
   check(grad_slab, "grad_slab", at::kFloat, nslab * P);
   check(loss_slab, "loss_slab", at::kFloat, nslab * 8);
   const float* m = opt_ptr<const float>(mask, "mask", at::kFloat, B * A);
-  const int* a = opt_ptr<const int>(act, "act", at::kInt, cat ? B : 0);
-  if (cat) TORCH_CHECK(a != nullptr, "act required for categorical heads");
+  const int* a = opt_ptr<const int>(act, "act", at::kInt, cat || qtd ? B : 0);
+  if (cat || qtd) TORCH_CHECK(a != nullptr, "act required for categorical and Q heads");
   const float* ac = opt_ptr<const float>(actc, "actc", at::kFloat, gauss ? B * A : 0);
   if (gauss) TORCH_CHECK(ac != nullptr, "actc required for Gaussian heads");
   const float* ad = opt_ptr<const float>(adv, "adv", at::kFloat, B);
-  if (!value) TORCH_CHECK(ad != nullptr, "adv required for policy heads");
+  if (!value && !qtd) TORCH_CHECK(ad != nullptr, "adv required for policy heads");
   const float* rt = opt_ptr<const float>(ret, "ret", at::kFloat, B);
-  if (value) TORCH_CHECK(rt != nullptr, "ret required for the value head");
+  if (value || qtd) TORCH_CHECK(rt != nullptr, "ret required for the value and Q heads");
   const float* lpo = opt_ptr<const float>(logp_old, "logp_old", at::kFloat, B);
   if (head == HEAD_PPO_CAT || head == HEAD_PPO_GAUSS) TORCH_CHECK(lpo != nullptr, "logp_old required for PPO heads");
   const float* st = opt_ptr<const float>(adv_stats, "adv_stats", at::kFloat, 3);
@@ -479,6 +480,11 @@ void evaluate_cont(int64_t env, const Tensor& params, const Tensor& env_consts, 
 
 void register_cnn_ops(pybind11::module_& m);      // cnn_ops.cpp
 void register_rollout_ops(pybind11::module_& m);  // rollout_ops.cpp (host-env rollout driver)
+void register_dqn_ops(pybind11::module_& m);      // dqn_ops.cpp
+
+namespace rrl_bind {
+int grid_cus() { return num_cus(); }
+}  // namespace rrl_bind
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "relayrl_prototype_amd gfx950 HIP kernels";
@@ -544,10 +550,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("FWD_MODES") = pybind11::dict(RRL_ENUM(MODE_VALUE), RRL_ENUM(MODE_CAT_SAMPLE), RRL_ENUM(MODE_CAT_EVAL),
                                        RRL_ENUM(MODE_LOGITS), RRL_ENUM(MODE_GAUSS_SAMPLE), RRL_ENUM(MODE_GAUSS_EVAL));
   m.attr("GRAD_HEADS") = pybind11::dict(RRL_ENUM(HEAD_PG_CAT), RRL_ENUM(HEAD_VALUE_MSE), RRL_ENUM(HEAD_PPO_CAT),
-                                        RRL_ENUM(HEAD_PPO_GAUSS), RRL_ENUM(HEAD_PG_GAUSS));
+                                        RRL_ENUM(HEAD_PPO_GAUSS), RRL_ENUM(HEAD_PG_GAUSS), RRL_ENUM(HEAD_Q_TD));
   m.attr("ENV_IDS") = pybind11::dict(RRL_ENUM(ENV_CARTPOLE), RRL_ENUM(ENV_MOUNTAINCAR), RRL_ENUM(ENV_ACROBOT),
                                      RRL_ENUM(ENV_LUNARLANDER), RRL_ENUM(ENV_HALFCHEETAH));
 #undef RRL_ENUM
   register_cnn_ops(m);
   register_rollout_ops(m);
+  register_dqn_ops(m);
 }

@@ -24,6 +24,7 @@ enum GradHead : int {
   HEAD_PPO_CAT = 2,    // PPO clipped surrogate, categorical
   HEAD_PPO_GAUSS = 3,  // PPO clipped surrogate, diagonal Gaussian
   HEAD_PG_GAUSS = 4,   // REINFORCE / A2C with a Gaussian policy
+  HEAD_Q_TD = 5,       // DQN: loss = mean(huber(Q(x)[act] - ret, delta)); delta travels in clip_eps
 };
 
 enum EnvId : int { ENV_CARTPOLE = 0, ENV_MOUNTAINCAR = 1, ENV_ACROBOT = 2, ENV_LUNARLANDER = 3, ENV_HALFCHEETAH = 4 };
@@ -42,7 +43,8 @@ int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D,
 int rrl_set_value_fwd_mode(int mode);
 
 // ---- mlp_grad.hip
-// head: a GradHead
+// head: a GradHead.  HEAD_Q_TD reads act and ret (the TD target) and takes its Huber threshold delta
+// from clip_eps, which it has no other use for; mask, adv, logp_old and ent_coef are ignored
 int rrl_mlp_grad(int head, const float* params, const float* X, int B, int D, int A, int H, const float* mask,
                  const int* act, const float* actc, const float* adv, const float* ret, const float* logp_old,
                  const float* adv_stats, float inv_B, float clip_eps, float ent_coef, float* grad_slab,
@@ -119,6 +121,29 @@ int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int
                       float* ep_ret, int* ep_len, int* ep_code, float* tr_obs, float* tr_act, float* tr_rew,
                       float* tr_done, uint64_t seed, uint64_t step0, int greedy, int max_steps, int num_cu,
                       void* stream);
+
+// ---- dqn.hip
+// Epsilon-greedy actor: T steps of N envs into slots slot0 .. slot0 + T - 1 of a replay ring of C slots
+// (obs / nobs [C][N][D], act / rew / done [C][N]; nobs = the post-step, pre-reset observation; done 0
+// running, 1 terminal, 2 time limit).  state / ep_len / ep_ret / reset_all / max_steps / ep_stats as
+// rrl_rollout, with ep_stats [rrl_dqn_rollout_grid()][8].  -1: a null pointer; -2: N, T, C or max_steps
+// below 1; -3: unsupported H or env; -4 (nothing written): a launch that would wrap, i.e. unless
+// C % T == 0, slot0 % T == 0 and slot0 + T <= C
+int rrl_dqn_rollout_grid(int N, int num_cu);
+int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, int slot0, float* state, int* ep_len,
+                    float* ep_ret, float* obs, float* nobs, int* act, float* rew, float* done, float* ep_stats,
+                    uint64_t seed, uint64_t step0, float epsilon, int reset_all, int max_steps, int num_cu,
+                    void* stream);
+// Batch row b of update `update` samples ring row r = (philox((b, update, 0), sample_key).x * filled) >> 32
+// of the first `filled` rows ([slot][env] order), gathers obs[r] -> Xb[b], act[r] -> act_b[b], r -> idx[b]
+// (idx may be null) and writes y[b] = rew[r] + gamma * (done[r] == 1 ? 0 : 1) * Q_target(nobs[r], a*), a* =
+// the lowest-index argmax of Q_target (double_q = 0) or Q_online (double_q = 1; online may be null
+// otherwise).  -1: a null pointer; -2: filled < 1 or >= 2^31, or B < 1; -3: H not 64 / 128, D outside
+// [1, 16] or A outside [1, 16]
+int rrl_dqn_targets(const float* online, const float* target, const float* obs, const float* nobs, const int* act,
+                    const float* rew, const float* done, long long filled, int B, int D, int A, int H, float gamma,
+                    int double_q, uint64_t sample_key, uint64_t update, float* Xb, int* act_b, float* y, int* idx,
+                    int num_cu, void* stream);
 
 // ---- cnn.hip (bf16 tensors as uint16_t)
 int rrl_conv_fwd(const void* x, int x_u8, const uint16_t* w, const float* b, uint16_t* y, int N, int H, int W,

@@ -7,7 +7,7 @@
 // 64-row slabs (16 rows per wave):
 //
 //   forward   : h1 = relu(W1 x + b1), h2 = relu(W2 h1 + b2)       (MFMA, registers)
-//   head      : dout = dLoss/d(out) for PG / value-MSE / PPO heads  (VALU epilogue)
+//   head      : dout = dLoss/d(out) for PG / value-MSE / PPO / Q-TD heads (VALU epilogue)
 //   bwd data  : dh2 = W3^T dout * (h2>0) (VALU), dh1 = W2^T dh2 * (h1>0) (MFMA)
 //   bwd weight: dW3, dW2, dW1 as MFMA products that sum over the batch.  The batch
 //               index lives on the lane axis of the activation tiles, so each
@@ -227,6 +227,24 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
         s_loss += loss_i;
         s_ent += cs.entropy;
         if (p.logp_old) s_kl += p.logp_old[row] - logp;
+        s_cnt += 1.f;
+      }
+    } else if (HEAD == HEAD_Q_TD) {
+      // Q-learning: Huber loss on Q(x)[act] - target, threshold delta = clip_eps
+      float qs[kMaxAct];
+      policy_logits<HT>(lds + L::W3, lds + L::B3, A, H, h2, qs);
+      const int act = valid ? p.act[row] : 0;
+      const float q = pick_logit(A, qs, act);
+      const float diff = valid ? q - p.ret[row] : 0.f;
+      const float delta = p.clip_eps;
+      const float ad = fabsf(diff);
+      const float dq = (valid ? invB : 0.f) * fminf(fmaxf(diff, -delta), delta);
+#pragma unroll
+      for (int a = 0; a < kMaxAct; ++a)
+        if (a < A) dout[a] = (a == act) ? dq : 0.f;
+      if (count) {
+        s_loss += ad <= delta ? 0.5f * diff * diff : delta * (ad - 0.5f * delta);
+        s_val += q;
         s_cnt += 1.f;
       }
     } else {  // Gaussian heads
@@ -478,6 +496,7 @@ static int dispatch_head(int head, const GradArgs& a, int grid, hipStream_t s) {
     case HEAD_PPO_CAT: return dispatch_a3<DT, HT, HEAD_PPO_CAT>(a, grid, s);
     case HEAD_PPO_GAUSS: return dispatch_a3<DT, HT, HEAD_PPO_GAUSS>(a, grid, s);
     case HEAD_PG_GAUSS: return dispatch_a3<DT, HT, HEAD_PG_GAUSS>(a, grid, s);
+    case HEAD_Q_TD: return dispatch_a3<DT, HT, HEAD_Q_TD>(a, grid, s);
   }
   return -1;
 }

@@ -1,6 +1,7 @@
 """Algorithm registry + custom-plugin loader.
 
-Built-ins: REINFORCE, PPO, A2C.  Custom algorithms follow the reference contract
+Built-ins: REINFORCE, PPO, A2C (DQN has no trajectory learner: it exists only as the single-rank
+device engine, ``TrainingServer("DQN", ..., engine="vec")``, runtime/dqn_trainer.py).  Custom algorithms follow the reference contract
 (python_algorithm_reply.py:16-52): ``<algorithm_dir>/<NAME>/<NAME>.py`` defines class
 ``<NAME>``; it is imported in-process (no subprocess / JSON pipe) and constructed with
 ``env_dir, config_path, obs_dim, act_dim, buf_size`` plus the hyperparameter overrides

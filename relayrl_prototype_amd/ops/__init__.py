@@ -69,12 +69,19 @@ from .mlp import (  # noqa: E402
 )
 from .integrity import payload_checksum, payload_verify  # noqa: E402
 from .evaluate import EvalTrace, evaluate_policy_op  # noqa: E402
+from .dqn import ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_sample_rows_ref, dqn_targets, dqn_targets_ref  # noqa: E402
 
 __all__ = [
     "payload_checksum",
     "payload_verify",
     "EvalTrace",
     "evaluate_policy_op",
+    "ReplayRing",
+    "dqn_rollout",
+    "dqn_rollout_grid",
+    "dqn_sample_rows_ref",
+    "dqn_targets",
+    "dqn_targets_ref",
     "hip",
     "hip_available",
     "use_hip",

@@ -1,0 +1,114 @@
+"""DQN device ops (csrc/kernels/dqn.hip) and their host oracles.
+
+* ``dqn_rollout``: the epsilon-greedy fused actor; T steps of N device envs into T slots of a replay
+  ring.  Like ``evaluate_policy_op`` it has no PyTorch path: it needs the HIP extension and GPU tensors.
+* ``dqn_targets``: sample ring rows, gather the batch and build the TD targets from the target (and,
+  for double Q-learning, the online) network.  CPU tensors take ``dqn_targets_ref``.
+* ``dqn_sample_rows_ref`` / ``dqn_targets_ref``: the oracles the kernel is held to.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import philox
+from . import reference as ref
+
+
+class ReplayRing(NamedTuple):
+    """Time-major SoA replay ring of C slots x N envs; a ring row is ``slot * N + env``."""
+    obs: torch.Tensor   # [C, N, D] the observation the action was computed from
+    nobs: torch.Tensor  # [C, N, D] the post-step, pre-reset observation
+    act: torch.Tensor   # [C, N] int32
+    rew: torch.Tensor   # [C, N]
+    done: torch.Tensor  # [C, N] 0 running, 1 terminal, 2 time-limit truncation
+
+    @staticmethod
+    def allocate(C: int, N: int, D: int, device) -> "ReplayRing":
+        return ReplayRing(torch.zeros(C, N, D, device=device), torch.zeros(C, N, D, device=device),
+                          torch.zeros(C, N, dtype=torch.int32, device=device), torch.zeros(C, N, device=device),
+                          torch.zeros(C, N, device=device))
+
+
+def dqn_rollout_grid(num_envs: int) -> int:
+    """Rows of the ``ep_stats`` tensor ``dqn_rollout`` fills for ``num_envs`` envs."""
+    from . import hip
+
+    return int(hip().dqn_rollout_grid(int(num_envs)))
+
+
+def dqn_rollout(env_id: int, params: torch.Tensor, hidden: int, rollout_len: int, slot0: int, ring: ReplayRing,
+                state, ep_len, ep_ret, ep_stats, *, seed: int, step0: int, epsilon: float, reset_all: bool,
+                max_steps: int) -> int:
+    """T = ``rollout_len`` epsilon-greedy steps of every env into ring slots ``slot0 .. slot0 + T - 1``.
+    Returns 0, or the kernel's negative code (nothing written) for a launch that would wrap: unless
+    ``C % T == 0``, ``slot0 % T == 0`` and ``slot0 + T <= C``.  Asynchronous on the current stream."""
+    from . import hip
+
+    h = hip()  # raises NativeExtensionMissing: there is no fallback
+    if not params.is_cuda:
+        raise ValueError("dqn_rollout runs the HIP kernel only: params must be a GPU tensor")
+    return int(h.dqn_rollout(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len, ep_ret,
+                             ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed), int(step0),
+                             float(epsilon), bool(reset_all), int(max_steps)))
+
+
+def dqn_sample_rows_ref(seed: int, update: int, B: int, filled: int) -> np.ndarray:
+    """int64 [B]: the ring rows batch rows 0 .. B - 1 of update ``update`` read,
+    ``(philox((b, update_lo, update_hi, 0), seed).x * filled) >> 32``."""
+    if filled < 1 or filled >= 2 ** 31:
+        raise ValueError(f"filled must be in [1, 2^31), got {filled}")
+    b = np.arange(B, dtype=np.uint32)
+    n = b.shape
+    x = philox.philox4x32(b, np.full(n, update & 0xFFFFFFFF, np.uint32), np.full(n, (update >> 32) & 0xFFFFFFFF, np.uint32),
+                          np.zeros(n, np.uint32), np.full(n, seed & 0xFFFFFFFF, np.uint32),
+                          np.full(n, (seed >> 32) & 0xFFFFFFFF, np.uint32))[0]
+    return ((x.astype(np.uint64) * np.uint64(filled)) >> np.uint64(32)).astype(np.int64)
+
+
+@torch.no_grad()
+def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: int, gamma: float, double_q: bool,
+                    seed: int, update: int, B: int, dtype=torch.float32):
+    """-> ``(Xb [B, D], act_b [B] int32, y [B], idx [B] int64)`` in ``dtype``;
+    ``y = rew + gamma * (done == 1 ? 0 : 1) * Q_target(nobs, a*)`` with ``a*`` the lowest-index argmax of the
+    target (``double_q`` false) or online net."""
+    D = ring.obs.shape[-1]
+    idx = torch.from_numpy(dqn_sample_rows_ref(seed, update, B, filled)).to(ring.obs.device)
+    obs = ring.obs.reshape(-1, D)[idx]
+    nobs = ring.nobs.reshape(-1, D)[idx].to(dtype)
+    q_t, _ = ref.trunk(target.to(dtype), nobs, D, H, A)
+    sel = ref.trunk(online.to(dtype), nobs, D, H, A)[0] if double_q else q_t
+    astar, _ = ref.greedy_from_logits(sel)
+    boot = (ring.done.reshape(-1)[idx] != 1).to(dtype)
+    y = ring.rew.reshape(-1)[idx].to(dtype) + gamma * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
+    return obs, ring.act.reshape(-1)[idx].to(torch.int32), y, idx
+
+
+def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
+                gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32):
+    """Sample, gather and TD target in one launch -> ``(Xb, act_b, y, idx)``; ``out`` = the four tensors to
+    write into (``idx`` int32 on the GPU, or None to skip it).  CPU tensors take the torch reference in
+    ``dtype``; a GPU tensor without the extension raises."""
+    from . import use_hip, hip
+
+    if not use_hip(target):
+        Xb, act_b, y, idx = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype)
+        if out is not None:
+            for dst, src in zip(out, (Xb, act_b, y, idx)):
+                if dst is not None:
+                    dst.copy_(src)
+            return out
+        return Xb, act_b, y, idx
+    dev = target.device
+    D = ring.obs.shape[-1]
+    if out is None:
+        out = (torch.empty(B, D, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    Xb, act_b, y, idx = out
+    if y.numel() != B:
+        raise ValueError(f"y must hold {B} targets, got {y.numel()}")
+    hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
+                      ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), Xb, act_b, y, idx)
+    return out

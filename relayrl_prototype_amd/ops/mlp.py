@@ -31,6 +31,7 @@ class GradHead(IntEnum):
     PPO_CAT = 2
     PPO_GAUSS = 3
     PG_GAUSS = 4
+    Q_TD = 5  # DQN: Huber loss on Q(x)[act] - ret; the threshold delta travels in clip_eps
 
 
 from ..models.mlp_spec import MLPSpec  # noqa: E402,F401 -- torch-free (CPU agents import it)

@@ -14,7 +14,7 @@ import torch
 from . import philox
 
 MODE_VALUE, MODE_CAT_SAMPLE, MODE_CAT_EVAL, MODE_LOGITS, MODE_GAUSS_SAMPLE, MODE_GAUSS_EVAL = range(6)
-HEAD_PG_CAT, HEAD_VALUE_MSE, HEAD_PPO_CAT, HEAD_PPO_GAUSS, HEAD_PG_GAUSS = range(5)
+HEAD_PG_CAT, HEAD_VALUE_MSE, HEAD_PPO_CAT, HEAD_PPO_GAUSS, HEAD_PG_GAUSS, HEAD_Q_TD = range(6)
 HALF_LOG_2PI = 0.91893853320467274
 
 
@@ -149,7 +149,8 @@ def normalize_adv(adv, adv_stats):
 def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None, ret=None, logp_old=None,
                  adv_stats=None, inv_B=None, clip_eps=0.2, ent_coef=0.0, dtype=torch.float32):
     """Returns (flat gradient, stats dict) of sum_i loss_i * inv_B (+ entropy bonus);
-    ``dtype=torch.float64`` gives the float64 oracle (tools/grad_fuzz_probe.py)."""
+    ``dtype=torch.float64`` gives the float64 oracle (tools/grad_fuzz_probe.py).
+    ``HEAD_Q_TD``: loss_i = huber(Q(x_i)[act_i] - ret_i, delta) with delta = ``clip_eps``."""
     B, D = X.shape
     gaussian = head in (HEAD_PPO_GAUSS, HEAD_PG_GAUSS)
     Aeff = 1 if head == HEAD_VALUE_MSE else A
@@ -163,6 +164,13 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
         li = (v - ret) ** 2
         loss = li.sum() * inv_B
         stats.update(loss=li.sum().item(), v=v.sum().item(), count=B)
+    elif head == HEAD_Q_TD:
+        q = out.gather(-1, act.long().unsqueeze(-1)).squeeze(-1)
+        diff = q - ret.to(dtype)
+        ad = diff.abs()
+        li = torch.where(ad <= clip_eps, 0.5 * diff * diff, clip_eps * (ad - 0.5 * clip_eps))
+        loss = li.sum() * inv_B
+        stats.update(loss=li.sum().item(), v=q.sum().item(), count=B)
     else:
         advn = normalize_adv(adv.to(dtype), None if adv_stats is None else adv_stats.to(dtype))
         if not gaussian:

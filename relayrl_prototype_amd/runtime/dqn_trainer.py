@@ -1,0 +1,245 @@
+"""DQN on the device: epsilon-greedy fused actor -> replay ring in HBM -> sampled TD updates.
+
+One epoch (single rank, eager launches):
+
+  1. ``dqn_rollout``: T steps x N envs of Q-network forward + epsilon-greedy action + env physics,
+     written into T slots of a ring of ``buffer_slots`` (csrc/kernels/dqn.hip).  The host owns the
+     epsilon schedule (linear, ``eps_start`` -> ``eps_end`` over ``eps_decay_epochs``) and the cursor.
+  2. once ``slots_written * N >= learning_starts``: ``updates_per_epoch`` x
+       ``dqn_targets``  sample + gather + TD target from the target (and online: double Q) network
+       ``mlp_grad(Q_TD)``  fused forward + Huber head + backward  (csrc/kernels/mlp_grad.hip)
+       ``adam_step``  slab-summing fused Adam
+     and every ``target_update_every`` updates the target network copies the online one.
+
+Every random draw is Philox at explicit coordinates (env streams: (env, global step); replay
+samples: (batch row, update)), so a run is a pure function of the seed and ``state_dict()`` /
+``load_state_dict()`` resume it bit for bit.  The API mirrors ``VecTrainer``.  Left for later:
+several ranks, hipGraph capture, prioritised replay, n-step returns, serving the policy to agents
+(the trainer exposes no ``learner``, so a TrainingServer engine publishes no model).
+"""
+from __future__ import annotations
+
+from dataclasses import asdict, dataclass
+from typing import Optional
+
+import torch
+
+from ..algorithms.core import FlatNet
+from ..ops import GradHead, MLPSpec, ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_targets, grad_slabs, hip, mlp_grad
+from ..parallel.comm import Comm
+from .rollout_learn import episode_metrics
+from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
+
+
+@dataclass
+class DQNConfig:
+    env: str = "CartPole-v1"
+    num_envs: int = 1024
+    rollout_len: int = 4            # T: env steps per env and epoch
+    hidden: int = 128
+    algo: str = "dqn"
+    buffer_slots: int = 256         # C: ring capacity in steps (C * num_envs transitions), a multiple of T
+    batch_size: int = 1024
+    updates_per_epoch: int = 4
+    gamma: float = 0.99
+    q_lr: float = 5e-4
+    eps_start: float = 1.0
+    eps_end: float = 0.05
+    eps_decay_epochs: int = 500
+    learning_starts: int = 8192     # transitions in the ring before the first update
+    target_update_every: int = 100  # updates between target <- online copies
+    double_q: bool = True
+    huber_delta: float = 1.0
+    seed: int = 1
+    max_episode_steps: Optional[int] = None
+
+    def to_dict(self):
+        return asdict(self)
+
+
+def dqn_seeds(seed: int) -> tuple:
+    """(env, replay-sample, evaluation) Philox keys of a run: three streams that never share draws."""
+    env = (int(seed) * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+    return env, (env ^ 0x2545F4914F6CDD1D) & 0x7FFFFFFFFFFFFFFF, (env ^ 0x5851F42D4C957F2D) & 0x7FFFFFFFFFFFFFFF
+
+
+def epsilon_at(cfg: DQNConfig, epoch: int) -> float:
+    """The exploration rate of (0-based) epoch ``epoch``: linear from eps_start to eps_end over eps_decay_epochs."""
+    frac = min(1.0, epoch / cfg.eps_decay_epochs) if cfg.eps_decay_epochs > 0 else 1.0
+    return float(cfg.eps_start + (cfg.eps_end - cfg.eps_start) * frac)
+
+
+class DQNTrainer:
+    def __init__(self, cfg: DQNConfig, comm: Optional[Comm] = None, device=None):
+        self.cfg = cfg
+        self.comm = comm or Comm()
+        if self.comm.multi:
+            raise ValueError("the DQN trainer is single-rank (world_size 1)")
+        if cfg.env in CONTINUOUS_DEVICE_ENVS:
+            raise ValueError(f"DQN needs a discrete action space; {cfg.env!r} is continuous")
+        if cfg.env not in DEVICE_ENVS:
+            raise ValueError(f"no device implementation of env {cfg.env!r}; have {list(DEVICE_ENVS)}")
+        N, T, C, H = cfg.num_envs, cfg.rollout_len, cfg.buffer_slots, cfg.hidden
+        if N < 1 or T < 1 or C < T or C % T:
+            raise ValueError(f"buffer_slots ({C}) must be a positive multiple of rollout_len ({T})")
+        if cfg.batch_size < 1 or cfg.updates_per_epoch < 0 or cfg.target_update_every < 1:
+            raise ValueError("batch_size and target_update_every must be >= 1, updates_per_epoch >= 0")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("the DQN trainer runs the fused HIP actor: it needs a GPU device")
+        self.env_id = DEVICE_ENVS[cfg.env]
+        D, A, NS, max_steps = hip().env_dims(self.env_id)
+        self.D, self.A, self.NS = D, A, NS
+        self.max_steps = cfg.max_episode_steps or max_steps
+        # the online net: the seeded init of PGLearner's policy, with its fused-Adam state
+        g = torch.Generator().manual_seed(int(cfg.seed))
+        self.q = FlatNet(MLPSpec(D, H, A), cfg.q_lr, dev, g)
+        self.target = self.q.params.clone()
+        self.ring = ReplayRing.allocate(C, N, D, dev)
+        self.state = torch.zeros(N, NS, device=dev)
+        self.ep_len = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.ep_ret = torch.zeros(N, device=dev)
+        self.ep_stats = torch.zeros(dqn_rollout_grid(N), 8, device=dev)
+        B = cfg.batch_size
+        self.Xb = torch.zeros(B, D, device=dev)
+        self.act_b = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.y = torch.zeros(B, device=dev)
+        ns = grad_slabs(B, dev)
+        self.slab = torch.zeros(ns, self.q.P, device=dev)
+        self.loss = torch.zeros(ns, 8, device=dev)
+        self.env_seed, self.sample_seed, self.eval_seed = dqn_seeds(cfg.seed)
+        self.eval_step0 = 0
+        self.epoch = 0
+        self.env_steps = 0
+        self.updates = 0
+        self.cursor = 0         # next ring slot to write
+        self.slots_written = 0  # total, not capped at C
+        self.last_epsilon = float(cfg.eps_start)
+        self._first = True
+        self._has_loss = False
+
+    # ------------------------------------------------------------------ one epoch
+    def epsilon(self, epoch: Optional[int] = None) -> float:
+        """The exploration rate of epoch ``epoch`` (0-based; default: the next one)."""
+        return epsilon_at(self.cfg, self.epoch if epoch is None else int(epoch))
+
+    def rollout(self):
+        cfg = self.cfg
+        T = cfg.rollout_len
+        self.last_epsilon = self.epsilon()
+        rc = dqn_rollout(self.env_id, self.q.params, cfg.hidden, T, self.cursor, self.ring, self.state, self.ep_len,
+                         self.ep_ret, self.ep_stats, seed=self.env_seed, step0=self.epoch * T,
+                         epsilon=self.last_epsilon, reset_all=self._first, max_steps=self.max_steps)
+        if rc != 0:
+            raise RuntimeError(f"dqn_rollout refused slot {self.cursor} of {cfg.buffer_slots} (code {rc})")
+        self._first = False
+        self.cursor = (self.cursor + T) % cfg.buffer_slots
+        self.slots_written += T
+
+    def update(self):
+        """One gradient step on a freshly sampled batch; the target network follows on its schedule."""
+        cfg = self.cfg
+        filled = min(self.slots_written, cfg.buffer_slots) * cfg.num_envs
+        dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
+                    self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None))
+        mlp_grad(GradHead.Q_TD, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                 clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
+        self.q.apply(self.slab)
+        self.updates += 1
+        self._has_loss = True
+        if self.updates % cfg.target_update_every == 0:
+            self.target.copy_(self.q.params)
+
+    def train_epoch(self):
+        cfg = self.cfg
+        self.rollout()
+        self.epoch += 1
+        self.env_steps += cfg.rollout_len * cfg.num_envs
+        if self.slots_written * cfg.num_envs >= cfg.learning_starts:
+            for _ in range(cfg.updates_per_epoch):
+                self.update()
+
+    # ------------------------------------------------------------------ evaluation
+    def evaluate(self, episodes: int = 1, num_envs: Optional[int] = None, greedy: bool = True):
+        """Score the greedy policy of the online network: ``num_envs`` fresh envs x ``episodes`` whole
+        episodes (the evaluator's argmax over "logits" is the greedy Q-policy).  It reads the weights
+        and touches none of the training state or the ring; its Philox stream is its own."""
+        if not greedy:
+            raise ValueError("a DQN policy is evaluated greedily: softmax-of-Q is not this algorithm's policy")
+        from ..ops import evaluate_policy_op
+        from .evaluate import EvalResult
+
+        E, N = int(episodes), int(num_envs or self.cfg.num_envs)
+        step0 = self.eval_step0
+        ep_ret, ep_len, ep_code, _ = evaluate_policy_op(self.env_id, self.q.params, self.cfg.hidden, E, N, greedy=True,
+                                                        seed=self.eval_seed, step0=step0, max_steps=self.max_steps)
+        self.eval_step0 += E * self.max_steps
+        return EvalResult(ep_ret, ep_len, ep_code, True, self.eval_seed, step0)
+
+    # ------------------------------------------------------------------ metrics
+    def metrics(self) -> dict:
+        """Synchronising read of the last epoch's statistics."""
+        ep = self.ep_stats.sum(0).tolist()
+        mx = self.ep_stats[:, 3].max().item()
+        mn = self.ep_stats[:, 4].min().item()
+        out = {"Epoch": self.epoch}
+        out.update(episode_metrics(self.comm, ep[0], ep[1], ep[2], mx, mn, ep[5]))
+        nan = float("nan")
+        loss_q = q_vals = nan
+        if self._has_loss:
+            ls = self.loss.sum(0).tolist()
+            if ls[5] > 0:
+                loss_q, q_vals = ls[0] / ls[5], ls[4] / ls[5]
+        out.update(LossQ=loss_q, QVals=q_vals, Epsilon=self.last_epsilon, Updates=self.updates,
+                   EnvSteps=self.env_steps, WorldSize=1)
+        return out
+
+    def episode_sums(self) -> tuple:
+        """(finished episodes, sum of their returns) in the last epoch, from one device->host read."""
+        n, s = self.ep_stats[:, :2].sum(0).tolist()
+        return n, s
+
+    def average_ep_return(self) -> float:
+        n, s = self.episode_sums()
+        return s / n if n > 0 else float("nan")
+
+    # ------------------------------------------------------------------ state
+    def snapshot_tensors(self):
+        q = self.q
+        return [q.params, q.m, q.v, q.step, self.target, *self.ring, self.state, self.ep_len, self.ep_ret]
+
+    def counters(self) -> dict:
+        return {"epoch": self.epoch, "env_steps": self.env_steps, "updates": self.updates, "cursor": self.cursor,
+                "slots_written": self.slots_written, "_first": self._first}
+
+    def set_counters(self, c: dict):
+        self.epoch, self.env_steps, self.updates = int(c["epoch"]), int(c["env_steps"]), int(c["updates"])
+        self.cursor, self.slots_written, self._first = int(c["cursor"]), int(c["slots_written"]), bool(c["_first"])
+
+    def state_dict(self) -> dict:
+        """Everything a bit-exact resume needs.  ``learner/pi/params`` is the online network, the
+        layout ``launcher.evaluate_checkpoint_state`` reads."""
+        return {"cfg": self.cfg.to_dict(),
+                "learner": {"pi": self.q.state_dict(), "target": {"params": self.target.cpu()}},
+                "ring": {k: t.cpu() for k, t in self.ring._asdict().items()},
+                "epoch": self.epoch, "env_steps": self.env_steps, "updates": self.updates, "cursor": self.cursor,
+                "slots_written": self.slots_written, "eval_step0": self.eval_step0,
+                "env_state": self.state.cpu(), "ep_len": self.ep_len.cpu(), "ep_ret": self.ep_ret.cpu()}
+
+    def load_state_dict(self, sd: dict):
+        """Resume from ``state_dict()``.  The Philox keys derive from ``cfg.seed``: build the trainer with the
+        checkpoint's config (the launcher does, from the preset and its overrides) for a bit-exact resume."""
+        self.q.load_state_dict(sd["learner"]["pi"])
+        self.target.copy_(sd["learner"]["target"]["params"].to(self.device))
+        for k, t in self.ring._asdict().items():
+            src = sd["ring"][k]
+            if tuple(src.shape) != tuple(t.shape):
+                raise ValueError(f"checkpoint ring {k} is {tuple(src.shape)}, this trainer's {tuple(t.shape)}")
+            t.copy_(src.to(self.device))
+        self.set_counters({k: sd[k] for k in ("epoch", "env_steps", "updates", "cursor", "slots_written")} | {"_first": False})
+        self.eval_step0 = int(sd.get("eval_step0", 0))
+        self.state.copy_(sd["env_state"].to(self.device))
+        self.ep_len.copy_(sd["ep_len"].to(self.device))
+        self.ep_ret.copy_(sd["ep_ret"].to(self.device))

@@ -7,6 +7,7 @@ config's ``"mi355x": {"engine": ...}`` block, or ``hyperparams={"engine": ...}``
 the device engines behind the same object instead:
 
   vec            runtime/vec_trainer.py     fused on-device actor + HIP learner per GPU
+                 runtime/dqn_trainer.py     ("DQN": replay ring + TD updates, single rank, no policy served)
   host           runtime/host_trainer.py    C++ host env threads + HIP learner
   actor_learner  runtime/actor_learner.py   actor ranks -> learner group over RCCL
   pixel          runtime/pixel_trainer.py   Pong pixels, Nature-CNN A2C
@@ -41,7 +42,10 @@ ENV_BY_DIMS = {(4, 2): "CartPole-v1", (2, 3): "MountainCar-v0", (6, 3): "Acrobot
 # reference hyperparameter name -> trainer config field
 _PARAM_MAP = {"gamma": "gamma", "lam": "lam", "pi_lr": "pi_lr", "vf_lr": "vf_lr", "train_vf_iters": "train_vf_iters",
               "train_pi_iters": "train_pi_iters", "clip_ratio": "clip_ratio", "target_kl": "target_kl",
-              "ent_coef": "ent_coef", "seed": "seed", "num_minibatches": "num_minibatches", "with_vf_baseline": "with_baseline"}
+              "ent_coef": "ent_coef", "seed": "seed", "num_minibatches": "num_minibatches", "with_vf_baseline": "with_baseline",
+              # the reference's "DQN" block (runtime/dqn_trainer.py; the host owns the epsilon schedule, so
+              # epsilon_decay, a per-step factor in the reference, has no counterpart: eps_decay_epochs)
+              "q_lr": "q_lr", "batch_size": "batch_size", "epsilon": "eps_start", "epsilon_min": "eps_end"}
 # "mi355x" block name -> trainer config field
 _MI355X_MAP = {"envs_per_actor": "num_envs", "num_envs": "num_envs", "rollout_len": "rollout_len",
                "hidden": "hidden", "use_graphs": "use_graphs", "max_episode_steps": "max_episode_steps",
@@ -53,7 +57,7 @@ _MI355X_MAP = {"envs_per_actor": "num_envs", "num_envs": "num_envs", "rollout_le
 class EngineSpec:
     kind: str
     env: str
-    algo: str                     # reinforce | ppo | a2c
+    algo: str                     # reinforce | ppo | a2c | dqn
     world_size: int = 1
     trainer: Dict[str, Any] = field(default_factory=dict)
 
@@ -84,7 +88,10 @@ def resolve_engine(algorithm_name: str, obs_dim: int, act_dim: int, algo_params:
         raise ValueError(f"no built-in env with obs_dim={obs_dim}, act_dim={act_dim}; name one in the "
                          "'mi355x' config block (\"env\": ...) or hyperparams")
     world = int(hp.pop("world_size", mi355x.get("world_size", 1)) or 1)
-    algo = {"REINFORCE": "reinforce", "PPO": "ppo", "A2C": "a2c"}.get(algorithm_name.upper(), "reinforce")
+    algo = {"REINFORCE": "reinforce", "PPO": "ppo", "A2C": "a2c", "DQN": "dqn"}.get(algorithm_name.upper(), "reinforce")
+    if algo == "dqn" and (kind != "vec" or world != 1):
+        raise ValueError(f"DQN runs on the single-rank vec engine (engine=\"vec\", world_size 1), not "
+                         f"engine={kind!r} with world_size {world}")
     tr: Dict[str, Any] = {}
     for k, v in (algo_params or {}).items():
         if k in _PARAM_MAP and v is not None:
@@ -111,6 +118,10 @@ def _filter(cls, kw: Dict[str, Any]) -> Dict[str, Any]:
 
 def make_trainer(spec: EngineSpec, comm=None, device=None):
     kw = dict(spec.trainer)
+    if spec.kind == "vec" and str(kw.get("algo", spec.algo)).lower() == "dqn":
+        from .dqn_trainer import DQNConfig, DQNTrainer
+
+        return DQNTrainer(DQNConfig(**_filter(DQNConfig, kw)), comm, device)
     if spec.kind == "vec":
         from .vec_trainer import VecTrainer, VecTrainerConfig
 

@@ -65,6 +65,13 @@ PRESETS: Dict[str, Preset] = {
         "H2D/D2H pipeline, lag-1 rollout/update overlap)",
         "host", {"env": "CartPole-v1", "num_envs": 8192, "rollout_len": 64, "with_baseline": True,
                  "num_threads": 16, "gamma": 0.98, "lam": 0.97, "overlap": True}),
+    "cartpole-dqn": Preset(
+        "cartpole-dqn", "Double DQN CartPole-v1: epsilon-greedy fused actor -> device replay ring -> fused TD-target "
+        "and Q-head kernels (single rank; the vec kind with algo = dqn builds a DQNTrainer)",
+        "vec", {"env": "CartPole-v1", "algo": "dqn", "num_envs": 1024, "rollout_len": 4, "buffer_slots": 256,
+                "batch_size": 1024, "updates_per_epoch": 4, "gamma": 0.99, "q_lr": 5e-4, "eps_start": 1.0,
+                "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
+                "double_q": True, "huber_delta": 1.0}),
 }
 
 
@@ -79,6 +86,10 @@ def _free_port() -> int:
 def _make_trainer(preset: Preset, comm, device, overrides: Dict):
     kw = dict(preset.overrides)
     kw.update(overrides)
+    if preset.kind == "vec" and str(kw.get("algo", "")).lower() == "dqn":
+        from .dqn_trainer import DQNConfig, DQNTrainer
+
+        return DQNTrainer(DQNConfig(**_filter(DQNConfig, kw)), comm, device)
     if preset.kind == "vec":
         from .vec_trainer import VecTrainer, VecTrainerConfig
 
@@ -490,8 +501,8 @@ def spread_episodes(episodes: int, num_envs: int) -> tuple:
 
 def run_evaluate(checkpoint: str, episodes: int = 100, num_envs: int = 1024, stochastic: bool = False,
                  seed: int = 0, max_episode_steps: Optional[int] = None) -> Dict:
-    """Score the policy of a VecTrainer or pixel (PongSynth A2C) trainer checkpoint directory
-    (utils/checkpoint.py): the env, the model shape and the weights come from the checkpoint;
+    """Score the policy of a VecTrainer, DQNTrainer (greedy only) or pixel (PongSynth A2C) trainer
+    checkpoint directory (utils/checkpoint.py): the env, the model shape and the weights come from the checkpoint;
     ``episodes`` is the total, spread over at most ``num_envs`` envs (rounded up to whole episodes
     per env).  Returns the EvalResult fields plus what was evaluated (``hidden`` only for a
     VecTrainer checkpoint)."""
@@ -525,6 +536,9 @@ def evaluate_checkpoint_state(st, checkpoint: str = "<state>", episodes: int = 1
                              "trainer's") from None
     if episodes < 1 or num_envs < 1:
         raise ValueError("--episodes and --num-envs must be >= 1")
+    if not pixel and stochastic and str(cfg.get("algo", "")).lower() == "dqn":
+        raise ValueError("--stochastic does not apply to a DQN checkpoint: its policy is the greedy one "
+                         "(softmax-of-Q is not the algorithm's policy)")
     per_env, n = spread_episodes(int(episodes), int(num_envs))
     if pixel:
         return _evaluate_pixel_checkpoint(st, tr, per_env, n, stochastic, seed, max_episode_steps)
