@@ -2,36 +2,21 @@
 // and a kernel that samples the ring, gathers the batch and builds the TD targets from a second
 // (target) network.  The Q-learning gradient head lives in mlp_grad.hip (HEAD_Q_TD).
 //
-// The actor is the rollout kernels' step (rollout.hip): one 16-env tile per wave, the env replica
-// in registers, the Q-network on fp32 MFMA out of LDS, the same Philox coordinates for the env
-// noise (rnd.y of tag 0) and the resets (tag 1).  What differs:
-//   * the action: with rnd = philox((env, gstep, 0), key) the env explores iff u01(rnd.z) < epsilon
-//     and then takes min(A - 1, floor(u01(rnd.w) * A)); otherwise the lowest index among the maximal
-//     Q-values (evaluate.hip's greedy convention).  rnd.x, the on-policy kernels' action draw, is unused.
+// The actor is the shared step of actor_step.h, the one the rollout and evaluation kernels are built
+// from: one 16-env tile per wave, the env replica in registers (EnvSlot), the Q-network on fp32 MFMA
+// out of LDS (policy_forward), the step's Philox word (step_draw; .y is the env noise), the resets and
+// the episode statistics.  What this kernel adds:
+//   * the action: with rnd = step_draw(env, gstep) the env explores iff u01(rnd.z) < epsilon and then
+//     takes min(A - 1, floor(u01(rnd.w) * A)); otherwise the lowest index among the maximal Q-values
+//     (argmax_first, the evaluation kernels' greedy rule).  rnd.x, the on-policy action draw, is unused.
 //   * the output: T slots of a ring of C, obs / nobs / act / rew / done, where nobs is the post-step,
 //     pre-reset observation of EVERY step (the bootstrap input of the TD target).  A launch never
 //     wraps: C % T == 0, slot0 % T == 0 and slot0 + T <= C, the host advances the cursor.
 //
 // One form only, the tile-stride one (4 tiles per workgroup, one per wave): see docs/KERNELS.md.
-#include "api.h"
-#include "common.h"
-#include "heads.h"
-#include "envs.h"
+#include "actor_step.h"
 
 namespace rrl {
-
-// Lowest index among the maximal values (evaluate.hip, reference.greedy_from_logits).
-RRL_DEV int dqn_argmax_first(int A, const float (&q)[kMaxAct]) {
-  int pick = 0;
-  float best = q[0];
-#pragma unroll
-  for (int a = 1; a < kMaxAct; ++a)
-    if (a < A && q[a] > best) {
-      best = q[a];
-      pick = a;
-    }
-  return pick;
-}
 
 struct DqnRolloutArgs {
   const float* params;
@@ -56,137 +41,51 @@ template <class Env, int HT>
 __global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(DqnRolloutArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = 1;
-  using L = LdsNet<DT, HT>;
-  constexpr int H = L::H;
-  constexpr int D = Env::D, A = Env::A, NS = Env::NS;
+  constexpr int D = Env::D, A = Env::A;
   static_assert(D <= 16, "device envs use one input tile");
+  const TileCtx c = tile_ctx(p);
   stage_net<DT, HT>(lds, p.params, D, A, false);
   __syncthreads();
 
-  const int l = lane_id();
-  const int j = l & 15, g = l >> 4;
-  const int wave_in_block = threadIdx.x >> 6;
-  const int waves_per_block = blockDim.x >> 6;
-  const int wave = wave_in_block + blockIdx.x * waves_per_block;
-  const int total_waves = gridDim.x * waves_per_block;
-  const int ntiles = (p.N + kTileB - 1) / kTileB;
-  const uint2 key = make_uint2(p.seed_lo, p.seed_hi);
-  const uint64_t step0 = ((uint64_t)p.step_hi << 32) | p.step_lo;
-
-  float st_n = 0.f, st_sum = 0.f, st_sq = 0.f, st_max = -INFINITY, st_min = INFINITY, st_len = 0.f;
-
-  for (int tile = wave; tile < ntiles; tile += total_waves) {
-    const int env = tile * kTileB + j;
-    const bool valid = env < p.N;
-    const int envc = valid ? env : p.N - 1;
-    float s[NS];
-    int len;
-    float ret;
-    if (p.reset_all) {
-      const uint4 r = philox4x32(make_uint4((uint32_t)envc, (uint32_t)step0, (uint32_t)(step0 >> 32), 1u), key);
-      Env::reset(s, r);
-      len = 0;
-      ret = 0.f;
-    } else {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) s[k] = p.state[(size_t)envc * NS + k];
-      len = p.ep_len[envc];
-      ret = p.ep_ret[envc];
-    }
+  EpStats st;
+  for (int tile = c.first; tile < c.ntiles; tile += c.stride) {
+    EnvSlot<Env> e(c, tile, p.N);
+    e.load_or_reset(c, p.reset_all, p.state, p.ep_len, p.ep_ret);
 
     for (int t = 0; t < p.T; ++t) {
-      const uint64_t gstep = step0 + (uint64_t)t;
-      const size_t base = (size_t)t * p.N + env;
-      floatx4 x[1];
-      x[0] = zero4();
-#pragma unroll
-      for (int f = 0; f < D; ++f) {
-        const float o = Env::obs(s, f);
-        if ((f & 3) == g) x[0][f >> 2] = o;
-      }
-      if (valid) {
-#pragma unroll
-        for (int f = 0; f < D; ++f)
-          if ((f & 3) == g) p.obs[base * D + f] = x[0][f >> 2];
-      }
-      floatx4 h1[HT], h2[HT];
-      dense_fwd<DT, HT, true>(lds + L::W1, L::S1, lds + L::B1, x, h1, (D + 3) >> 2);
-      dense_fwd<HT, HT, true>(lds + L::W2, L::S2, lds + L::B2, h1, h2);
+      const uint64_t gstep = c.step0 + (uint64_t)t;
+      const size_t base = (size_t)t * p.N + e.env;
+      floatx4 x[DT];
+      pack_obs<Env, DT>(e.s, c.g, x);
+      if (e.valid) store_obs_row<D, DT>(p.obs + base * D, c.g, x);
       float q[kMaxAct];
-      policy_logits<HT>(lds + L::W3, lds + L::B3, A, H, h2, q);
-      const uint4 rnd = philox4x32(make_uint4((uint32_t)envc, (uint32_t)gstep, (uint32_t)(gstep >> 32), 0u), key);
+      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), A, q);
+      const uint4 rnd = step_draw(e.envc, gstep, c.key);
       const bool explore = u01(rnd.z) < p.epsilon;
       const int a_rand = min(A - 1, (int)floorf(u01(rnd.w) * (float)A));
-      const int a = explore ? a_rand : dqn_argmax_first(A, q);
+      const int a = explore ? a_rand : argmax_first(A, q);
 
       bool term;
-      const float r = Env::step(s, a, term, u01(rnd.y));
-      len += 1;
-      ret += r;
-      const bool trunc = len >= p.max_steps;
+      const float r = Env::step(e.s, a, term, u01(rnd.y));
+      e.advance(r);
+      const bool trunc = e.len >= p.max_steps;
       const bool done = term || trunc;
-      if (valid) {
-#pragma unroll
-        for (int f = 0; f < D; ++f)
-          if ((f & 3) == g) p.nobs[base * D + f] = Env::obs(s, f);
-        if (g == 0) {
+      if (e.valid) {
+        store_obs<Env>(p.nobs + base * D, c.g, e.s);
+        if (c.g == 0) {
           p.act[base] = a;
           p.rew[base] = r;
           p.done[base] = term ? 1.f : (trunc ? 2.f : 0.f);
         }
       }
       if (done) {
-        if (valid && g == 0) {
-          st_n += 1.f;
-          st_sum += ret;
-          st_sq += ret * ret;
-          st_max = fmaxf(st_max, ret);
-          st_min = fminf(st_min, ret);
-          st_len += (float)len;
-        }
-        const uint4 rr = philox4x32(make_uint4((uint32_t)envc, (uint32_t)gstep, (uint32_t)(gstep >> 32), 1u), key);
-        Env::reset(s, rr);
-        len = 0;
-        ret = 0.f;
+        if (e.valid && c.g == 0) st.add(e.ret, e.len);
+        e.end_episode(c, gstep);
       }
     }
-    // persistent env state
-    if (valid && g == 0) {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) p.state[(size_t)env * NS + k] = s[k];
-      p.ep_len[env] = len;
-      p.ep_ret[env] = ret;
-    }
+    if (e.valid && c.g == 0) e.write_back(p.state, p.ep_len, p.ep_ret);  // persistent env state
   }
-
-  // workgroup reduction of episode statistics
-  __syncthreads();
-  float* red = lds;  // weights no longer needed
-  float v0 = wave_sum(st_n), v1 = wave_sum(st_sum), v2 = wave_sum(st_sq), v5 = wave_sum(st_len);
-  float v3 = st_max, v4 = st_min;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    v3 = fmaxf(v3, __shfl_xor(v3, o, 64));
-    v4 = fminf(v4, __shfl_xor(v4, o, 64));
-  }
-  if (l == 0) {
-    red[wave_in_block * 8 + 0] = v0;
-    red[wave_in_block * 8 + 1] = v1;
-    red[wave_in_block * 8 + 2] = v2;
-    red[wave_in_block * 8 + 3] = v3;
-    red[wave_in_block * 8 + 4] = v4;
-    red[wave_in_block * 8 + 5] = v5;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int k = threadIdx.x;
-    float v = red[k];
-    for (int w = 1; w < waves_per_block; ++w) {
-      const float u = red[w * 8 + k];
-      v = (k == 3) ? fmaxf(v, u) : (k == 4) ? fminf(v, u) : v + u;
-    }
-    p.ep_stats[blockIdx.x * 8 + k] = v;
-  }
+  st.reduce_block(c, lds, p.ep_stats);  // the weights are no longer needed
 }
 
 // ------------------------------------------------------------------ sample + gather + TD target
@@ -225,7 +124,6 @@ RRL_DEV uint32_t dqn_sample_row(int b, const DqnTargetArgs& p) {
 template <int HT>
 RRL_DEV void dqn_q_values(const float* __restrict__ lds, const float* __restrict__ nobs, size_t r, bool ok, int D,
                           int A, float (&q)[kMaxAct]) {
-  using L = LdsNet<1, HT>;
   const int g = lane_id() >> 4;
   floatx4 x[1];
   const float* row = nobs + r * (size_t)D;
@@ -234,10 +132,7 @@ RRL_DEV void dqn_q_values(const float* __restrict__ lds, const float* __restrict
     const int f = 4 * k + g;
     x[0][k] = (ok && f < D) ? row[f] : 0.f;
   }
-  floatx4 h1[HT], h2[HT];
-  dense_fwd<1, HT, true>(lds + L::W1, L::S1, lds + L::B1, x, h1, (D + 3) >> 2);
-  dense_fwd<HT, HT, true>(lds + L::W2, L::S2, lds + L::B2, h1, h2);
-  policy_logits<HT>(lds + L::W3, lds + L::B3, A, L::H, h2, q);
+  policy_forward<1, HT>(lds, x, (D + 3) >> 2, A, q);
 }
 
 template <int HT>
@@ -256,7 +151,7 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
       const size_t r = ok ? dqn_sample_row(b, p) : 0;
       float q[kMaxAct];
       dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, p.A, q);
-      if (ok && g == 0) p.y[b] = __int_as_float(dqn_argmax_first(p.A, q));
+      if (ok && g == 0) p.y[b] = __int_as_float(argmax_first(p.A, q));
     }
     __syncthreads();  // every wave is done with the online image
   }
@@ -271,7 +166,7 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
     if (ok) {
       for (int f = g; f < p.D; f += 4) p.Xb[(size_t)b * p.D + f] = p.obs[r * p.D + f];
       if (g == 0) {
-        const int astar = p.double_q ? __float_as_int(p.y[b]) : dqn_argmax_first(p.A, q);
+        const int astar = p.double_q ? __float_as_int(p.y[b]) : argmax_first(p.A, q);
         const float boot = (p.done[r] == 1.f) ? 0.f : 1.f;
         p.y[b] = p.rew[r] + p.gamma * boot * pick_logit(p.A, q, astar);
         p.act_b[b] = p.act[r];
@@ -286,23 +181,12 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
 using namespace rrl;
 
 // 4 tiles per workgroup, one per wave; at most two workgroups per CU, beyond that the waves stride.
-extern "C" int rrl_dqn_rollout_grid(int N, int num_cu) {
-  const int tiles = (N + kTileB - 1) / kTileB;
-  int grid = (tiles + 3) / 4;
-  const int cap = 2 * (num_cu > 0 ? num_cu : 256);
-  if (grid > cap) grid = cap;
-  return grid < 1 ? 1 : grid;
-}
+extern "C" int rrl_dqn_rollout_grid(int N, int num_cu) { return tile_stride_grid(N, num_cu); }
 
 template <class Env, int HT>
 static int launch_dqn_rollout(DqnRolloutArgs a, int slot0, int grid, hipStream_t s) {
   using L = LdsNet<1, HT>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dqn_rollout_kernel<Env, HT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              163840);
-    attr = true;
-  }
+  raise_lds_limit<dqn_rollout_kernel<Env, HT>>();
   const size_t off = (size_t)slot0 * a.N;
   a.obs += off * Env::D;
   a.nobs += off * Env::D;
@@ -325,34 +209,16 @@ extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H
                    (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step0, (uint32_t)(step0 >> 32), epsilon,
                    reset_all, max_steps};
   const int grid = rrl_dqn_rollout_grid(N, num_cu);
-  hipStream_t s = (hipStream_t)stream;
-  if (H == 128) {
-    switch (env) {
-      case ENV_CARTPOLE: return launch_dqn_rollout<CartPoleEnv, 8>(a, slot0, grid, s);
-      case ENV_MOUNTAINCAR: return launch_dqn_rollout<MountainCarEnv, 8>(a, slot0, grid, s);
-      case ENV_ACROBOT: return launch_dqn_rollout<AcrobotEnv, 8>(a, slot0, grid, s);
-      case ENV_LUNARLANDER: return launch_dqn_rollout<LunarLanderSynthEnv, 8>(a, slot0, grid, s);
-    }
-  } else if (H == 64) {
-    switch (env) {
-      case ENV_CARTPOLE: return launch_dqn_rollout<CartPoleEnv, 4>(a, slot0, grid, s);
-      case ENV_MOUNTAINCAR: return launch_dqn_rollout<MountainCarEnv, 4>(a, slot0, grid, s);
-      case ENV_ACROBOT: return launch_dqn_rollout<AcrobotEnv, 4>(a, slot0, grid, s);
-      case ENV_LUNARLANDER: return launch_dqn_rollout<LunarLanderSynthEnv, 4>(a, slot0, grid, s);
-    }
-  }
-  return -3;
+  return dispatch_env_h(env, H, [&](auto k) {
+    using K = decltype(k);
+    return launch_dqn_rollout<typename K::Env, K::HT>(a, slot0, grid, (hipStream_t)stream);
+  });
 }
 
 template <int HT>
 static int launch_dqn_targets(const DqnTargetArgs& a, int grid, hipStream_t s) {
   using L = LdsNet<1, HT>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dqn_targets_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              163840);
-    attr = true;
-  }
+  raise_lds_limit<dqn_targets_kernel<HT>>();
   const size_t bytes = (size_t)L::floats(a.A) * sizeof(float);
   hipLaunchKernelGGL((dqn_targets_kernel<HT>), dim3(grid), dim3(256), bytes, s, a);
   return (int)hipGetLastError();

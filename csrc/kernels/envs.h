@@ -12,6 +12,7 @@ namespace rrl {
 struct CartPoleEnv {
   static constexpr int D = 4, A = 2, NS = 4;
   static constexpr int kMaxSteps = 500;
+  static constexpr bool kOwnDraws = false;
   RRL_DEV static void reset(float (&s)[NS], uint4 r) {
     s[0] = -0.05f + 0.1f * u01(r.x);
     s[1] = -0.05f + 0.1f * u01(r.y);
@@ -44,6 +45,7 @@ struct CartPoleEnv {
 struct MountainCarEnv {
   static constexpr int D = 2, A = 3, NS = 2;
   static constexpr int kMaxSteps = 200;
+  static constexpr bool kOwnDraws = false;
   RRL_DEV static void reset(float (&s)[NS], uint4 r) {
     s[0] = -0.6f + 0.2f * u01(r.x);
     s[1] = 0.f;
@@ -68,6 +70,7 @@ struct MountainCarEnv {
 struct AcrobotEnv {
   static constexpr int D = 6, A = 3, NS = 4;
   static constexpr int kMaxSteps = 500;
+  static constexpr bool kOwnDraws = false;
   RRL_DEV static void reset(float (&s)[NS], uint4 r) {
     s[0] = -0.1f + 0.2f * u01(r.x);
     s[1] = -0.1f + 0.2f * u01(r.y);
@@ -134,10 +137,15 @@ struct AcrobotEnv {
 struct LunarLanderSynthEnv {
   static constexpr int D = 8, A = 4, NS = 7;  // x y vx vy ang angv prev_shaping
   static constexpr int kMaxSteps = 1000;
+  static constexpr bool kOwnDraws = false;
+  // -100 |pos| - 100 |vel| - 100 |angle| + legs, with every fused multiply-add written out: left
+  // to contraction, the compiler fused the one product of a sum of squares at one call site and
+  // the other at the next (the two resets of one kernel differed, and so did the rollout and the
+  // evaluation kernels), so that equal states did not give equal shaping bits.
   RRL_DEV static float shaping(const float (&s)[NS]) {
     const float legs = s[1] < 0.05f ? 20.f : 0.f;
-    return -100.f * sqrtf(s[0] * s[0] + s[1] * s[1]) - 100.f * sqrtf(s[2] * s[2] + s[3] * s[3]) -
-           100.f * fabsf(s[4]) + legs;
+    const float pos = sqrtf(fmaf(s[0], s[0], s[1] * s[1])), vel = sqrtf(fmaf(s[2], s[2], s[3] * s[3]));
+    return fmaf(-100.f, fabsf(s[4]), fmaf(-100.f, pos, -100.f * vel)) + legs;
   }
   RRL_DEV static void reset(float (&s)[NS], uint4 r) {
     s[0] = -0.3f + 0.6f * u01(r.x);
@@ -197,6 +205,8 @@ struct HalfCheetahSynthEnv {
   static constexpr int D = 17, A = 6, NS = 17;
   static constexpr int kMaxSteps = 1000;
   static constexpr int kConsts = 17 * 17 + 17 * 6;
+  static constexpr bool kOwnDraws = true;  // reset and step draw their own Philox words
+  RRL_DEV static float obs(const float (&s)[NS], int f) { return s[f]; }
   RRL_DEV static void reset(float (&s)[NS], uint2 key, uint32_t env, uint64_t step) {
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
@@ -236,5 +246,18 @@ struct HalfCheetahSynthEnv {
     return s[8] - 0.1f * ctrl;
   }
 };
+
+// The reset of every actor kernel, at the first step of a launch (step = step0) or after the
+// episode that ended at `step`.  The classic envs take one Philox word at (env, step, tag 1).
+// HalfCheetahSynth draws its own words from (key, env, step), and after an episode from counter
+// step + 2^32.
+template <class Env>
+RRL_DEV void env_reset(float (&s)[Env::NS], uint2 key, uint32_t env, uint64_t step, bool after_episode) {
+  if constexpr (Env::kOwnDraws) {
+    Env::reset(s, key, env, after_episode ? step + 0x100000000ull : step);
+  } else {
+    Env::reset(s, philox4x32(make_uint4(env, (uint32_t)step, (uint32_t)(step >> 32), 1u), key));
+  }
+}
 
 }  // namespace rrl

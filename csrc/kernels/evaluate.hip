@@ -1,10 +1,12 @@
 // Fused policy evaluation: every one of N vectorised envs runs E complete episodes under fixed
 // weights in ONE launch, and only the O(E * N) episode results reach HBM.
 //
-// The step is the rollout kernels' (rollout.hip): one 16-env tile per wave, the env replica in
-// registers, the policy MLP on fp32 MFMA out of LDS, the same Philox coordinates for the first
-// reset (env, step0, tag 1), the action draw and env noise of step t (counter step0 + t) and the
-// reset that follows a finished episode.  What differs:
+// The step is the shared one of actor_step.h, the code the rollout kernels run: one 16-env tile
+// per wave, the env replica in registers (EnvSlot), the policy MLP on fp32 MFMA out of LDS
+// (policy_forward), and, because EnvSlot, step_draw and gauss_noise own the Philox coordinates,
+// the rollout's first reset, its action draw and env noise of step t (counter step0 + t) and its
+// reset after a finished episode.  tests/test_actor_step_gpu.py holds a sampled trace to the
+// rollout bit for bit.  What this file adds:
 //   * greedy = 1 takes the lowest index among the maximal logits (a = mu for the Gaussian
 //     policy); greedy = 0 draws exactly what the rollout kernels draw.  Env noise is drawn as in
 //     training in both modes: greedy removes policy noise, not env noise.
@@ -15,10 +17,7 @@
 //   * outputs are ep_ret / ep_len / ep_code [E][N] (the fp32 running sum ret += r, the length,
 //     1 terminal / 2 time limit) and, optionally, a trace of the first Tc steps in the rollout
 //     buffers' layout.  No reductions: statistics are torch reductions over the [E][N] tensors.
-#include "api.h"
-#include "common.h"
-#include "heads.h"
-#include "envs.h"
+#include "actor_step.h"
 
 namespace rrl {
 
@@ -39,78 +38,46 @@ struct EvalArgs {
   int max_steps;
 };
 
-// Lowest index among the maximal logits.
-RRL_DEV int argmax_first(int A, const float (&logits)[kMaxAct]) {
-  int pick = 0;
-  float best = logits[0];
-#pragma unroll
-  for (int a = 1; a < kMaxAct; ++a)
-    if (a < A && logits[a] > best) {
-      best = logits[a];
-      pick = a;
-    }
-  return pick;
+// One lane of an env that finished episode `ep` records it.
+template <class Env>
+RRL_DEV void store_episode(const EvalArgs& p, const EnvSlot<Env>& e, int ep, int code) {
+  const size_t o = (size_t)ep * p.N + e.env;
+  p.ep_ret[o] = e.ret;
+  p.ep_len[o] = e.len;
+  p.ep_code[o] = code;
 }
 
 template <class Env, int HT>
 __global__ __launch_bounds__(256, 2) void evaluate_kernel(EvalArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = 1;
-  using L = LdsNet<DT, HT>;
-  constexpr int H = L::H;
-  constexpr int D = Env::D, A = Env::A, NS = Env::NS;
+  constexpr int D = Env::D, A = Env::A;
   static_assert(D <= 16, "device envs use one input tile");
+  const TileCtx c = tile_ctx(p);
   stage_net<DT, HT>(lds, p.params, D, A, false);
   __syncthreads();
 
-  const int l = lane_id();
-  const int j = l & 15, g = l >> 4;
-  const int waves_per_block = blockDim.x >> 6;
-  const int wave = (threadIdx.x >> 6) + blockIdx.x * waves_per_block;
-  const int total_waves = gridDim.x * waves_per_block;
-  const int ntiles = (p.N + kTileB - 1) / kTileB;
-  const uint2 key = make_uint2(p.seed_lo, p.seed_hi);
-  const uint64_t step0 = ((uint64_t)p.step_hi << 32) | p.step_lo;
   const int tmax = p.E * p.max_steps;  // < 2^31: checked by the host entry point
   const bool trace = p.tr_obs != nullptr;
   int* tr_act = static_cast<int*>(p.tr_act);
 
-  for (int tile = wave; tile < ntiles; tile += total_waves) {
-    const int env = tile * kTileB + j;
-    const bool valid = env < p.N;
-    const int envc = valid ? env : p.N - 1;
-    float s[NS];
-    {
-      const uint4 r = philox4x32(make_uint4((uint32_t)envc, (uint32_t)step0, (uint32_t)(step0 >> 32), 1u), key);
-      Env::reset(s, r);
-    }
-    int len = 0, ep = 0;
-    float ret = 0.f;
+  for (int tile = c.first; tile < c.ntiles; tile += c.stride) {
+    EnvSlot<Env> e(c, tile, p.N);
+    e.reset(c, c.step0, false);
+    int ep = 0;
 
     for (int t = 0; t < tmax; ++t) {
-      const bool active = valid && ep < p.E;
+      const bool active = e.valid && ep < p.E;
       if (__ballot(active) == 0) break;  // wave-uniform: every lane of the tile has its E episodes
-      const uint64_t gstep = step0 + (uint64_t)t;
-      const size_t base = (size_t)t * p.N + env;
+      const uint64_t gstep = c.step0 + (uint64_t)t;
+      const size_t base = (size_t)t * p.N + e.env;
       const bool tr = trace && active && t < p.Tc;
-      floatx4 x[1];
-      x[0] = zero4();
-#pragma unroll
-      for (int f = 0; f < D; ++f) {
-        const float o = Env::obs(s, f);
-        if ((f & 3) == g) x[0][f >> 2] = o;
-      }
-      if (tr) {
-#pragma unroll
-        for (int f = 0; f < D; ++f)
-          if ((f & 3) == g) p.tr_obs[base * D + f] = x[0][f >> 2];
-      }
-      floatx4 h1[HT], h2[HT];
-      dense_fwd<DT, HT, true>(lds + L::W1, L::S1, lds + L::B1, x, h1, (D + 3) >> 2);
-      dense_fwd<HT, HT, true>(lds + L::W2, L::S2, lds + L::B2, h1, h2);
+      floatx4 x[DT];
+      pack_obs<Env, DT>(e.s, c.g, x);
+      if (tr) store_obs_row<D, DT>(p.tr_obs + base * D, c.g, x);
       float logits[kMaxAct];
-      policy_logits<HT>(lds + L::W3, lds + L::B3, A, H, h2, logits);
-      const uint4 rnd = philox4x32(make_uint4((uint32_t)envc, (uint32_t)gstep, (uint32_t)(gstep >> 32), 0u), key);
+      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), A, logits);
+      const uint4 rnd = step_draw(e.envc, gstep, c.key);
       int a;
       if (p.greedy) {
         a = argmax_first(A, logits);
@@ -121,27 +88,18 @@ __global__ __launch_bounds__(256, 2) void evaluate_kernel(EvalArgs p) {
 
       if (active) {
         bool term;
-        const float r = Env::step(s, a, term, u01(rnd.y));
-        len += 1;
-        ret += r;
-        const bool done = term || len >= p.max_steps;
-        if (tr && g == 0) {
+        const float r = Env::step(e.s, a, term, u01(rnd.y));
+        e.advance(r);
+        const bool done = term || e.len >= p.max_steps;
+        if (tr && c.g == 0) {
           tr_act[base] = a;
           p.tr_rew[base] = r;
           p.tr_done[base] = done ? 1.f : 0.f;
         }
         if (done) {
-          if (g == 0) {
-            const size_t o = (size_t)ep * p.N + env;
-            p.ep_ret[o] = ret;
-            p.ep_len[o] = len;
-            p.ep_code[o] = term ? 1 : 2;
-          }
-          const uint4 rr = philox4x32(make_uint4((uint32_t)envc, (uint32_t)gstep, (uint32_t)(gstep >> 32), 1u), key);
-          Env::reset(s, rr);
+          if (c.g == 0) store_episode(p, e, ep, term ? 1 : 2);
+          e.end_episode(c, gstep);
           ep += 1;
-          len = 0;
-          ret = 0.f;
         }
       }
     }
@@ -149,111 +107,63 @@ __global__ __launch_bounds__(256, 2) void evaluate_kernel(EvalArgs p) {
 }
 
 // Diagonal-Gaussian policy on the continuous device env: a = mu + exp(log_std) * n with the
-// rollout kernel's Box-Muller draws (tags 0 and 2), or a = mu when greedy.
+// rollout kernel's Box-Muller draws (gauss_noise), or a = mu when greedy.
 template <class Env, int HT>
 __global__ __launch_bounds__(256, 2) void evaluate_cont_kernel(EvalArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = (Env::D + 15) / 16;
   using L = LdsNet<DT, HT>;
-  constexpr int H = L::H;
-  constexpr int D = Env::D, A = Env::A, NS = Env::NS;
-  static_assert(NS == D, "continuous device envs observe their full state");
-  const int net_floats = (L::floats(A) + 3) & ~3;
-  float* cst = lds + net_floats;
+  constexpr int D = Env::D, A = Env::A;
+  float* cst = lds + ((L::floats(A) + 3) & ~3);
+  const TileCtx c = tile_ctx(p);
   stage_net<DT, HT>(lds, p.params, D, A, true);
   for (int i = threadIdx.x; i < Env::kConsts; i += blockDim.x) cst[i] = p.env_consts[i];
   __syncthreads();
 
-  const int l = lane_id();
-  const int j = l & 15, g = l >> 4;
-  const int waves_per_block = blockDim.x >> 6;
-  const int wave = (threadIdx.x >> 6) + blockIdx.x * waves_per_block;
-  const int total_waves = gridDim.x * waves_per_block;
-  const int ntiles = (p.N + kTileB - 1) / kTileB;
-  const uint2 key = make_uint2(p.seed_lo, p.seed_hi);
-  const uint64_t step0 = ((uint64_t)p.step_hi << 32) | p.step_lo;
-  const int kr1 = input_kr_last(D, DT);
   const int tmax = p.E * p.max_steps;
   const bool trace = p.tr_obs != nullptr;
   float* tr_act = static_cast<float*>(p.tr_act);
 
-  for (int tile = wave; tile < ntiles; tile += total_waves) {
-    const int env = tile * kTileB + j;
-    const bool valid = env < p.N;
-    const int envc = valid ? env : p.N - 1;
-    float s[NS];
-    Env::reset(s, key, (uint32_t)envc, step0);
-    int len = 0, ep = 0;
-    float ret = 0.f;
+  for (int tile = c.first; tile < c.ntiles; tile += c.stride) {
+    EnvSlot<Env> e(c, tile, p.N);
+    e.reset(c, c.step0, false);
+    int ep = 0;
 
     for (int t = 0; t < tmax; ++t) {
-      const bool active = valid && ep < p.E;
+      const bool active = e.valid && ep < p.E;
       if (__ballot(active) == 0) break;
-      const uint64_t gstep = step0 + (uint64_t)t;
-      const size_t base = (size_t)t * p.N + env;
+      const uint64_t gstep = c.step0 + (uint64_t)t;
+      const size_t base = (size_t)t * p.N + e.env;
       const bool tr = trace && active && t < p.Tc;
       floatx4 x[DT];
-#pragma unroll
-      for (int q = 0; q < DT; ++q) x[q] = zero4();
-#pragma unroll
-      for (int f = 0; f < D; ++f)
-        if ((f & 3) == g) x[f >> 4][(f >> 2) & 3] = s[f];
-      if (tr) {
-#pragma unroll
-        for (int f = 0; f < D; ++f)
-          if ((f & 3) == g) p.tr_obs[base * D + f] = s[f];
-      }
-      floatx4 h1[HT], h2[HT];
-      dense_fwd<DT, HT, true>(lds + L::W1, L::S1, lds + L::B1, x, h1, kr1);
-      dense_fwd<HT, HT, true>(lds + L::W2, L::S2, lds + L::B2, h1, h2);
+      pack_obs<Env, DT>(e.s, c.g, x);
+      if (tr) store_obs_row<D, DT>(p.tr_obs + base * D, c.g, x);
       float mu[kMaxAct];
-      policy_logits<HT>(lds + L::W3, lds + L::B3, A, H, h2, mu);
+      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), A, mu);
       float act[kMaxAct];
       if (p.greedy) {
 #pragma unroll
         for (int a = 0; a < kMaxAct; ++a) act[a] = a < A ? mu[a] : 0.f;
       } else {
-        const uint4 r0 = philox4x32(make_uint4((uint32_t)envc, (uint32_t)gstep, (uint32_t)(gstep >> 32), 0u), key);
-        const uint4 r1 = philox4x32(make_uint4((uint32_t)envc, (uint32_t)gstep, (uint32_t)(gstep >> 32), 2u), key);
-        const float uu[8] = {u01(r0.x), u01(r0.y), u01(r0.z), u01(r0.w), u01(r1.x), u01(r1.y), u01(r1.z), u01(r1.w)};
         float nrm[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float rad = sqrtf(-2.f * __logf(1.f - uu[2 * q]));
-          float sn, cs;
-          __sincosf(6.283185307179586f * uu[2 * q + 1], &sn, &cs);
-          nrm[2 * q] = rad * cs;
-          nrm[2 * q + 1] = rad * sn;
-        }
-#pragma unroll
-        for (int a = 0; a < kMaxAct; ++a) {
-          act[a] = 0.f;
-          if (a < A) act[a] = mu[a] + __expf(lds[L::LOGSTD + a]) * nrm[a < 8 ? a : 0];
-        }
+        gauss_noise(e.envc, gstep, c.key, nrm);
+        gauss_act(A, mu, lds + L::LOGSTD, nrm, act);
       }
 
       if (active) {
-        const float r = Env::step(s, act, cst, key, (uint32_t)envc, gstep);
-        len += 1;
-        ret += r;
-        const bool done = len >= p.max_steps;  // this env only truncates (time limit)
-        if (tr && g == 0) {
+        const float r = Env::step(e.s, act, cst, c.key, (uint32_t)e.envc, gstep);
+        e.advance(r);
+        const bool done = e.len >= p.max_steps;  // this env only truncates (time limit)
+        if (tr && c.g == 0) {
 #pragma unroll
           for (int a = 0; a < A; ++a) tr_act[base * A + a] = act[a];
           p.tr_rew[base] = r;
           p.tr_done[base] = done ? 1.f : 0.f;
         }
         if (done) {
-          if (g == 0) {
-            const size_t o = (size_t)ep * p.N + env;
-            p.ep_ret[o] = ret;
-            p.ep_len[o] = len;
-            p.ep_code[o] = 2;
-          }
-          Env::reset(s, key, (uint32_t)envc, gstep + 0x100000000ull);
+          if (c.g == 0) store_episode(p, e, ep, 2);
+          e.end_episode(c, gstep);
           ep += 1;
-          len = 0;
-          ret = 0.f;
         }
       }
     }
@@ -272,12 +182,9 @@ namespace {
 // the waves stride over the tiles like rollout_kernel's.
 void eval_geometry(int N, int num_cu, int* grid, int* block) {
   const int tiles = (N + kTileB - 1) / kTileB;
-  const int cap = 2 * (num_cu > 0 ? num_cu : 256);
   int wpb = 1;
-  while (wpb < 4 && (tiles + wpb - 1) / wpb > cap) wpb *= 2;
-  int g = (tiles + wpb - 1) / wpb;
-  if (g > cap) g = cap;
-  *grid = g < 1 ? 1 : g;
+  while (wpb < 4 && (tiles + wpb - 1) / wpb > grid_cap(num_cu)) wpb *= 2;
+  *grid = tile_stride_grid(N, num_cu, wpb);
   *block = 64 * wpb;
 }
 
@@ -295,12 +202,7 @@ int eval_args_bad(int N, int E, int Tc, int max_steps, const void* tr_obs, const
 template <class Env, int HT>
 int launch_evaluate(const EvalArgs& a, int num_cu, hipStream_t s) {
   using L = LdsNet<1, HT>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)evaluate_kernel<Env, HT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              163840);
-    attr = true;
-  }
+  raise_lds_limit<evaluate_kernel<Env, HT>>();
   int grid, block;
   eval_geometry(a.N, num_cu, &grid, &block);
   const size_t bytes = (size_t)L::floats(Env::A) * sizeof(float);
@@ -312,12 +214,7 @@ template <class Env, int HT>
 int launch_evaluate_cont(const EvalArgs& a, int num_cu, hipStream_t s) {
   constexpr int DT = (Env::D + 15) / 16;
   using L = LdsNet<DT, HT>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)evaluate_cont_kernel<Env, HT>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    attr = true;
-  }
+  raise_lds_limit<evaluate_cont_kernel<Env, HT>>();
   int grid, block;
   eval_geometry(a.N, num_cu, &grid, &block);
   const size_t bytes = ((size_t)((L::floats(Env::A) + 3) & ~3) + Env::kConsts) * sizeof(float);
@@ -334,23 +231,10 @@ extern "C" int rrl_evaluate(int env, const float* params, int N, int E, int Tc, 
   EvalArgs a{params, nullptr, N, E, Tc, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done,
              (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step0, (uint32_t)(step0 >> 32), greedy ? 1 : 0,
              max_steps};
-  hipStream_t s = (hipStream_t)stream;
-  if (H == 128) {
-    switch (env) {
-      case ENV_CARTPOLE: return launch_evaluate<CartPoleEnv, 8>(a, num_cu, s);
-      case ENV_MOUNTAINCAR: return launch_evaluate<MountainCarEnv, 8>(a, num_cu, s);
-      case ENV_ACROBOT: return launch_evaluate<AcrobotEnv, 8>(a, num_cu, s);
-      case ENV_LUNARLANDER: return launch_evaluate<LunarLanderSynthEnv, 8>(a, num_cu, s);
-    }
-  } else if (H == 64) {
-    switch (env) {
-      case ENV_CARTPOLE: return launch_evaluate<CartPoleEnv, 4>(a, num_cu, s);
-      case ENV_MOUNTAINCAR: return launch_evaluate<MountainCarEnv, 4>(a, num_cu, s);
-      case ENV_ACROBOT: return launch_evaluate<AcrobotEnv, 4>(a, num_cu, s);
-      case ENV_LUNARLANDER: return launch_evaluate<LunarLanderSynthEnv, 4>(a, num_cu, s);
-    }
-  }
-  return -3;
+  return dispatch_env_h(env, H, [&](auto k) {
+    using K = decltype(k);
+    return launch_evaluate<typename K::Env, K::HT>(a, num_cu, (hipStream_t)stream);
+  });
 }
 
 extern "C" int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int N, int E, int Tc, int H,

@@ -71,6 +71,19 @@ RRL_DEV int cat_sample(int A, const float (&logits)[kMaxAct], float lse, float u
   return pick < 0 ? 0 : pick;
 }
 
+// Lowest index among the maximal values: the greedy action (reference.greedy_from_logits).
+RRL_DEV int argmax_first(int A, const float (&logits)[kMaxAct]) {
+  int pick = 0;
+  float best = logits[0];
+#pragma unroll
+  for (int a = 1; a < kMaxAct; ++a)
+    if (a < A && logits[a] > best) {
+      best = logits[a];
+      pick = a;
+    }
+  return pick;
+}
+
 RRL_DEV float pick_logit(int A, const float (&logits)[kMaxAct], int act) {
   float v = 0.f;
 #pragma unroll

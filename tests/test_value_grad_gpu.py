@@ -173,7 +173,8 @@ def test_unaligned_params_slice(cuda, D, B, shift):
         ref, lref = ref.clone(), lref.clone()
         s, ls = mlp_grad(GradHead.VALUE_MSE, pv, X, 1, H, ret=ret)
         assert torch.equal(s, ref)
-        assert torch.equal(ls, lref)
+        # the kernels write columns 0..5 of a loss-slab row; 6 and 7 keep whatever the allocator's block held
+        assert torch.equal(ls[:, :6], lref[:, :6])
     finally:
         set_value_grad_mode(old)
 

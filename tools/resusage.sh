@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools_resusage.sh file.hip  -> one line per kernel: name VGPR AGPR spill occupancy LDS
+# usage: tools_resusage.sh file.hip  -> one line per kernel: name VGPR AGPR spill scratch occupancy LDS
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC ${RU_FLAGS} -c "$1" -o /tmp/_ru.o -Rpass-analysis=kernel-resource-usage 2>&1 | \
 python3 -c '
 import sys,re
@@ -15,5 +15,5 @@ for line in sys.stdin:
     elif cur is not None and ":" in s:
         k,v=s.split(":",1);cur[k.strip()]=v.strip()
 for r in rows:
-    print(r["name"][:70].ljust(70),"V",r.get("VGPRs"),"A",r.get("AGPRs"),"Vsp",r.get("VGPRs Spill"),"Ssp",r.get("SGPRs Spill"),"occ",r.get("Occupancy [waves/SIMD]"),"lds",r.get("LDS Size [bytes/block]"))
+    print(r["name"][:70].ljust(70),"V",r.get("VGPRs"),"A",r.get("AGPRs"),"Vsp",r.get("VGPRs Spill"),"Ssp",r.get("SGPRs Spill"),"scr",r.get("ScratchSize [bytes/lane]"),"occ",r.get("Occupancy [waves/SIMD]"),"lds",r.get("LDS Size [bytes/block]"))
 '
