@@ -417,39 +417,65 @@ void head_wgrad(const Tensor& h, const Tensor& dhead, int64_t B, int64_t A, cons
 
 int64_t pong_state_size() { return rrl_pong_state_size(); }
 
-void pong_step(const Tensor& state, const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& fin_ret,
-               const Tensor& fin_len, const OptT& ep_acc, int64_t N, int64_t seed, int64_t step, int64_t max_steps,
-               bool reset_all, const OptT& step_base, const OptT& obs, const OptT& hist, const OptT& frames,
-               const OptT& fidx, int64_t ring_slots) {
+// The per-env tensors every PongSynth step launch of N envs writes, checked
+struct PongOut {
+  float *state, *rew, *done, *fin_ret, *fin_len;
+};
+PongOut pong_outputs(const Tensor& state, const Tensor& rew, const Tensor& done, const Tensor& fin_ret,
+                     const Tensor& fin_len, int64_t N) {
   check(state, "state", at::kFloat, N * pong_state_size());
-  check(act, "act", at::kInt, reset_all ? 0 : N);
   check(rew, "rew", at::kFloat, N);
   check(done, "done", at::kFloat, N);
   check(fin_ret, "fin_ret", at::kFloat, N);
   check(fin_len, "fin_len", at::kFloat, N);
+  return {state.data_ptr<float>(), rew.data_ptr<float>(), done.data_ptr<float>(), fin_ret.data_ptr<float>(),
+          fin_len.data_ptr<float>()};
+}
+
+// Where a step launch of N envs draws: the frame ring (frames + fidx, R slots: ONE new frame per
+// env) when frames is given, else the s2d observations obs.  op: the caller, for the error.
+struct Picture {
+  uint8_t* obs;
+  uint8_t* frames;
+  int32_t* fidx;
+};
+bool given(const OptT& t) { return t.has_value() && t->defined(); }
+Picture picture_target(const OptT& obs, const OptT& frames, const OptT& fidx, int64_t N, int64_t R, const char* op) {
+  if (given(frames)) return {nullptr, ring_store(frames, fidx, N, R), fidx->data_ptr<int32_t>()};
+  TORCH_CHECK(given(obs), op, ": obs or frames + fidx is required");
+  check(*obs, "obs", at::kByte, N * 84 * 84 * 4);
+  return {obs->data_ptr<uint8_t>(), nullptr, nullptr};
+}
+
+// The head inputs of the fused launches: fc split-K partials, fc bias, the packed head parameters
+void check_head_inputs(const Tensor& part, const Tensor& fc_b, const Tensor& head_params, int64_t splits, int64_t N,
+                       int64_t A) {
+  constexpr int64_t F = 512;
+  check(part, "part", at::kFloat, splits * N * F);
+  check(fc_b, "fc_b", at::kFloat, F);
+  check(head_params, "head_params", at::kFloat, A * F + A + F + 1);
+}
+
+// One env step (pong.hip): step + render in one launch (obs, or frames + fidx), or with neither the
+// physics alone and, when given, the new frame histories hist [N][16] for a fused-render conv stack.
+void pong_step(const Tensor& state, const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& fin_ret,
+               const Tensor& fin_len, const OptT& ep_acc, int64_t N, int64_t seed, int64_t step, int64_t max_steps,
+               bool reset_all, const OptT& step_base, const OptT& obs, const OptT& hist, const OptT& frames,
+               const OptT& fidx, int64_t ring_slots) {
+  const PongOut o = pong_outputs(state, rew, done, fin_ret, fin_len, N);
+  check(act, "act", at::kInt, reset_all ? 0 : N);
   float* acc = opt_ptr<float>(ep_acc, "ep_acc", at::kFloat, 4 * N);
   const unsigned long long* sb = opt_ptr<const unsigned long long>(step_base, "step_base", at::kLong, 1);
-  if (frames.has_value() && frames->defined()) {  // step + ONE new frame into the frame ring (pong.hip)
-    uint8_t* fp = ring_store(frames, fidx, N, ring_slots);
-    rc_check(rrl_pong_step_render(state.data_ptr<float>(), act.data_ptr<int32_t>(), rew.data_ptr<float>(),
-                                  done.data_ptr<float>(), fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), acc,
-                                  nullptr, (int)N, (uint64_t)seed, (uint64_t)step, sb, (int)max_steps,
-                                  reset_all ? 1 : 0, fp, fidx->data_ptr<int32_t>(), (int)ring_slots, cur_stream()),
-             "pong_step_render (frame ring)");
-    return;
-  }
-  if (obs.has_value() && obs->defined()) {  // step + render in one launch (pong.hip)
-    check(*obs, "obs", at::kByte, N * 84 * 84 * 4);
-    rc_check(rrl_pong_step_render(state.data_ptr<float>(), act.data_ptr<int32_t>(), rew.data_ptr<float>(),
-                                  done.data_ptr<float>(), fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), acc,
-                                  obs->data_ptr<uint8_t>(), (int)N, (uint64_t)seed, (uint64_t)step, sb,
-                                  (int)max_steps, reset_all ? 1 : 0, nullptr, nullptr, 0, cur_stream()),
+  if (given(frames) || given(obs)) {
+    const Picture pic = picture_target(obs, frames, fidx, N, ring_slots, "pong_step");
+    rc_check(rrl_pong_step_render(o.state, act.data_ptr<int32_t>(), o.rew, o.done, o.fin_ret, o.fin_len, acc, pic.obs,
+                                  (int)N, (uint64_t)seed, (uint64_t)step, sb, (int)max_steps, reset_all ? 1 : 0,
+                                  pic.frames, pic.fidx, (int)ring_slots, cur_stream()),
              "pong_step_render");
     return;
   }
-  float* hout = opt_ptr<float>(hist, "hist", at::kFloat, N * 16);  // the new frame histories (fused render)
-  rc_check(rrl_pong_step(state.data_ptr<float>(), act.data_ptr<int32_t>(), rew.data_ptr<float>(),
-                         done.data_ptr<float>(), fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), acc, (int)N,
+  float* hout = opt_ptr<float>(hist, "hist", at::kFloat, N * 16);
+  rc_check(rrl_pong_step(o.state, act.data_ptr<int32_t>(), o.rew, o.done, o.fin_ret, o.fin_len, acc, (int)N,
                          (uint64_t)seed, (uint64_t)step, sb, (int)max_steps, reset_all ? 1 : 0, hout, cur_stream()),
            "pong_step");
 }
@@ -462,39 +488,23 @@ void pong_head_step(const Tensor& part, int64_t splits, const Tensor& fc_b, cons
                     const Tensor& done, const Tensor& fin_ret, const Tensor& fin_len, const OptT& ep_acc,
                     const OptT& obs, int64_t N, int64_t seed, int64_t step, const OptT& step_base,
                     int64_t max_steps, const OptT& frames, const OptT& fidx, int64_t ring_slots) {
-  constexpr int64_t F = 512;
   TORCH_CHECK(A >= 1 && A <= 8 && splits >= 1 && N >= 1, "pong_head_step: 1 <= A <= 8, splits >= 1");
-  check(part, "part", at::kFloat, splits * N * F);
-  check(fc_b, "fc_b", at::kFloat, F);
-  check(head_params, "head_params", at::kFloat, A * F + A + F + 1);
-  check(h_out, "h_out", at::kBFloat16, N * F);
+  check_head_inputs(part, fc_b, head_params, splits, N, A);
+  check(h_out, "h_out", at::kBFloat16, N * 512);
   check(act, "act", at::kInt, N);
   check(logp, "logp", at::kFloat, N);
   check(value, "value", at::kFloat, N);
-  check(state, "state", at::kFloat, N * pong_state_size());
-  check(rew, "rew", at::kFloat, N);
-  check(done, "done", at::kFloat, N);
-  check(fin_ret, "fin_ret", at::kFloat, N);
-  check(fin_len, "fin_len", at::kFloat, N);
-  uint8_t* fp = nullptr;
-  uint8_t* op = nullptr;
-  if (frames.has_value() && frames->defined()) {
-    fp = ring_store(frames, fidx, N, ring_slots);
-  } else {
-    TORCH_CHECK(obs.has_value() && obs->defined(), "pong_head_step: obs or frames + fidx is required");
-    check(*obs, "obs", at::kByte, N * 84 * 84 * 4);
-    op = obs->data_ptr<uint8_t>();
-  }
+  const PongOut o = pong_outputs(state, rew, done, fin_ret, fin_len, N);
+  const Picture pic = picture_target(obs, frames, fidx, N, ring_slots, "pong_head_step");
   float* acc = opt_ptr<float>(ep_acc, "ep_acc", at::kFloat, 4 * N);
   const unsigned long long* sb = opt_ptr<const unsigned long long>(step_base, "step_base", at::kLong, 1);
   const unsigned long long* ssb = opt_ptr<const unsigned long long>(sample_base, "sample_base", at::kLong, 1);
   rc_check(rrl_pong_head_step_render(part.data_ptr<float>(), (int)splits, fc_b.data_ptr<float>(),
                                      head_params.data_ptr<float>(), (int)A, bf(h_out), act.data_ptr<int32_t>(),
                                      logp.data_ptr<float>(), value.data_ptr<float>(), (uint64_t)sample_seed,
-                                     (uint64_t)sample_step, ssb, state.data_ptr<float>(), rew.data_ptr<float>(),
-                                     done.data_ptr<float>(), fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), acc,
-                                     op, (int)N, (uint64_t)seed, (uint64_t)step, sb, (int)max_steps, fp,
-                                     fp ? fidx->data_ptr<int32_t>() : nullptr, (int)ring_slots, cur_stream()),
+                                     (uint64_t)sample_step, ssb, o.state, o.rew, o.done, o.fin_ret, o.fin_len, acc,
+                                     pic.obs, (int)N, (uint64_t)seed, (uint64_t)step, sb, (int)max_steps, pic.frames,
+                                     pic.fidx, (int)ring_slots, cur_stream()),
            "pong_head_step");
 }
 
@@ -509,18 +519,11 @@ void pong_eval_step(const Tensor& part, int64_t splits, const Tensor& fc_b, cons
                     const Tensor& ep_len, const Tensor& ep_code, const Tensor& remaining, const OptT& frames,
                     const OptT& fidx, int64_t ring_slots, const OptT& tr_act, const OptT& tr_logits, const OptT& tr_rew,
                     const OptT& tr_done) {
-  constexpr int64_t F = 512;
   TORCH_CHECK(A >= 1 && A <= 8 && splits >= 1 && N >= 1, "pong_eval_step: 1 <= A <= 8, splits >= 1, N >= 1");
   TORCH_CHECK(E >= 1 && max_steps >= 1 && E * max_steps < (int64_t(1) << 31),
               "pong_eval_step: E >= 1, max_steps >= 1 and E * max_steps < 2^31");
-  check(part, "part", at::kFloat, splits * N * F);
-  check(fc_b, "fc_b", at::kFloat, F);
-  check(head_params, "head_params", at::kFloat, A * F + A + F + 1);
-  check(state, "state", at::kFloat, N * pong_state_size());
-  check(rew, "rew", at::kFloat, N);
-  check(done, "done", at::kFloat, N);
-  check(fin_ret, "fin_ret", at::kFloat, N);
-  check(fin_len, "fin_len", at::kFloat, N);
+  check_head_inputs(part, fc_b, head_params, splits, N, A);
+  const PongOut o = pong_outputs(state, rew, done, fin_ret, fin_len, N);
   check(ep_cnt, "ep_cnt", at::kInt, N);
   check(remaining, "remaining", at::kInt, 1);
   // the slots are indexed [k][N]: a tensor of another row length would be written across its rows
@@ -532,30 +535,19 @@ void pong_eval_step(const Tensor& part, int64_t splits, const Tensor& fc_b, cons
   slots(ep_ret, "ep_ret", at::kFloat);
   slots(ep_len, "ep_len", at::kInt);
   slots(ep_code, "ep_code", at::kInt);
-  const int ntr = int(tr_act.has_value() && tr_act->defined()) + int(tr_logits.has_value() && tr_logits->defined()) +
-                  int(tr_rew.has_value() && tr_rew->defined()) + int(tr_done.has_value() && tr_done->defined());
+  const int ntr = int(given(tr_act)) + int(given(tr_logits)) + int(given(tr_rew)) + int(given(tr_done));
   TORCH_CHECK(ntr == 0 || ntr == 4, "pong_eval_step: tr_act, tr_logits, tr_rew and tr_done go together (all or none)");
   int32_t* ta = opt_ptr<int32_t>(tr_act, "tr_act", at::kInt, N);
   float* tl = opt_ptr<float>(tr_logits, "tr_logits", at::kFloat, N * A);
   float* tr = opt_ptr<float>(tr_rew, "tr_rew", at::kFloat, N);
   float* td = opt_ptr<float>(tr_done, "tr_done", at::kFloat, N);
-  uint8_t* fp = nullptr;
-  uint8_t* op = nullptr;
-  if (frames.has_value() && frames->defined()) {
-    fp = ring_store(frames, fidx, N, ring_slots);
-  } else {
-    TORCH_CHECK(obs.has_value() && obs->defined(), "pong_eval_step: obs or frames + fidx is required");
-    check(*obs, "obs", at::kByte, N * 84 * 84 * 4);
-    op = obs->data_ptr<uint8_t>();
-  }
+  const Picture pic = picture_target(obs, frames, fidx, N, ring_slots, "pong_eval_step");
   rc_check(rrl_pong_eval_step(part.data_ptr<float>(), (int)splits, fc_b.data_ptr<float>(), head_params.data_ptr<float>(),
-                              (int)A, greedy ? 1 : 0, (uint64_t)sample_seed, (uint64_t)sample_step,
-                              state.data_ptr<float>(), rew.data_ptr<float>(), done.data_ptr<float>(),
-                              fin_ret.data_ptr<float>(), fin_len.data_ptr<float>(), op, (int)N, (uint64_t)seed,
-                              (uint64_t)step, (int)max_steps, fp, fp ? fidx->data_ptr<int32_t>() : nullptr,
-                              (int)ring_slots, (int)E, ep_cnt.data_ptr<int32_t>(), ep_ret.data_ptr<float>(),
-                              ep_len.data_ptr<int32_t>(), ep_code.data_ptr<int32_t>(), remaining.data_ptr<int32_t>(), ta,
-                              tl, tr, td, cur_stream()),
+                              (int)A, greedy ? 1 : 0, (uint64_t)sample_seed, (uint64_t)sample_step, o.state, o.rew,
+                              o.done, o.fin_ret, o.fin_len, pic.obs, (int)N, (uint64_t)seed, (uint64_t)step,
+                              (int)max_steps, pic.frames, pic.fidx, (int)ring_slots, (int)E, ep_cnt.data_ptr<int32_t>(),
+                              ep_ret.data_ptr<float>(), ep_len.data_ptr<int32_t>(), ep_code.data_ptr<int32_t>(),
+                              remaining.data_ptr<int32_t>(), ta, tl, tr, td, cur_stream()),
            "pong_eval_step");
 }
 

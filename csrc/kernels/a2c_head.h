@@ -43,6 +43,26 @@ struct HeadArgs {
   uint16_t* h_out;        // [B][F]
 };
 
+// The arguments every head launch starts from: the packed parameters head_params =
+// [A x 512 policy rows | A biases | 512 value row | value bias], B rows, and the sample draw's
+// seed and step (step_base: see above).  Everything else is zero / null.
+inline HeadArgs head_args(const float* head_params, int A, int B, unsigned long long seed, unsigned long long step,
+                          const unsigned long long* step_base) {
+  HeadArgs a = {};
+  a.w = head_params;
+  a.bias = head_params + A * kHeadF;
+  a.w_v = a.bias + A;
+  a.b_v = a.w_v + kHeadF;
+  a.B = B;
+  a.A = A;
+  a.seed_lo = (uint32_t)seed;
+  a.seed_hi = (uint32_t)(seed >> 32);
+  a.step_lo = (uint32_t)step;
+  a.step_hi = (uint32_t)(step >> 32);
+  a.step_base = step_base;
+  return a;
+}
+
 // fp32 split-K partial sum of one lane's 8 features (S > 0: compile-time split count)
 template <int S>
 __device__ __forceinline__ void head_sum_part(float (&v)[8], const float* pr, size_t zs, int splits) {
@@ -142,38 +162,33 @@ RRL_DEV int a2c_rollout_row_streamed(const HeadArgs& a, int row, int lane, const
       logits[o] = wave_sum(s) + a.bias[o];
     }
   }
-  if constexpr (EVAL) {
-    int pick = -1;
-    if (lane == 0) {
-      if (lg_out) {
-#pragma unroll
-        for (int o = 0; o < AMAX; ++o)
-          if (o < A) lg_out[o] = logits[o];
-      }
-      if (greedy) {
-        pick = head_argmax_first(A, logits);
-      } else {
-        const CatStats cs = cat_stats(A, logits);
-        unsigned long long st = ((unsigned long long)a.step_hi << 32) | a.step_lo;
-        if (a.step_base) st += *a.step_base;
-        const uint4 r = philox4x32(make_uint4((uint32_t)(row + a.row_offset), (uint32_t)st, (uint32_t)(st >> 32), 0x50u),
-                                   make_uint2(a.seed_lo, a.seed_hi));
-        pick = cat_sample(A, logits, cs.lse, u01(r.x));
-      }
-    }
-    return pick;
-  }
-  const CatStats cs = cat_stats(A, logits);
+  // where the statistics are taken is all the two forms keep apart: the rollout on every lane ahead
+  // of lane 0's branch, as a2c_head_kernel does (its kernels compile as they did before the tails
+  // were merged); the evaluation only where it draws
+  CatStats cs = {};
+  if constexpr (!EVAL) cs = cat_stats(A, logits);
   int pick = -1;
   if (lane == 0) {
-    unsigned long long st = ((unsigned long long)a.step_hi << 32) | a.step_lo;
-    if (a.step_base) st += *a.step_base;
-    const uint4 r = philox4x32(make_uint4((uint32_t)(row + a.row_offset), (uint32_t)st, (uint32_t)(st >> 32), 0x50u),
-                               make_uint2(a.seed_lo, a.seed_hi));
-    pick = cat_sample(A, logits, cs.lse, u01(r.x));
-    if (a.act) a.act[row] = pick;
-    if (a.logp) a.logp[row] = pick_logit(A, logits, pick) - cs.lse;
-    if (a.value) a.value[row] = value;
+    if (EVAL && lg_out) {
+#pragma unroll
+      for (int o = 0; o < AMAX; ++o)
+        if (o < A) lg_out[o] = logits[o];
+    }
+    if (EVAL && greedy) {
+      pick = head_argmax_first(A, logits);
+    } else {
+      if constexpr (EVAL) cs = cat_stats(A, logits);
+      unsigned long long st = ((unsigned long long)a.step_hi << 32) | a.step_lo;
+      if (a.step_base) st += *a.step_base;
+      const uint4 r = philox4x32(make_uint4((uint32_t)(row + a.row_offset), (uint32_t)st, (uint32_t)(st >> 32), 0x50u),
+                                 make_uint2(a.seed_lo, a.seed_hi));
+      pick = cat_sample(A, logits, cs.lse, u01(r.x));
+      if constexpr (!EVAL) {
+        if (a.act) a.act[row] = pick;
+        if (a.logp) a.logp[row] = pick_logit(A, logits, pick) - cs.lse;
+        if (a.value) a.value[row] = value;
+      }
+    }
   }
   return pick;
 }

@@ -1989,27 +1989,16 @@ int rrl_a2c_head(int mode, const uint16_t* h, const float* head_params, int B, i
   hipStream_t st = (hipStream_t)stream_;
   if (A < 1 || A > kMaxAct) return -1;
   if (part && (mode != 0 || !fc_b || !h_out || splits < 1)) return -1;
-  HeadArgs a;
+  HeadArgs a = head_args(head_params, A, B, seed, step, step_base);
   a.part = part;
   a.splits = splits;
   a.fc_b = fc_b;
   a.h_out = h_out;
   a.h = h;
-  a.w = head_params;
-  a.bias = head_params + A * kHeadF;
-  a.w_v = a.bias + A;
-  a.b_v = a.w_v + kHeadF;
-  a.B = B;
-  a.A = A;
   a.act = act;
   a.logp = logp;
   a.value = value;
   a.logits_out = logits_out;
-  a.seed_lo = (uint32_t)seed;
-  a.seed_hi = (uint32_t)(seed >> 32);
-  a.step_lo = (uint32_t)step;
-  a.step_hi = (uint32_t)(step >> 32);
-  a.step_base = step_base;
   a.row_offset = row_offset;
   a.act_in = act_in;
   a.adv = adv;

@@ -58,12 +58,25 @@ struct PongEnd {
   float ret, len;
 };
 
-RRL_DEV void pong_step_state(int e, float* s, int a, float* __restrict__ rew,
-                             float* __restrict__ done, float* __restrict__ fin_ret, float* __restrict__ fin_len,
-                             float* __restrict__ ep_acc, uint2 key, uint32_t step_lo, uint32_t step_hi, int max_steps,
-                             int reset_all, const unsigned long long* __restrict__ step_base, PongEnd* end = nullptr) {
-  if (step_base) {  // device step counter (graph replays): the host value is an offset
-    const unsigned long long st = (((unsigned long long)step_hi << 32) | step_lo) + *step_base;
+// What a step launch hands every env: the per-env outputs ([N] each; ep_acc [N][4] or null), the
+// Philox key, the step counter (a host value, or an offset to the device counter *step_base for
+// graph replays), the time limit, and reset_all (every env is reset, no action is read).
+struct PongStepArgs {
+  float *rew, *done, *fin_ret, *fin_len, *ep_acc;
+  uint2 key;
+  uint32_t step_lo, step_hi;
+  int max_steps, reset_all;
+  const unsigned long long* step_base;
+};
+
+RRL_DEV void pong_step_state(int e, float* s, int a, const PongStepArgs& p, PongEnd* end = nullptr) {
+  // the names the step below was written with (tests/pong_oracle.py follows it line by line)
+  float *rew = p.rew, *done = p.done, *fin_ret = p.fin_ret, *fin_len = p.fin_len, *ep_acc = p.ep_acc;
+  const uint2 key = p.key;
+  uint32_t step_lo = p.step_lo, step_hi = p.step_hi;
+  const int max_steps = p.max_steps, reset_all = p.reset_all;
+  if (p.step_base) {  // device step counter (graph replays): the host value is an offset
+    const unsigned long long st = (((unsigned long long)step_hi << 32) | step_lo) + *p.step_base;
     step_lo = (uint32_t)st;
     step_hi = (uint32_t)(st >> 32);
   }
@@ -135,15 +148,12 @@ RRL_DEV void pong_step_state(int e, float* s, int a, float* __restrict__ rew,
   }
 }
 
-RRL_DEV void pong_step_env(int e, float* __restrict__ state, const int32_t* __restrict__ act, float* __restrict__ rew,
-                           float* __restrict__ done, float* __restrict__ fin_ret, float* __restrict__ fin_len,
-                           float* __restrict__ ep_acc, uint2 key, uint32_t step_lo, uint32_t step_hi, int max_steps,
-                           int reset_all, const unsigned long long* __restrict__ step_base, float* __restrict__ hist_out) {
+RRL_DEV void pong_step_env(int e, float* __restrict__ state, const int32_t* __restrict__ act, const PongStepArgs& p,
+                           float* __restrict__ hist_out) {
   float s[kPongState];
 #pragma unroll
   for (int i = 0; i < kPongState; ++i) s[i] = state[(size_t)e * kPongState + i];
-  pong_step_state(e, s, reset_all ? 0 : act[e], rew, done, fin_ret, fin_len, ep_acc, key, step_lo, step_hi, max_steps, reset_all,
-                  step_base);
+  pong_step_state(e, s, p.reset_all ? 0 : act[e], p);
 #pragma unroll
   for (int i = 0; i < kPongState; ++i) state[(size_t)e * kPongState + i] = s[i];
   if (hist_out) {  // the new frame history: all a fused-render conv kernel needs to draw the observation
@@ -154,66 +164,17 @@ RRL_DEV void pong_step_env(int e, float* __restrict__ state, const int32_t* __re
   }
 }
 
-__global__ void pong_step_kernel(float* __restrict__ state, const int32_t* __restrict__ act, float* __restrict__ rew,
-                                 float* __restrict__ done, float* __restrict__ fin_ret, float* __restrict__ fin_len,
-                                 float* __restrict__ ep_acc, int N, uint2 key, uint32_t step_lo, uint32_t step_hi, int max_steps,
-                                 int reset_all, const unsigned long long* __restrict__ step_base,
+__global__ void pong_step_kernel(float* __restrict__ state, const int32_t* __restrict__ act, PongStepArgs p, int N,
                                  float* __restrict__ hist_out) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= N) return;
-  pong_step_env(e, state, act, rew, done, fin_ret, fin_len, ep_acc, key, step_lo, step_hi, max_steps, reset_all,
-                step_base, hist_out);
-}
-
-// The row-only half of pong_render_chunk, once per image row y (84 per env instead of once per
-// chunk: 21 chunks share a row): bit f = ball on the row in frame f, 4 + f = agent paddle,
-// 8 + f = opponent paddle, 12 = wall.  Same float comparisons, so the render stays bitwise.
-RRL_DEV uint32_t pong_row_flags(const float* h, int y) {
-  const float fy = (float)y + 0.5f;
-  uint32_t m = (fy < kTop || fy >= kBot) ? (1u << 12) : 0u;
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    const float by = h[4 * f + 1], pa = h[4 * f + 2], po = h[4 * f + 3];
-    if (fy >= by && fy < by + kBall) m |= 1u << f;
-    if (fabsf(fy - pa) < kPadHalf) m |= 1u << (4 + f);
-    if (fabsf(fy - po) < kPadHalf) m |= 1u << (8 + f);
-  }
-  return m;
-}
-
-// pong_render_chunk from the per-row flags: an unlit row (most of the screen) is one LDS read
-// and a constant; lit rows keep only the per-pixel x tests.
-RRL_DEV uint4 pong_render_chunk_rows(const float* h, const uint32_t* rows, int q) {
-  const int a = q / 84, rem = q - a * 84, c = rem >> 2, dy = rem & 3;
-  const uint32_t m = rows[4 * a + dy];
-  const bool wall = (m >> 12) & 1u;
-  if ((m & 0xfffu) == 0u) {
-    const uint32_t v = wall ? 0x64646464u : 0u;
-    return make_uint4(v, v, v, v);
-  }
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    const float bx = h[4 * f];
-    const bool b_on = (m >> f) & 1u, pa_on = (m >> (4 + f)) & 1u, po_on = (m >> (8 + f)) & 1u;
-#pragma unroll
-    for (int px = 0; px < 4; ++px) {
-      const float fx = (float)(4 * c + px) + 0.5f;
-      uint32_t v = wall ? 100u : 0u;
-      if (pa_on && fx >= kAgentX && fx < kAgentX + kPadW) v = 255u;
-      if (po_on && fx >= kOppX && fx < kOppX + kPadW) v = 255u;
-      if (b_on && fx >= bx && fx < bx + kBall) v = 255u;
-      w[px] |= v << (8 * f);
-    }
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
+  pong_step_env(e, state, act, p, hist_out);
 }
 
 __global__ void pong_render_kernel(const float* __restrict__ state, uint8_t* __restrict__ obs, int N) {
-  constexpr int kChunks = kPongHW * kPongHW * 4 / 16;  // 1764 per env
   const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (t >= (size_t)N * kChunks) return;
-  const int e = (int)(t / kChunks), q = (int)(t % kChunks);
+  if (t >= (size_t)N * kPongChunks) return;
+  const int e = (int)(t / kPongChunks), q = (int)(t % kPongChunks);
   *reinterpret_cast<uint4*>(obs + t * 16) = pong_render_chunk(state + (size_t)e * kPongState + P_HIST, q);
 }
 
@@ -246,7 +207,7 @@ RRL_DEV void pong_ring_write(const RingOut& ro, int e, int N, const float* ss, u
   }
   __syncthreads();
   uint8_t* fo = ro.frames + ((size_t)pong_ring_slot(st, ro.R) * N + e) * kPongFrameBytes;
-  for (int q = t; q < kPongFramePos; q += blockDim.x)
+  for (int q = t; q < kPongFramePos; q += 256)
     *reinterpret_cast<uint4*>(fo + 16 * q) = pong_frame_chunk(h3[0], rows, q);
 }
 
@@ -279,16 +240,36 @@ __global__ void __launch_bounds__(256) pong_ring_fill_kernel(float* __restrict__
   }
 }
 
-// Step + render in one launch: workgroup e steps env e on one thread (the physics is a short
-// serial chain) and renders its 1,764 chunks on all 256 threads from the new history in LDS.
-// One launch per env step instead of two, and the tiny step kernel's own launch / drain is gone.
+// Where a step launch draws: the s2d frame stack obs [N][21][21][64], or with RING the ring.
+// All 256 threads of env e's workgroup, the stepped state row in LDS (ss).
 template <bool RING>
-__global__ void __launch_bounds__(256, 8) pong_step_render_kernel(
-    float* __restrict__ state, const int32_t* __restrict__ act, float* __restrict__ rew, float* __restrict__ done,
-    float* __restrict__ fin_ret, float* __restrict__ fin_len, float* __restrict__ ep_acc, uint8_t* __restrict__ obs,
-    uint2 key, uint32_t step_lo, uint32_t step_hi, int max_steps, int reset_all,
-    const unsigned long long* __restrict__ step_base, RingOut ro) {
-  constexpr int kChunks = kPongHW * kPongHW * 4 / 16;
+RRL_DEV void pong_write_picture(uint8_t* __restrict__ obs, const RingOut& ro, const PongStepArgs& p, int e,
+                                const float* ss, uint32_t* rows) {
+  if constexpr (RING) {  // one new frame + the observation's frame rows
+    pong_ring_write(ro, e, gridDim.x, ss, rows, pong_abs_step(p.step_lo, p.step_hi, p.step_base));
+  } else {
+    const int t = threadIdx.x;
+    const float* hist = ss + P_HIST;
+    // the render is VALU-bound (every chunk re-tested its row against 12 objects): the row tests
+    // once per row here, the chunks then read them (21 chunks per row)
+    if (t < kPongHW) rows[t] = pong_row_flags(hist, t);
+    __syncthreads();
+    uint8_t* o = obs + (size_t)e * kPongChunks * 16;
+    for (int q = t; q < kPongChunks; q += 256)
+      *reinterpret_cast<uint4*>(o + (size_t)q * 16) = pong_render_chunk_rows(hist, rows, q);
+  }
+}
+
+// Env e's workgroup of a step launch (grid = N envs, 256 threads), the one body of the three
+// kernels below: load the state row, step it on thread 0, store it, draw.  The physics is a short
+// serial chain; the 1,764 chunks (or the ring frame) are drawn by all threads from the new history
+// in LDS.  The kernels differ in three callables:
+//   before(e, t)       every thread, before the first barrier (the head leaves its action in LDS)
+//   action(e)          thread 0: the action to step with
+//   after(e, a, end)   thread 0, after the physics, before the second barrier
+template <bool RING, class Before, class Action, class After>
+RRL_DEV void pong_env_workgroup(float* __restrict__ state, const PongStepArgs& p, uint8_t* __restrict__ obs,
+                                const RingOut& ro, Before before, Action action, After after) {
   __shared__ float ss[kPongState];
   __shared__ uint32_t rows[kPongHW];
   const int e = blockIdx.x, t = threadIdx.x;
@@ -296,47 +277,28 @@ __global__ void __launch_bounds__(256, 8) pong_step_render_kernel(
   // in registers it set the kernel at 67 VGPRs = 7 waves per SIMD, so 1/8 of the 2,048
   // workgroups of a step waited for a second round
   if (t < kPongState) ss[t] = state[(size_t)e * kPongState + t];
+  before(e, t);
   __syncthreads();
-  if (t == 0)
-    pong_step_state(e, ss, reset_all ? 0 : act[e], rew, done, fin_ret, fin_len, ep_acc, key, step_lo, step_hi, max_steps, reset_all,
-                    step_base);
+  if (t == 0) {
+    PongEnd end{};
+    const int a = action(e);
+    pong_step_state(e, ss, a, p, &end);
+    after(e, a, end);
+  }
   __syncthreads();
   if (t < kPongState) state[(size_t)e * kPongState + t] = ss[t];
-  if constexpr (RING) {  // one new frame + the observation's frame rows
-    pong_ring_write(ro, e, gridDim.x, ss, rows, pong_abs_step(step_lo, step_hi, step_base));
-    return;
-  }
-  const float* hist = ss + P_HIST;
-  // the render is VALU-bound (every chunk re-tested its row against 12 objects): the row tests
-  // once per row here, the chunks then read them (21 chunks per row)
-  if (t < kPongHW) rows[t] = pong_row_flags(hist, t);
-  __syncthreads();
-  uint8_t* o = obs + (size_t)e * kChunks * 16;
-  for (int q = threadIdx.x; q < kChunks; q += 256)
-    *reinterpret_cast<uint4*>(o + (size_t)q * 16) = pong_render_chunk_rows(hist, rows, q);
+  pong_write_picture<RING>(obs, ro, p, e, ss, rows);
 }
 
-
-// The rollout step's policy head fused in front of the env step: one workgroup per env, wave 0
-// forms the env's hidden row from the fc split-K partials and samples its action
-// (a2c_rollout_row_streamed: bitwise the a2c_head_kernel result), thread 0 steps the physics
-// with it, and the workgroup renders the new frame stack -- one launch instead of head + step
-// (the head launch was ~10 us per rollout step at 2,048 envs, mostly its fixed cost).
-template <int AMAX, bool WLDS, bool RING = false>
-__global__ void __launch_bounds__(256, 8) pong_head_step_render_kernel(
-    HeadArgs ha, float* __restrict__ state, float* __restrict__ rew, float* __restrict__ done,
-    float* __restrict__ fin_ret, float* __restrict__ fin_len, float* __restrict__ ep_acc, uint8_t* __restrict__ obs,
-    uint2 key, uint32_t step_lo, uint32_t step_hi, int max_steps, const unsigned long long* __restrict__ step_base,
-    RingOut ro) {
-  constexpr int kChunks = kPongHW * kPongHW * 4 / 16;
-  __shared__ float ss[kPongState];
-  __shared__ uint32_t rows[kPongHW];
-  __shared__ int pick_s;
-  const int e = blockIdx.x, t = threadIdx.x;
-  if (t < kPongState) ss[t] = state[(size_t)e * kPongState + t];
+// The policy head in front of the env step: wave 0 forms env e's hidden row from the fc split-K
+// partials and picks its action (a2c_rollout_row_streamed: bitwise the a2c_head_kernel result),
+// thread 0 leaves it in *pick_s for the thread that steps the env after the next barrier.
+// WLDS: waves 1-3 copy the head weights (w_v, then the A policy rows) into LDS while wave 0 sums
+// the fc partials: one L2 round trip instead of one per output row (RRL_PONG_HEAD_WLDS).
+template <int AMAX, bool WLDS, bool EVAL = false>
+RRL_DEV void pong_head_pick(const HeadArgs& ha, int e, int t, int* pick_s, int greedy = 0, float* lg_out = nullptr) {
+  const float *wv = ha.w_v, *wp = ha.w;
   if constexpr (WLDS) {
-    // waves 1-3 copy the head weights (w_v, then the A policy rows) into LDS while wave 0 sums
-    // the fc partials: one L2 round trip instead of one per output row (RRL_PONG_HEAD_WLDS)
     __shared__ __attribute__((aligned(16))) float wl[(AMAX + 1) * kHeadF];
     const int nf4 = (ha.A + 1) * (kHeadF / 4);
     for (int i = t - 64; i >= 0 && i < nf4; i += 192) {
@@ -344,29 +306,43 @@ __global__ void __launch_bounds__(256, 8) pong_head_step_render_kernel(
       *reinterpret_cast<float4*>(wl + 4 * i) = *reinterpret_cast<const float4*>(src);
     }
     __syncthreads();
-    if (t < 64) {
-      const int pick = a2c_rollout_row_streamed<AMAX>(ha, e, t, wl, wl + kHeadF);
-      if (t == 0) pick_s = pick;
-    }
-  } else if (t < 64) {
-    const int pick = a2c_rollout_row_streamed<AMAX>(ha, e, t);
-    if (t == 0) pick_s = pick;
+    wv = wl;
+    wp = wl + kHeadF;
   }
-  __syncthreads();
-  if (t == 0)
-    pong_step_state(e, ss, pick_s, rew, done, fin_ret, fin_len, ep_acc, key, step_lo, step_hi, max_steps, 0, step_base);
-  __syncthreads();
-  if (t < kPongState) state[(size_t)e * kPongState + t] = ss[t];
-  if constexpr (RING) {
-    pong_ring_write(ro, e, gridDim.x, ss, rows, pong_abs_step(step_lo, step_hi, step_base));
-    return;
+  if (t < 64) {
+    const int pick = a2c_rollout_row_streamed<AMAX, EVAL>(ha, e, t, wv, wp, greedy, lg_out);
+    if (t == 0) *pick_s = pick;
   }
-  const float* hist = ss + P_HIST;
-  if (t < kPongHW) rows[t] = pong_row_flags(hist, t);
-  __syncthreads();
-  uint8_t* o = obs + (size_t)e * kChunks * 16;
-  for (int q = threadIdx.x; q < kChunks; q += 256)
-    *reinterpret_cast<uint4*>(o + (size_t)q * 16) = pong_render_chunk_rows(hist, rows, q);
+}
+
+// Step + render in one launch instead of two: the tiny step kernel's own launch / drain is gone.
+// step_base is p.step_base once more: only as a __restrict__ kernel parameter is the device counter
+// read with a scalar load behind the stores of the launch (through the struct it is a vector load
+// on thread 0's path, +0.4 us per fused step launch at 2,048 envs).
+template <bool RING>
+__global__ void __launch_bounds__(256, 8) pong_step_render_kernel(float* __restrict__ state,
+                                                                  const int32_t* __restrict__ act, PongStepArgs p,
+                                                                  const unsigned long long* __restrict__ step_base,
+                                                                  uint8_t* __restrict__ obs, RingOut ro) {
+  p.step_base = step_base;
+  pong_env_workgroup<RING>(
+      state, p, obs, ro, [](int, int) {}, [&](int e) { return p.reset_all ? 0 : act[e]; },
+      [](int, int, const PongEnd&) {});
+}
+
+// The rollout step's policy head fused in front of the env step -- one launch instead of head +
+// step (the head launch was ~10 us per rollout step at 2,048 envs, mostly its fixed cost).
+template <int AMAX, bool WLDS, bool RING = false>
+__global__ void __launch_bounds__(256, 8) pong_head_step_render_kernel(HeadArgs ha, float* __restrict__ state,
+                                                                       PongStepArgs p,
+                                                                       const unsigned long long* __restrict__ step_base,
+                                                                       uint8_t* __restrict__ obs, RingOut ro) {
+  __shared__ int pick_s;
+  p.step_base = step_base;
+  p.reset_all = 0;  // known here, so the reset-all path is not compiled in
+  pong_env_workgroup<RING>(
+      state, p, obs, ro, [&](int e, int t) { pong_head_pick<AMAX, WLDS>(ha, e, t, &pick_s); },
+      [&](int) { return pick_s; }, [](int, int, const PongEnd&) {});
 }
 
 // Policy evaluation's bookkeeping (rrl_pong_eval_step): every env plays E whole episodes, slot k of
@@ -385,64 +361,55 @@ struct EvalOut {
   float* tr_done;     // [N]
 };
 
-// One evaluation step: pong_head_step_render_kernel with the greedy (or the rollout's sampled)
-// action, nothing stored for a backward pass, and the per-env episode slots.  An env that has
-// finished its E episodes is FROZEN: its workgroup leaves before the first barrier (ep_cnt[e] is
-// uniform over the workgroup and only thread 0 writes it, after the barriers) and writes nothing,
-// so its state, frames, fidx row and trace rows stay what its last step left.
+// One evaluation step: the fused head + step with the greedy (or the rollout's sampled) action,
+// nothing stored for a backward pass, and the per-env episode slots.  An env that has finished its
+// E episodes is FROZEN: its workgroup leaves before the first barrier (ep_cnt[e] is uniform over
+// the workgroup and only thread 0 writes it, after the barriers) and writes nothing, so its state,
+// frames, fidx row and trace rows stay what its last step left.
 template <int AMAX, bool RING>
-__global__ void __launch_bounds__(256, 8) pong_eval_step_kernel(
-    HeadArgs ha, EvalOut ev, float* __restrict__ state, float* __restrict__ rew, float* __restrict__ done,
-    float* __restrict__ fin_ret, float* __restrict__ fin_len, uint8_t* __restrict__ obs, uint2 key, uint32_t step_lo,
-    uint32_t step_hi, int max_steps, RingOut ro) {
-  constexpr int kChunks = kPongHW * kPongHW * 4 / 16;
-  __shared__ float ss[kPongState];
-  __shared__ uint32_t rows[kPongHW];
+__global__ void __launch_bounds__(256, 8) pong_eval_step_kernel(HeadArgs ha, EvalOut ev, float* __restrict__ state,
+                                                                PongStepArgs p, uint8_t* __restrict__ obs, RingOut ro) {
   __shared__ int pick_s;
-  const int e = blockIdx.x, t = threadIdx.x, N = gridDim.x;
-  const int k = ev.ep_cnt[e];
+  const int N = gridDim.x;
+  const int k = ev.ep_cnt[blockIdx.x];
   if (k >= ev.E) return;
-  if (t < kPongState) ss[t] = state[(size_t)e * kPongState + t];
-  if (t < 64) {
-    const int pick = a2c_rollout_row_streamed<AMAX, true>(ha, e, t, ha.w_v, ha.w, ev.greedy,
-                                                          ev.tr_logits ? ev.tr_logits + (size_t)e * ha.A : nullptr);
-    if (t == 0) pick_s = pick;
-  }
-  __syncthreads();
-  if (t == 0) {
-    PongEnd end;
-    pong_step_state(e, ss, pick_s, rew, done, fin_ret, fin_len, nullptr, key, step_lo, step_hi, max_steps, 0, nullptr,
-                    &end);
-    if (ev.tr_act) {
-      ev.tr_act[e] = pick_s;
-      ev.tr_rew[e] = rew[e];
-      ev.tr_done[e] = end.cause ? 1.f : 0.f;
-    }
-    if (end.cause) {
-      const size_t slot = (size_t)k * N + e;
-      ev.ep_ret[slot] = end.ret;
-      ev.ep_len[slot] = (int32_t)end.len;
-      ev.ep_code[slot] = end.cause;
-      ev.ep_cnt[e] = k + 1;
-      if (k + 1 == ev.E) atomicSub(ev.remaining, 1);
-    }
-  }
-  __syncthreads();
-  if (t < kPongState) state[(size_t)e * kPongState + t] = ss[t];
-  if constexpr (RING) {
-    pong_ring_write(ro, e, N, ss, rows, pong_abs_step(step_lo, step_hi, nullptr));
-    return;
-  }
-  const float* hist = ss + P_HIST;
-  if (t < kPongHW) rows[t] = pong_row_flags(hist, t);
-  __syncthreads();
-  uint8_t* o = obs + (size_t)e * kChunks * 16;
-  for (int q = threadIdx.x; q < kChunks; q += 256)
-    *reinterpret_cast<uint4*>(o + (size_t)q * 16) = pong_render_chunk_rows(hist, rows, q);
+  // known here, so their paths are not compiled in: no reset-all, no accumulators, a host step counter
+  p.reset_all = 0;
+  p.ep_acc = nullptr;
+  p.step_base = nullptr;
+  pong_env_workgroup<RING>(
+      state, p, obs, ro,
+      [&](int e, int t) {
+        pong_head_pick<AMAX, false, true>(ha, e, t, &pick_s, ev.greedy,
+                                          ev.tr_logits ? ev.tr_logits + (size_t)e * ha.A : nullptr);
+      },
+      [&](int) { return pick_s; },
+      [&](int e, int a, const PongEnd& end) {
+        if (ev.tr_act) {
+          ev.tr_act[e] = a;
+          ev.tr_rew[e] = p.rew[e];
+          ev.tr_done[e] = end.cause ? 1.f : 0.f;
+        }
+        if (end.cause) {
+          const size_t slot = (size_t)k * N + e;
+          ev.ep_ret[slot] = end.ret;
+          ev.ep_len[slot] = (int32_t)end.len;
+          ev.ep_code[slot] = end.cause;
+          ev.ep_cnt[e] = k + 1;
+          if (k + 1 == ev.E) atomicSub(ev.remaining, 1);
+        }
+      });
 }
 }  // namespace rrl
 
 using namespace rrl;
+
+static PongStepArgs step_args(float* rew, float* done, float* fin_ret, float* fin_len, float* ep_acc,
+                              unsigned long long seed, unsigned long long step, const unsigned long long* step_base,
+                              int max_steps, int reset_all) {
+  return {rew, done, fin_ret, fin_len, ep_acc, make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)),
+          (uint32_t)step, (uint32_t)(step >> 32), max_steps, reset_all, step_base};
+}
 
 extern "C" {
 
@@ -451,11 +418,9 @@ int rrl_pong_state_size() { return kPongState; }
 int rrl_pong_step(float* state, const int32_t* act, float* rew, float* done, float* fin_ret, float* fin_len,
                   float* ep_acc, int N, unsigned long long seed, unsigned long long step,
                   const unsigned long long* step_base, int max_steps, int reset_all, float* hist_out, void* stream_) {
-  hipStream_t st = (hipStream_t)stream_;
-  const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
-  hipLaunchKernelGGL(pong_step_kernel, dim3((N + 255) / 256), dim3(256), 0, st, state, act, rew, done, fin_ret,
-                     fin_len, ep_acc, N, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, reset_all,
-                     step_base, hist_out);
+  const PongStepArgs p = step_args(rew, done, fin_ret, fin_len, ep_acc, seed, step, step_base, max_steps, reset_all);
+  hipLaunchKernelGGL(pong_step_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream_, state, act, p, N,
+                     hist_out);
   return (int)hipGetLastError();
 }
 
@@ -464,19 +429,15 @@ int rrl_pong_step_render(float* state, const int32_t* act, float* rew, float* do
                          float* ep_acc, uint8_t* obs, int N, unsigned long long seed, unsigned long long step,
                          const unsigned long long* step_base, int max_steps, int reset_all, uint8_t* frames,
                          int32_t* fidx, int R, void* stream_) {
-  hipStream_t st = (hipStream_t)stream_;
   if (N < 1) return 0;
   if (frames && (!fidx || R < 5)) return -1;
-  const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
+  const PongStepArgs p = step_args(rew, done, fin_ret, fin_len, ep_acc, seed, step, step_base, max_steps, reset_all);
   const RingOut ro{frames, fidx, R};
-  if (frames)
-    hipLaunchKernelGGL(pong_step_render_kernel<true>, dim3(N), dim3(256), 0, st, state, act, rew, done, fin_ret, fin_len,
-                       ep_acc, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, reset_all, step_base, ro);
-  else
-    hipLaunchKernelGGL(pong_step_render_kernel<false>, dim3(N), dim3(256), 0, st, state, act, rew, done, fin_ret, fin_len,
-                       ep_acc, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, reset_all, step_base, ro);
+  const auto kernel = frames ? pong_step_render_kernel<true> : pong_step_render_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(N), dim3(256), 0, (hipStream_t)stream_, state, act, p, step_base, obs, ro);
   return (int)hipGetLastError();
 }
+
 
 // the ring rebuilt from the env state (restore): frames of steps st - 3 .. st and fidx [N][4]
 int rrl_pong_ring_fill(float* state, uint8_t* frames, int32_t* fidx, int N, int R, unsigned long long step,
@@ -505,14 +466,12 @@ int rrl_pong_render_hist(const float* hist, uint8_t* obs, int N, void* stream_) 
 
 int rrl_pong_render(const float* state, uint8_t* obs, int N, void* stream_) {
   hipStream_t st = (hipStream_t)stream_;
-  const size_t t = (size_t)N * (kPongHW * kPongHW * 4 / 16);
+  const size_t t = (size_t)N * kPongChunks;
   hipLaunchKernelGGL(pong_render_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, st, state, obs, N);
   return (int)hipGetLastError();
 }
-
-
 // Fused rollout step: head (from the fc split-K partials part[splits][N][512]) + env step +
-// render.  head_params = [A x 512 policy rows | A biases | 512 value row | value bias].
+// render.  head_params: see head_args (a2c_head.h).
 int rrl_pong_head_step_render(const float* part, int splits, const float* fc_b, const float* head_params, int A,
                               uint16_t* h_out, int32_t* act, float* logp, float* value, unsigned long long sample_seed,
                               unsigned long long sample_step, const unsigned long long* sample_base, float* state,
@@ -522,39 +481,21 @@ int rrl_pong_head_step_render(const float* part, int splits, const float* fc_b, 
                               int R, void* stream_) {
   if (N < 1 || A < 1 || A > 8 || splits < 1 || !part || !fc_b || !h_out) return -1;
   if (frames && (!fidx || R < 5)) return -1;
-  const RingOut ro{frames, fidx, R};
-  HeadArgs a = {};
+  HeadArgs a = head_args(head_params, A, N, sample_seed, sample_step, sample_base);
   a.part = part;
   a.splits = splits;
   a.fc_b = fc_b;
   a.h_out = h_out;
-  a.w = head_params;
-  a.bias = head_params + A * kHeadF;
-  a.w_v = a.bias + A;
-  a.b_v = a.w_v + kHeadF;
-  a.B = N;
-  a.A = A;
   a.act = act;
   a.logp = logp;
   a.value = value;
-  a.seed_lo = (uint32_t)sample_seed;
-  a.seed_hi = (uint32_t)(sample_seed >> 32);
-  a.step_lo = (uint32_t)sample_step;
-  a.step_hi = (uint32_t)(sample_step >> 32);
-  a.step_base = sample_base;
-  const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
+  const PongStepArgs p = step_args(rew, done, fin_ret, fin_len, ep_acc, seed, step, step_base, max_steps, 0);
+  const RingOut ro{frames, fidx, R};
   const char* wl_env = getenv("RRL_PONG_HEAD_WLDS");
-  if (frames) {  // frame ring: one new frame per env
-    hipLaunchKernelGGL((pong_head_step_render_kernel<8, false, true>), dim3(N), dim3(256), 0, (hipStream_t)stream_, a, state,
-                       rew, done, fin_ret, fin_len, ep_acc, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps,
-                       step_base, ro);
-  } else if (wl_env && wl_env[0] == '1') {  // the head weights through LDS (A/B)
-    hipLaunchKernelGGL((pong_head_step_render_kernel<8, true>), dim3(N), dim3(256), 0, (hipStream_t)stream_, a, state, rew, done,
-                       fin_ret, fin_len, ep_acc, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, step_base, ro);
-  } else {
-    hipLaunchKernelGGL((pong_head_step_render_kernel<8, false>), dim3(N), dim3(256), 0, (hipStream_t)stream_, a, state, rew, done,
-                       fin_ret, fin_len, ep_acc, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, step_base, ro);
-  }
+  const auto kernel = frames                       ? pong_head_step_render_kernel<8, false, true>  // one new frame per env
+                      : wl_env && wl_env[0] == '1' ? pong_head_step_render_kernel<8, true>  // the head weights through LDS (A/B)
+                                                   : pong_head_step_render_kernel<8, false>;
+  hipLaunchKernelGGL(kernel, dim3(N), dim3(256), 0, (hipStream_t)stream_, a, state, p, step_base, obs, ro);
   return (int)hipGetLastError();
 }
 
@@ -576,29 +517,15 @@ int rrl_pong_eval_step(const float* part, int splits, const float* fc_b, const f
   if (ntr != 0 && ntr != 4) return -1;
   if (E < 1 || max_steps < 1 || (long long)E * max_steps >= (1ll << 31)) return -2;
   if (A > 8) return -3;
-  const RingOut ro{frames, fidx, R};
-  HeadArgs a = {};
+  HeadArgs a = head_args(head_params, A, N, sample_seed, sample_step, nullptr);
   a.part = part;
   a.splits = splits;
   a.fc_b = fc_b;
-  a.w = head_params;
-  a.bias = head_params + A * kHeadF;
-  a.w_v = a.bias + A;
-  a.b_v = a.w_v + kHeadF;
-  a.B = N;
-  a.A = A;
-  a.seed_lo = (uint32_t)sample_seed;
-  a.seed_hi = (uint32_t)(sample_seed >> 32);
-  a.step_lo = (uint32_t)sample_step;
-  a.step_hi = (uint32_t)(sample_step >> 32);
   const EvalOut ev{ep_cnt, ep_ret, ep_len, ep_code, remaining, E, greedy ? 1 : 0, tr_act, tr_logits, tr_rew, tr_done};
-  const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
-  if (frames)
-    hipLaunchKernelGGL((pong_eval_step_kernel<8, true>), dim3(N), dim3(256), 0, (hipStream_t)stream_, a, ev, state, rew, done,
-                       fin_ret, fin_len, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, ro);
-  else
-    hipLaunchKernelGGL((pong_eval_step_kernel<8, false>), dim3(N), dim3(256), 0, (hipStream_t)stream_, a, ev, state, rew, done,
-                       fin_ret, fin_len, obs, key, (uint32_t)step, (uint32_t)(step >> 32), max_steps, ro);
+  const PongStepArgs p = step_args(rew, done, fin_ret, fin_len, nullptr, seed, step, nullptr, max_steps, 0);
+  const RingOut ro{frames, fidx, R};
+  const auto kernel = frames ? pong_eval_step_kernel<8, true> : pong_eval_step_kernel<8, false>;
+  hipLaunchKernelGGL(kernel, dim3(N), dim3(256), 0, (hipStream_t)stream_, a, ev, state, p, obs, ro);
   return (int)hipGetLastError();
 }
 

@@ -58,6 +58,50 @@ RRL_DEV uint4 pong_render_chunk(const float* h, int q) {
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// The row-only half of pong_render_chunk, once per image row y (84 per env instead of once per
+// chunk: 21 chunks share a row): bit f = ball on the row in frame f, 4 + f = agent paddle,
+// 8 + f = opponent paddle, 12 = wall.  Same float comparisons, so the render stays bitwise.
+RRL_DEV uint32_t pong_row_flags(const float* h, int y) {
+  const float fy = (float)y + 0.5f;
+  uint32_t m = (fy < kTop || fy >= kBot) ? (1u << 12) : 0u;
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const float by = h[4 * f + 1], pa = h[4 * f + 2], po = h[4 * f + 3];
+    if (fy >= by && fy < by + kBall) m |= 1u << f;
+    if (fabsf(fy - pa) < kPadHalf) m |= 1u << (4 + f);
+    if (fabsf(fy - po) < kPadHalf) m |= 1u << (8 + f);
+  }
+  return m;
+}
+
+// pong_render_chunk from the per-row flags: an unlit row (most of the screen) is one LDS read
+// and a constant; lit rows keep only the per-pixel x tests.
+RRL_DEV uint4 pong_render_chunk_rows(const float* h, const uint32_t* rows, int q) {
+  const int a = q / 84, rem = q - a * 84, c = rem >> 2, dy = rem & 3;
+  const uint32_t m = rows[4 * a + dy];
+  const bool wall = (m >> 12) & 1u;
+  if ((m & 0xfffu) == 0u) {
+    const uint32_t v = wall ? 0x64646464u : 0u;
+    return make_uint4(v, v, v, v);
+  }
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const float bx = h[4 * f];
+    const bool b_on = (m >> f) & 1u, pa_on = (m >> (4 + f)) & 1u, po_on = (m >> (8 + f)) & 1u;
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+      const float fx = (float)(4 * c + px) + 0.5f;
+      uint32_t v = wall ? 100u : 0u;
+      if (pa_on && fx >= kAgentX && fx < kAgentX + kPadW) v = 255u;
+      if (po_on && fx >= kOppX && fx < kOppX + kPadW) v = 255u;
+      if (b_on && fx >= bx && fx < bx + kBall) v = 255u;
+      w[px] |= v << (8 * f);
+    }
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // ----------------------------------------------------------------------------- frame ring
 // The 4-frame stack of consecutive observations shares 3 frames, so the ring path renders ONE
 // frame per env step into a frame store and describes an observation by the store rows of its 4

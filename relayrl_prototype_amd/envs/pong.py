@@ -268,21 +268,25 @@ class DevicePong:
     def advance(self, k: int):
         self.h.counter_add(self.step_t, int(k))
 
+    @staticmethod
+    def _picture(obs_out, hist_out, ring):
+        """The keyword arguments that tell a step launch where to draw: the frame ring (ONE new frame,
+        7 KB instead of the 28 KB stack, its frame rows to ``obs_out``), the frame histories alone
+        (one thread per env, no render), or the new 4-frame stack (one workgroup per env)."""
+        if ring is not None:
+            return {"obs": None, "frames": ring.frames, "fidx": obs_out, "ring_slots": ring.R}
+        if hist_out is not None:
+            return {"obs": None, "hist": hist_out}
+        return {"obs": obs_out}
+
     def reset(self, obs_out: torch.Tensor = None, hist_out: torch.Tensor = None, ring=None):
         """Reset every env; the first observation is rendered into ``obs_out`` ([N, 21, 21, 64]) or,
         for the fused-render path, only its frame history goes to ``hist_out`` ([N, 16]); ``ring``
         (a ``FrameRing`` and its fidx row [N, 4]): the reset frame into the ring."""
-        if ring is not None:
-            fr, fidx = ring
-            self.h.pong_step(self.state, self._dummy_act, self.rew, self.done, self.fin_ret, self.fin_len, None,
-                             self.N, self.seed, 0, self.max_steps, True, self.step_t, frames=fr.frames, fidx=fidx,
-                             ring_slots=fr.R)
-        elif hist_out is not None:
-            self.h.pong_step(self.state, self._dummy_act, self.rew, self.done, self.fin_ret, self.fin_len, None,
-                             self.N, self.seed, 0, self.max_steps, True, self.step_t, hist=hist_out)
-        else:
-            self.h.pong_step(self.state, self._dummy_act, self.rew, self.done, self.fin_ret, self.fin_len, None,
-                             self.N, self.seed, 0, self.max_steps, True, self.step_t, obs=obs_out)
+        fr, fidx = ring if ring is not None else (None, None)
+        self.h.pong_step(self.state, self._dummy_act, self.rew, self.done, self.fin_ret, self.fin_len, None,
+                         self.N, self.seed, 0, self.max_steps, True, self.step_t,
+                         **self._picture(obs_out if ring is None else fidx, hist_out, fr))
         self.advance(1)
 
     def ring_fill(self, ring, fidx: torch.Tensor):
@@ -306,11 +310,11 @@ class DevicePong:
         ([N, 4] int32)."""
         rew = self.rew if rew_out is None else rew_out
         done = self.done if done_out is None else done_out
-        rk = {} if ring is None else {"frames": ring.frames, "fidx": obs_out, "ring_slots": ring.R}
         self.h.pong_head_step(part, int(splits), fc_b, head_params, int(A), h_out, act_out, logp_out, value_out,
                               int(sample_seed), int(sample_step), sample_base, self.state, rew, done, self.fin_ret,
-                              self.fin_len, self.ep_acc, None if ring is not None else obs_out, self.N, self.seed,
-                              0 if offset is None else int(offset), self.step_t, self.max_steps, **rk)
+                              self.fin_len, self.ep_acc, N=self.N, seed=self.seed,
+                              step=0 if offset is None else int(offset), step_base=self.step_t,
+                              max_steps=self.max_steps, **self._picture(obs_out, None, ring))
         if offset is None:
             self.advance(1)
         return rew, done
@@ -330,13 +334,13 @@ class DevicePong:
         step, written for the envs that stepped.  There is no CPU fallback."""
         rew = self.rew if rew_out is None else rew_out
         done = self.done if done_out is None else done_out
-        rk = {} if ring is None else {"frames": ring.frames, "fidx": obs_out, "ring_slots": ring.R}
+        rk = self._picture(obs_out, None, ring)
         if trace is not None:
             rk.update(zip(("tr_act", "tr_logits", "tr_rew", "tr_done"), trace))
         self.h.pong_eval_step(part, int(splits), fc_b, head_params, int(A), bool(greedy), int(sample_seed),
                               int(sample_step), self.state, rew, done, self.fin_ret, self.fin_len,
-                              None if ring is not None else obs_out, self.N, self.seed, int(step), self.max_steps,
-                              int(episodes), ep_cnt, ep_ret, ep_len, ep_code, remaining, **rk)
+                              N=self.N, seed=self.seed, step=int(step), max_steps=self.max_steps, E=int(episodes),
+                              ep_cnt=ep_cnt, ep_ret=ep_ret, ep_len=ep_len, ep_code=ep_code, remaining=remaining, **rk)
         return rew, done
 
     def step(self, act: torch.Tensor, obs_out: torch.Tensor = None, rew_out=None, done_out=None, offset: int = None,
@@ -348,16 +352,9 @@ class DevicePong:
         ``FrameRing``): one new frame per env into the ring, the frame rows to ``obs_out`` ([N, 4])."""
         rew = self.rew if rew_out is None else rew_out
         done = self.done if done_out is None else done_out
-        if ring is not None:  # physics + ONE new frame (7 KB instead of the 28 KB stack)
-            self.h.pong_step(self.state, act, rew, done, self.fin_ret, self.fin_len, self.ep_acc, self.N, self.seed,
-                             0 if offset is None else int(offset), self.max_steps, False, self.step_t,
-                             frames=ring.frames, fidx=obs_out, ring_slots=ring.R)
-        elif hist_out is not None:  # physics (one thread per env) + the 64-byte history row
-            self.h.pong_step(self.state, act, rew, done, self.fin_ret, self.fin_len, self.ep_acc, self.N, self.seed,
-                             0 if offset is None else int(offset), self.max_steps, False, self.step_t, hist=hist_out)
-        else:  # physics + render of the new 4-frame stack in one launch (one workgroup per env)
-            self.h.pong_step(self.state, act, rew, done, self.fin_ret, self.fin_len, self.ep_acc, self.N, self.seed,
-                             0 if offset is None else int(offset), self.max_steps, False, self.step_t, obs=obs_out)
+        self.h.pong_step(self.state, act, rew, done, self.fin_ret, self.fin_len, self.ep_acc, self.N, self.seed,
+                         0 if offset is None else int(offset), self.max_steps, False, self.step_t,
+                         **self._picture(obs_out, hist_out, ring))
         if offset is None:
             self.advance(1)
         return rew, done
