@@ -14,6 +14,12 @@ One JSON line:
   uses (the value-grad mode switched to 0 for the reading): the two share everything but the head.
 
     python benchmarks/dqn_bench.py --out profiles/dqn_bench.jsonl
+
+``--prioritized`` adds, from the same process, the ``cartpole-dqn-per`` preset (prioritised replay):
+``per_epoch_us`` / ``per_env_steps_per_s`` / ``per_grad_steps_per_s`` beside the uniform figures, and the
+microseconds per launch of ``per_insert``, ``dqn_targets_per``, ``mlp_grad_q_td_weighted`` and ``per_update``
+(``per_insert`` and ``per_update`` are one workgroup each: their time is latency, not throughput).  The
+line goes to ``profiles/dqn_per_bench.jsonl`` unless ``--out`` names another file.
 """
 import argparse
 import json
@@ -41,6 +47,53 @@ def event_us(fn, iters, reps):
     return round(statistics.median(out), 3), round(min(out), 3), round(max(out), 3)
 
 
+def per_records(a, dev, event_us):
+    """The prioritised preset: epoch wall clock and the four launches prioritised replay adds or changes."""
+    from relayrl_prototype_amd.ops import GradHead, dqn_targets, mlp_grad, per_insert, per_update
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    cfg = DQNConfig(**PRESETS["cartpole-dqn-per"].overrides)
+    tr = DQNTrainer(cfg, device=dev)
+    for _ in range(a.warmup):
+        tr.train_epoch()
+    assert tr.updates > 0, "the warm-up must reach learning_starts"
+    torch.cuda.synchronize()
+    u0, t0 = tr.updates, time.perf_counter()
+    for _ in range(a.epochs):
+        tr.train_epoch()
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    N, T, B, C = cfg.num_envs, cfg.rollout_len, cfg.batch_size, cfg.buffer_slots
+    rec = dict(per_preset="cartpole-dqn-per", per_alpha=cfg.per_alpha, per_tree_leaves=tr.per.P2,
+               per_env_steps_per_s=round(a.epochs * N * T / el, 1),
+               per_grad_steps_per_s=round((tr.updates - u0) / el, 1), per_epoch_us=round(1e6 * el / a.epochs, 2))
+    filled = min(tr.slots_written, C) * N
+
+    def insert():  # the same slots every time: timing only
+        per_insert(tr.per, C, N, T, 0)
+
+    def targets():
+        dqn_targets(tr.q.params, tr.target, cfg.hidden, tr.A, tr.ring, filled, cfg.gamma, cfg.double_q, tr.sample_seed,
+                    7, B, tree=tr.per.tree, beta=0.7, out=(tr.Xb, tr.act_b, tr.y, tr.idx, tr.w, tr.wmax))
+
+    def grad_q():
+        mlp_grad(GradHead.Q_TD, tr.q.params, tr.Xb, tr.A, cfg.hidden, act=tr.act_b, ret=tr.y, clip_eps=cfg.huber_delta,
+                 grad_slab=tr.slab, loss_slab=tr.loss, row_w=tr.w, w_norm=tr.wmax, td_abs=tr.td_abs)
+
+    def update():
+        per_update(tr.per, tr.idx, tr.td_abs, cfg.per_alpha, cfg.per_eps)
+
+    for name, fn in (("per_insert", insert), ("dqn_targets_per", targets), ("mlp_grad_q_td_weighted", grad_q),
+                     ("per_update", update)):
+        fn()
+        torch.cuda.synchronize()
+        med, lo, hi = event_us(fn, a.iters, a.reps)
+        rec[name + "_us"] = med
+        rec[name + "_us_range"] = [lo, hi]
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2000)
@@ -49,7 +102,11 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--tag", default="")
     ap.add_argument("--out", default="")
+    ap.add_argument("--prioritized", action="store_true", help="also measure the cartpole-dqn-per preset")
     a = ap.parse_args()
+    if a.prioritized and not a.out:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "dqn_per_bench.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("dqn_bench needs a GPU: a CPU timing says nothing about the MI355X")
     from relayrl_prototype_amd.ops import GradHead, dqn_rollout, dqn_targets, mlp_grad, set_value_grad_mode
@@ -106,6 +163,8 @@ def main():
             rec[name + "_us_range"] = [lo, hi]
     finally:
         set_value_grad_mode(old)
+    if a.prioritized:
+        rec.update(per_records(a, dev, event_us))
     rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
     line = json.dumps(rec)
     print(line, flush=True)

@@ -1,5 +1,6 @@
 // Bindings of the DQN kernels (csrc/kernels/dqn.hip): the epsilon-greedy actor that fills the replay
-// ring and the sample + gather + TD-target kernel.  Every tensor is validated before a launch.
+// ring and the sample + gather + TD-target kernel, uniform and prioritised, and of the priority sum
+// tree (csrc/kernels/per.hip).  Every tensor is validated before a launch.
 #include <tuple>
 
 #include "api.h"
@@ -85,10 +86,94 @@ void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A,
            "dqn_targets");
 }
 
+// ------------------------------------------------------------------ prioritised replay (per.hip)
+int64_t per_tree_leaves(int64_t L) { return rrl_per_tree_leaves((long long)L); }
+
+// tree [2 * P2] for a ring of L rows and a one-float companion (pmax, wmax); returns P2
+int64_t check_tree(const Tensor& tree, const Tensor& one, const char* one_name, int64_t L) {
+  const int64_t P2 = per_tree_leaves(L);
+  TORCH_CHECK(P2 >= 1, "a priority tree needs 1 <= C * N <= 2^30 rows, got ", L);
+  check(tree, "tree", at::kFloat, 2 * P2);
+  TORCH_CHECK(tree.numel() == 2 * P2, "tree must hold 2 * ", P2, " floats for ", L, " rows, has ", tree.numel());
+  check(one, one_name, at::kFloat, 1);
+  return P2;
+}
+
+// Returns the kernel's code for a range that would wrap (-4, nothing written); raises for anything else.
+int64_t per_insert(const Tensor& tree, const Tensor& pmax, int64_t C, int64_t N, int64_t T, int64_t slot0) {
+  TORCH_CHECK(C >= 1 && N >= 1 && T >= 1 && C < (int64_t)INT32_MAX && N < (int64_t)INT32_MAX &&
+                  T < (int64_t)INT32_MAX && slot0 >= 0 && slot0 < (int64_t)INT32_MAX,
+              "C, N, T must be >= 1 and slot0 >= 0, all below 2^31");
+  check_tree(tree, pmax, "pmax", C * N);
+  const int rc = rrl_per_insert(tree.data_ptr<float>(), pmax.data_ptr<float>(), (int)C, (int)N, (int)T, (int)slot0,
+                                cur_stream());
+  if (rc == -4) return rc;
+  check_rc(rc, "per_insert");
+  return 0;
+}
+
+void per_update(const Tensor& tree, const Tensor& pmax, int64_t L, const Tensor& idx, const Tensor& td_abs,
+                double alpha, double prio_eps) {
+  check_tree(tree, pmax, "pmax", L);
+  check(idx, "idx", at::kInt, 1);
+  const int64_t B = idx.numel();
+  TORCH_CHECK(B < (int64_t)INT32_MAX, "batch size out of range");
+  check(td_abs, "td_abs", at::kFloat, B);
+  TORCH_CHECK(alpha >= 0.0 && prio_eps > 0.0, "per_update needs alpha >= 0 and prio_eps > 0");
+  check_rc(rrl_per_update(tree.data_ptr<float>(), pmax.data_ptr<float>(), idx.data_ptr<int>(),
+                          td_abs.data_ptr<float>(), (int)B, (long long)L, (float)alpha, (float)prio_eps, cur_stream()),
+           "per_update");
+}
+
+void dqn_targets_per(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
+                     const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& tree,
+                     int64_t filled, double gamma, bool double_q, double beta, int64_t sample_key, int64_t update,
+                     const Tensor& Xb, const Tensor& act_b, const Tensor& y, const Tensor& idx, const Tensor& w,
+                     const Tensor& wmax) {
+  TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
+  const int64_t D = obs.size(2);
+  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
+  TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
+  TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
+  auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
+  TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
+  TORCH_CHECK(beta > 0.0 && beta <= 1.0, "beta must be in (0, 1], got ", beta);
+  check_tree(tree, wmax, "wmax", C * N);
+  const int64_t P = H * D + H + H * H + H + A * H + A;
+  check(target, "target", at::kFloat, P);
+  const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
+  TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
+  check(y, "y", at::kFloat);
+  const int64_t B = y.numel();
+  TORCH_CHECK(B >= 1 && B * D < (int64_t)INT32_MAX, "batch size out of range");
+  check(Xb, "Xb", at::kFloat, B * D);
+  check(act_b, "act_b", at::kInt, B);
+  check(idx, "idx", at::kInt, B);
+  check(w, "w", at::kFloat, B);
+  check_rc(rrl_dqn_targets_per(on, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
+                               act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(),
+                               tree.data_ptr<float>(), (long long)(C * N), (long long)filled, (int)B, (int)D, (int)A,
+                               (int)H, (float)gamma, double_q ? 1 : 0, (float)beta, (uint64_t)sample_key,
+                               (uint64_t)update, Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(),
+                               idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), grid_cus(),
+                               cur_stream()),
+           "dqn_targets_per");
+}
+
 }  // namespace
 
 void register_dqn_ops(pybind11::module_& m) {
   namespace py = pybind11;
+  m.def("per_tree_leaves", &per_tree_leaves);
+  m.def("per_insert", &per_insert, py::arg("tree"), py::arg("pmax"), py::arg("C"), py::arg("N"), py::arg("T"),
+        py::arg("slot0"));
+  m.def("per_update", &per_update, py::arg("tree"), py::arg("pmax"), py::arg("L"), py::arg("idx"), py::arg("td_abs"),
+        py::arg("alpha"), py::arg("prio_eps"));
+  m.def("dqn_targets_per", &dqn_targets_per, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
+        py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("tree"),
+        py::arg("filled"), py::arg("gamma"), py::arg("double_q"), py::arg("beta"), py::arg("sample_key"),
+        py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("w"),
+        py::arg("wmax"));
   m.def("dqn_rollout_grid", &dqn_rollout_grid);
   m.def("dqn_rollout", &dqn_rollout, py::arg("env"), py::arg("params"), py::arg("H"), py::arg("T"), py::arg("slot0"),
         py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"), py::arg("act"),

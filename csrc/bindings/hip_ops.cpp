@@ -100,7 +100,8 @@ int64_t mlp_grad_slabs(int64_t B) { return rrl_mlp_grad_slabs((int)B, num_cus())
 void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, int64_t H, const OptT& mask,
               const OptT& act, const OptT& actc, const OptT& adv, const OptT& ret, const OptT& logp_old,
               const OptT& adv_stats, double inv_B, double clip_eps, double ent_coef, const Tensor& grad_slab,
-              const Tensor& loss_slab, const OptT& nvalid, const OptT& inv_B_dev) {
+              const Tensor& loss_slab, const OptT& nvalid, const OptT& inv_B_dev, const OptT& row_w,
+              const OptT& w_norm, const OptT& td_abs) {
   check(params, "params", at::kFloat);
   check(X, "X", at::kFloat);
   TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
@@ -134,10 +135,16 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   // device-side batch shape (graph replays with a changing batch): valid rows / 1 / global rows
   const int* nv = opt_ptr<const int>(nvalid, "nvalid", at::kInt, 1);
   const float* ibd = opt_ptr<const float>(inv_B_dev, "inv_B_dev", at::kFloat, 1);
-  const int rc = rrl_mlp_grad((int)head, params.data_ptr<float>(), X.data_ptr<float>(), (int)B, (int)D, (int)A,
-                              (int)H, m, a, ac, ad, rt, lpo, st, (float)inv_B, (float)clip_eps, (float)ent_coef,
-                              grad_slab.data_ptr<float>(), loss_slab.data_ptr<float>(), (int)P, nv, ibd, num_cus(),
-                              cur_stream());
+  // prioritised replay (the Q head only): importance weights, their normaliser, |TD error| out
+  const float* rw = opt_ptr<const float>(row_w, "row_w", at::kFloat, B);
+  const float* wn = opt_ptr<const float>(w_norm, "w_norm", at::kFloat, 1);
+  float* ta = opt_ptr<float>(td_abs, "td_abs", at::kFloat, B);
+  TORCH_CHECK((rw == nullptr) == (wn == nullptr), "row_w and w_norm come together");
+  TORCH_CHECK(qtd || (rw == nullptr && ta == nullptr), "row_w / w_norm / td_abs apply to the Q_TD head only");
+  const int rc = rrl_mlp_grad_weighted((int)head, params.data_ptr<float>(), X.data_ptr<float>(), (int)B, (int)D,
+                                       (int)A, (int)H, m, a, ac, ad, rt, lpo, st, (float)inv_B, (float)clip_eps,
+                                       (float)ent_coef, grad_slab.data_ptr<float>(), loss_slab.data_ptr<float>(),
+                                       (int)P, nv, ibd, rw, wn, ta, num_cus(), cur_stream());
   check_rc(rc, "mlp_grad");
 }
 

@@ -49,6 +49,15 @@ int rrl_mlp_grad(int head, const float* params, const float* X, int B, int D, in
                  const int* act, const float* actc, const float* adv, const float* ret, const float* logp_old,
                  const float* adv_stats, float inv_B, float clip_eps, float ent_coef, float* grad_slab,
                  float* loss_slab, int P, const int* nvalid, const float* inv_B_dev, int num_cu, void* stream);
+// rrl_mlp_grad plus the per-row weights of prioritised replay, read by HEAD_Q_TD alone: with w_i =
+// row_w[i] / *w_norm the row's loss is w_i * huber and its gradient is scaled by w_i; td_abs[i] (may be
+// null) receives |Q(x_i)[act_i] - ret_i| of every valid row.  row_w and w_norm come together or not at
+// all (-1); all three null is rrl_mlp_grad
+int rrl_mlp_grad_weighted(int head, const float* params, const float* X, int B, int D, int A, int H,
+                          const float* mask, const int* act, const float* actc, const float* adv, const float* ret,
+                          const float* logp_old, const float* adv_stats, float inv_B, float clip_eps, float ent_coef,
+                          float* grad_slab, float* loss_slab, int P, const int* nvalid, const float* inv_B_dev,
+                          const float* row_w, const float* w_norm, float* td_abs, int num_cu, void* stream);
 // number of partial-gradient slabs (== grid size) rrl_mlp_grad uses
 int rrl_mlp_grad_slabs(int B, int num_cu);
 // 1 = bf16x6 weight-stationary kernels, 0 = fp32 MFMA; returns the previous mode (-1 queries)
@@ -144,6 +153,34 @@ int rrl_dqn_targets(const float* online, const float* target, const float* obs, 
                     const float* rew, const float* done, long long filled, int B, int D, int A, int H, float gamma,
                     int double_q, uint64_t sample_key, uint64_t update, float* Xb, int* act_b, float* y, int* idx,
                     int num_cu, void* stream);
+// The prioritised form: batch row b descends the sum tree of per.hip (L = the ring's C * N rows, leaf of
+// row r at tree[P2 + r]) with m = (b + u01(philox((b, update, 1), sample_key).x)) * (tree[1] / B), exactly
+// log2(P2) steps `if (m >= left && right > 0) { m -= left; go right } else go left`, and clamps the row to
+// [0, filled - 1].  On top of rrl_dqn_targets' outputs (idx is mandatory) it writes w[b] = (filled * leaf /
+// tree[1])^-beta and *wmax = max_b w[b] (reset by the launcher, a bit-pattern maximum: the same bits every
+// launch).  -1: a null pointer; -2: filled outside [1, L], L < 1 or >= 2^30, or B < 1; -3: as rrl_dqn_targets
+int rrl_dqn_targets_per(const float* online, const float* target, const float* obs, const float* nobs,
+                        const int* act, const float* rew, const float* done, const float* tree, long long L,
+                        long long filled, int B, int D, int A, int H, float gamma, int double_q, float beta,
+                        uint64_t sample_key, uint64_t update, float* Xb, int* act_b, float* y, int* idx, float* w,
+                        float* wmax, int num_cu, void* stream);
+
+// ---- per.hip
+// The priority sum tree of prioritised replay over a ring of L = C * N rows: fp32 tree[2 * P2], P2 =
+// rrl_per_tree_leaves(L) the smallest power of two >= L, root tree[1], leaf of row r tree[P2 + r], and
+// after every launch tree[i] == tree[2i] + tree[2i + 1] (one fp32 add) for every internal node.  Each
+// launch is ONE workgroup that walks the levels bottom-up.  0 for L outside [1, 2^30]
+long long rrl_per_tree_leaves(long long L);
+// leaves of rows [slot0 * N, (slot0 + T) * N) <- *pmax, ancestors refreshed.  The codes of
+// rrl_dqn_rollout: -1 a null pointer; -2 N, T or C below 1 or C * N > 2^30; -4 (nothing written) unless
+// C % T == 0, slot0 % T == 0 and slot0 + T <= C
+int rrl_per_insert(float* tree, const float* pmax, int C, int N, int T, int slot0, void* stream);
+// leaf of every row r in idx[0 .. B) <- max over {b : idx[b] == r} of (td_abs[b] + prio_eps)^alpha (a
+// non-finite td_abs[b], or a power that is not finite, counts as the *pmax of before the launch), *pmax <-
+// max(*pmax, every new leaf), ancestors refreshed.  An idx outside [0, L) is skipped.  -1: a null
+// pointer; -2: B < 1, L outside [1, 2^30], alpha < 0 or prio_eps <= 0
+int rrl_per_update(float* tree, float* pmax, const int* idx, const float* td_abs, int B, long long L, float alpha,
+                   float prio_eps, void* stream);
 
 // ---- cnn.hip (bf16 tensors as uint16_t)
 int rrl_conv_fwd(const void* x, int x_u8, const uint16_t* w, const float* b, uint16_t* y, int N, int H, int W,

@@ -1,6 +1,7 @@
 // DQN on the device: an epsilon-greedy fused actor that writes transitions into a replay ring,
 // and a kernel that samples the ring, gathers the batch and builds the TD targets from a second
-// (target) network.  The Q-learning gradient head lives in mlp_grad.hip (HEAD_Q_TD).
+// (target) network, uniformly or through the priority sum tree of prioritised replay (per.hip).  The
+// Q-learning gradient head lives in mlp_grad.hip (HEAD_Q_TD).
 //
 // The actor is the shared step of actor_step.h, the one the rollout and evaluation kernels are built
 // from: one 16-env tile per wave, the env replica in registers (EnvSlot), the Q-network on fp32 MFMA
@@ -114,6 +115,13 @@ struct DqnTargetArgs {
   int* act_b;   // [B]
   float* y;     // [B]
   int* idx;     // [B] or null
+  // the prioritised instance (PER = true) only
+  const float* tree = nullptr;  // [2 * P2] priority sum tree (per.hip)
+  uint32_t P2 = 0;              // leaves of the tree, a power of two
+  int levels = 0;               // log2(P2)
+  float beta = 0.f;
+  float* w = nullptr;           // [B] importance weights (filled * leaf / total)^-beta
+  int* wmax = nullptr;          // [1] max_b w[b] as float bits, zeroed by the launcher
 };
 
 RRL_DEV uint32_t dqn_sample_row(int b, const DqnTargetArgs& p) {
@@ -135,7 +143,35 @@ RRL_DEV void dqn_q_values(const float* __restrict__ lds, const float* __restrict
   policy_forward<1, HT>(lds, x, (D + 3) >> 2, A, q);
 }
 
-template <int HT>
+// The prioritised draw: batch row b takes the point m = (b + u) * (total / B) of its own stratum of the
+// tree's mass and descends from the root, exactly `levels` steps whatever the tree holds.  Every step is
+// one fp32 operation (the numpy oracle per_sample_rows_ref repeats them bit for bit).  The `r > 0` guard
+// ends the walk on a leaf of positive priority, hence on a written row, whatever rounding did to m; the
+// clamp to [0, filled - 1] keeps a corrupt tree from reading out of bounds.  Counter word 3 = 1: not
+// the uniform sampler's draws.
+RRL_DEV uint32_t per_sample_row(int b, const DqnTargetArgs& p) {
+  const uint4 rnd = philox4x32(make_uint4((uint32_t)b, p.upd_lo, p.upd_hi, 1u), make_uint2(p.key_lo, p.key_hi));
+  const float total = p.tree[1];
+  const float seg = total / (float)p.B;
+  float m = ((float)b + u01(rnd.x)) * seg;
+  uint32_t i = 1;
+  for (int k = 0; k < p.levels; ++k) {
+    const float l = p.tree[2 * (size_t)i], r = p.tree[2 * (size_t)i + 1];
+    if (m >= l && r > 0.f) {
+      m -= l;
+      i = 2 * i + 1;
+    } else {
+      i = 2 * i;
+    }
+  }
+  const uint32_t row = (i & (p.P2 - 1));  // i - P2 for a walk that started at the root
+  return min(row, p.filled - 1u);
+}
+
+// PER = false: the uniform sampler.  PER = true: the rows come from the priority tree, and the kernel
+// also writes the importance weight w[b] and raises *wmax to it (a maximum on the bits of non-negative
+// floats).  With double_q the online pass parks the row in idx[b], so the tree is descended once.
+template <int HT, bool PER>
 __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int l = lane_id();
@@ -148,10 +184,13 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
     for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
       const int b = base + 16 * wave + j;
       const bool ok = b < p.B;
-      const size_t r = ok ? dqn_sample_row(b, p) : 0;
+      const size_t r = ok ? (PER ? per_sample_row(b, p) : dqn_sample_row(b, p)) : 0;
       float q[kMaxAct];
       dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, p.A, q);
-      if (ok && g == 0) p.y[b] = __int_as_float(argmax_first(p.A, q));
+      if (ok && g == 0) {
+        p.y[b] = __int_as_float(argmax_first(p.A, q));
+        if (PER) p.idx[b] = (int)r;
+      }
     }
     __syncthreads();  // every wave is done with the online image
   }
@@ -160,7 +199,12 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
   for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
     const int b = base + 16 * wave + j;
     const bool ok = b < p.B;
-    const size_t r = ok ? dqn_sample_row(b, p) : 0;
+    size_t r = 0;
+    if (ok) {
+      if (!PER) r = dqn_sample_row(b, p);
+      else if (p.double_q) r = min((uint32_t)p.idx[b], p.filled - 1u);  // parked by this wave's lane g = 0
+      else r = per_sample_row(b, p);
+    }
     float q[kMaxAct];
     dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, p.A, q);
     if (ok) {
@@ -171,6 +215,13 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
         p.y[b] = p.rew[r] + p.gamma * boot * pick_logit(p.A, q, astar);
         p.act_b[b] = p.act[r];
         if (p.idx != nullptr) p.idx[b] = (int)r;
+        if (PER) {
+          const float leaf = p.tree[p.P2 + r], total = p.tree[1];
+          // a walk on a sound tree ends on a positive leaf; anything else weighs like the uniform sampler
+          const float wb = (leaf > 0.f && total > 0.f) ? powf((float)p.filled * leaf / total, -p.beta) : 1.f;
+          p.w[b] = wb;
+          atomicMax(p.wmax, __float_as_int(wb));
+        }
       }
     }
   }
@@ -215,13 +266,19 @@ extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H
   });
 }
 
-template <int HT>
+template <int HT, bool PER = false>
 static int launch_dqn_targets(const DqnTargetArgs& a, int grid, hipStream_t s) {
   using L = LdsNet<1, HT>;
-  raise_lds_limit<dqn_targets_kernel<HT>>();
+  raise_lds_limit<dqn_targets_kernel<HT, PER>>();
   const size_t bytes = (size_t)L::floats(a.A) * sizeof(float);
-  hipLaunchKernelGGL((dqn_targets_kernel<HT>), dim3(grid), dim3(256), bytes, s, a);
+  hipLaunchKernelGGL((dqn_targets_kernel<HT, PER>), dim3(grid), dim3(256), bytes, s, a);
   return (int)hipGetLastError();
+}
+
+static int dqn_targets_grid(int B, int num_cu) {
+  int grid = (B + 63) / 64;
+  const int cap = num_cu > 0 ? num_cu : 256;
+  return grid > cap ? cap : grid;
 }
 
 extern "C" int rrl_dqn_targets(const float* online, const float* target, const float* obs, const float* nobs,
@@ -234,9 +291,35 @@ extern "C" int rrl_dqn_targets(const float* online, const float* target, const f
   DqnTargetArgs a{online, target, obs, nobs, act, rew, done, B, D, A, (uint32_t)filled, gamma, double_q ? 1 : 0,
                   (uint32_t)sample_key, (uint32_t)(sample_key >> 32), (uint32_t)update, (uint32_t)(update >> 32),
                   Xb, act_b, y, idx};
-  int grid = (B + 63) / 64;
-  const int cap = num_cu > 0 ? num_cu : 256;
-  if (grid > cap) grid = cap;
+  const int grid = dqn_targets_grid(B, num_cu);
   hipStream_t s = (hipStream_t)stream;
   return H == 128 ? launch_dqn_targets<8>(a, grid, s) : launch_dqn_targets<4>(a, grid, s);
+}
+
+extern "C" int rrl_dqn_targets_per(const float* online, const float* target, const float* obs, const float* nobs,
+                                   const int* act, const float* rew, const float* done, const float* tree,
+                                   long long L, long long filled, int B, int D, int A, int H, float gamma,
+                                   int double_q, float beta, uint64_t sample_key, uint64_t update, float* Xb,
+                                   int* act_b, float* y, int* idx, float* w, float* wmax, int num_cu,
+                                   void* stream) {
+  if (!target || (double_q && !online) || !obs || !nobs || !act || !rew || !done || !Xb || !act_b || !y) return -1;
+  if (!tree || !idx || !w || !wmax) return -1;
+  const long long P2 = rrl_per_tree_leaves(L);
+  if (P2 < 1 || filled < 1 || filled > L || B < 1) return -2;
+  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A > kMaxAct) return -3;
+  DqnTargetArgs a{online, target, obs, nobs, act, rew, done, B, D, A, (uint32_t)filled, gamma, double_q ? 1 : 0,
+                  (uint32_t)sample_key, (uint32_t)(sample_key >> 32), (uint32_t)update, (uint32_t)(update >> 32),
+                  Xb, act_b, y, idx};
+  a.tree = tree;
+  a.P2 = (uint32_t)P2;
+  for (a.levels = 0; (1ll << a.levels) < P2; ++a.levels) {
+  }
+  a.beta = beta;
+  a.w = w;
+  a.wmax = reinterpret_cast<int*>(wmax);
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(wmax, 0, sizeof(float), s);  // +0.0f: below every weight
+  if (e != hipSuccess) return (int)e;
+  const int grid = dqn_targets_grid(B, num_cu);
+  return H == 128 ? launch_dqn_targets<8, true>(a, grid, s) : launch_dqn_targets<4, true>(a, grid, s);
 }

@@ -31,6 +31,11 @@ struct GradArgs {
   const int* nvalid = nullptr;
   const float* inv_B_dev = nullptr;
   float* vout = nullptr;  // value forward (value_grad.hip FWD instance): V of every row
+  // Prioritised replay (HEAD_Q_TD of mlp_grad.hip only): row i weighs row_w[i] / *w_norm in the loss
+  // and the gradient, and td_abs[i] receives |Q - target| of every valid row.  Null = unweighted.
+  const float* row_w = nullptr;   // [B]
+  const float* w_norm = nullptr;  // [1]
+  float* td_abs = nullptr;        // [B]
 };
 
 // Weight-stationary bf16x6 gradient kernels (value_grad.hip): value head for H = 128,

@@ -100,7 +100,11 @@ RRL_DEV void stage_x_tiles(float* __restrict__ St, int wave, const floatx4 (&v)[
 // the VALU in registers (dout x h2 outer products, reduced once at the end) instead of
 // a 16-row MFMA tile that would be 1/16 (value) or 1/8 (CartPole policy) useful; this
 // also removes one staging phase and two workgroup barriers per 64-row slab.
-template <int DT, int HT, int HEAD, int A3, int EARLY>
+//
+// WEIGHTED (HEAD_Q_TD only): the prioritised-replay instance.  Row i weighs row_w[i] / *w_norm in
+// the loss and in dq (row_w may be null: weight 1), and td_abs[i] (may be null) receives |diff| of
+// every valid row.  The unweighted instance reads none of the three pointers.
+template <int DT, int HT, int HEAD, int A3, int EARLY, bool WEIGHTED = false>
 __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using L = LdsNet<DT, HT>;
@@ -238,14 +242,21 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
       const float diff = valid ? q - p.ret[row] : 0.f;
       const float delta = p.clip_eps;
       const float ad = fabsf(diff);
-      const float dq = (valid ? invB : 0.f) * fminf(fmaxf(diff, -delta), delta);
+      float dq = (valid ? invB : 0.f) * fminf(fmaxf(diff, -delta), delta);
+      float loss_i = ad <= delta ? 0.5f * diff * diff : delta * (ad - 0.5f * delta);
+      if (WEIGHTED && p.row_w != nullptr) {  // prioritised replay: the importance weight of the row
+        const float wi = valid ? p.row_w[row] / *p.w_norm : 0.f;
+        dq = (valid ? invB : 0.f) * wi * fminf(fmaxf(diff, -delta), delta);
+        loss_i = wi * loss_i;
+      }
 #pragma unroll
       for (int a = 0; a < kMaxAct; ++a)
         if (a < A) dout[a] = (a == act) ? dq : 0.f;
       if (count) {
-        s_loss += ad <= delta ? 0.5f * diff * diff : delta * (ad - 0.5f * delta);
+        s_loss += loss_i;
         s_val += q;
         s_cnt += 1.f;
+        if (WEIGHTED && p.td_abs != nullptr) p.td_abs[row] = ad;
       }
     } else {  // Gaussian heads
       float adv = valid ? p.adv[row] : 0.f;
@@ -459,7 +470,7 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
 
 using namespace rrl;
 
-template <int DT, int HT, int HEAD, int A3, int EARLY>
+template <int DT, int HT, int HEAD, int A3, int EARLY, bool WEIGHTED = false>
 static int launch_grad_v(const GradArgs& a, int grid, hipStream_t s) {
   using L = LdsNet<DT, HT>;
   const int A = (HEAD == HEAD_VALUE_MSE) ? 1 : a.A;
@@ -468,16 +479,19 @@ static int launch_grad_v(const GradArgs& a, int grid, hipStream_t s) {
   if (bytes > 163840) return -4;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)mlp_grad_kernel<DT, HT, HEAD, A3, EARLY>,
+    (void)hipFuncSetAttribute((const void*)mlp_grad_kernel<DT, HT, HEAD, A3, EARLY, WEIGHTED>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
     attr_set = true;
   }
-  hipLaunchKernelGGL((mlp_grad_kernel<DT, HT, HEAD, A3, EARLY>), dim3(grid), dim3(256), bytes, s, a);
+  hipLaunchKernelGGL((mlp_grad_kernel<DT, HT, HEAD, A3, EARLY, WEIGHTED>), dim3(grid), dim3(256), bytes, s, a);
   return (int)hipGetLastError();
 }
 
 template <int DT, int HT, int HEAD, int A3>
 static int launch_grad(const GradArgs& a, int grid, hipStream_t s) {
+  if constexpr (HEAD == HEAD_Q_TD) {  // prioritised replay: the weighted instance
+    if (a.row_w != nullptr || a.td_abs != nullptr) return launch_grad_v<DT, HT, HEAD, A3, 1, true>(a, grid, s);
+  }
   return launch_grad_v<DT, HT, HEAD, A3, 1>(a, grid, s);
 }
 
@@ -526,11 +540,27 @@ extern "C" int rrl_mlp_grad(int head, const float* params, const float* X, int B
                             float inv_B, float clip_eps, float ent_coef, float* grad_slab,
                             float* loss_slab, int P, const int* nvalid, const float* inv_B_dev, int num_cu,
                             void* stream) {
+  return rrl_mlp_grad_weighted(head, params, X, B, D, A, H, mask, act, actc, adv, ret, logp_old, adv_stats, inv_B,
+                               clip_eps, ent_coef, grad_slab, loss_slab, P, nvalid, inv_B_dev, nullptr, nullptr,
+                               nullptr, num_cu, stream);
+}
+
+extern "C" int rrl_mlp_grad_weighted(int head, const float* params, const float* X, int B, int D, int A, int H,
+                                     const float* mask, const int* act, const float* actc, const float* adv,
+                                     const float* ret, const float* logp_old, const float* adv_stats, float inv_B,
+                                     float clip_eps, float ent_coef, float* grad_slab, float* loss_slab, int P,
+                                     const int* nvalid, const float* inv_B_dev, const float* row_w,
+                                     const float* w_norm, float* td_abs, int num_cu, void* stream) {
   if (A < 1 || A > kMaxAct || D < 1 || D > 32) return -2;
+  if ((row_w == nullptr) != (w_norm == nullptr)) return -1;
+  if ((row_w != nullptr || td_abs != nullptr) && head != HEAD_Q_TD) return -1;
   GradArgs a{params, X, B, D, A, mask, act, actc, adv, ret, logp_old, adv_stats, inv_B, clip_eps,
              ent_coef, grad_slab, loss_slab, P};
   a.nvalid = nvalid;
   a.inv_B_dev = inv_B_dev;
+  a.row_w = row_w;
+  a.w_norm = w_norm;
+  a.td_abs = td_abs;
   const int grid = rrl_mlp_grad_slabs(B, num_cu);
   hipStream_t s = (hipStream_t)stream;
   if (head == HEAD_VALUE_MSE && g_value_grad_mode == 1 && value_grad_split_supported(D, H))

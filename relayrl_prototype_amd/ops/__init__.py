@@ -70,8 +70,24 @@ from .mlp import (  # noqa: E402
 from .integrity import payload_checksum, payload_verify  # noqa: E402
 from .evaluate import EvalTrace, evaluate_policy_op  # noqa: E402
 from .dqn import ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_sample_rows_ref, dqn_targets, dqn_targets_ref  # noqa: E402
+from .per import (  # noqa: E402
+    PriorityTree,
+    per_insert,
+    per_sample_rows_ref,
+    per_tree_build,
+    per_tree_leaves,
+    per_update,
+    per_weights_ref,
+)
 
 __all__ = [
+    "PriorityTree",
+    "per_insert",
+    "per_sample_rows_ref",
+    "per_tree_build",
+    "per_tree_leaves",
+    "per_update",
+    "per_weights_ref",
     "payload_checksum",
     "payload_verify",
     "EvalTrace",

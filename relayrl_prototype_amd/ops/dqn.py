@@ -70,12 +70,21 @@ def dqn_sample_rows_ref(seed: int, update: int, B: int, filled: int) -> np.ndarr
 
 @torch.no_grad()
 def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: int, gamma: float, double_q: bool,
-                    seed: int, update: int, B: int, dtype=torch.float32):
+                    seed: int, update: int, B: int, dtype=torch.float32, tree=None, beta: Optional[float] = None):
     """-> ``(Xb [B, D], act_b [B] int32, y [B], idx [B] int64)`` in ``dtype``;
     ``y = rew + gamma * (done == 1 ? 0 : 1) * Q_target(nobs, a*)`` with ``a*`` the lowest-index argmax of the
-    target (``double_q`` false) or online net."""
+    target (``double_q`` false) or online net.  With ``tree`` (the priority sum tree of ops/per.py) the rows
+    are ``per_sample_rows_ref``'s and two more results follow: ``w [B] = (filled * leaf / total)^-beta`` and
+    ``wmax [1]``, its maximum."""
     D = ring.obs.shape[-1]
-    idx = torch.from_numpy(dqn_sample_rows_ref(seed, update, B, filled)).to(ring.obs.device)
+    if tree is None:
+        rows = dqn_sample_rows_ref(seed, update, B, filled)
+    else:
+        from .per import per_sample_rows_ref, per_weights_ref
+
+        rows = per_sample_rows_ref(tree, seed, update, B, filled)
+        w = per_weights_ref(tree, rows, filled, beta, dtype).to(ring.obs.device)
+    idx = torch.from_numpy(rows).to(ring.obs.device)
     obs = ring.obs.reshape(-1, D)[idx]
     nobs = ring.nobs.reshape(-1, D)[idx].to(dtype)
     q_t, _ = ref.trunk(target.to(dtype), nobs, D, H, A)
@@ -83,32 +92,51 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
     astar, _ = ref.greedy_from_logits(sel)
     boot = (ring.done.reshape(-1)[idx] != 1).to(dtype)
     y = ring.rew.reshape(-1)[idx].to(dtype) + gamma * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
-    return obs, ring.act.reshape(-1)[idx].to(torch.int32), y, idx
+    res = (obs, ring.act.reshape(-1)[idx].to(torch.int32), y, idx)
+    return res if tree is None else res + (w, w.max().reshape(1))
 
 
 def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
-                gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32):
+                gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32,
+                tree=None, beta: Optional[float] = None):
     """Sample, gather and TD target in one launch -> ``(Xb, act_b, y, idx)``; ``out`` = the four tensors to
     write into (``idx`` int32 on the GPU, or None to skip it).  CPU tensors take the torch reference in
-    ``dtype``; a GPU tensor without the extension raises."""
+    ``dtype``; a GPU tensor without the extension raises.
+
+    ``tree`` (the ``[2 * P2]`` priority sum tree of ops/per.py) selects the prioritised form: the rows come
+    from the tree, and the result (and ``out``) is ``(Xb, act_b, y, idx, w, wmax)`` with the importance
+    weights ``w [B] = (filled * leaf / total)^-beta`` and ``wmax [1]`` their maximum; ``idx`` is mandatory."""
     from . import use_hip, hip
 
+    per = tree is not None
+    if per and not (beta is not None and 0.0 < beta <= 1.0):
+        raise ValueError(f"the prioritised form needs beta in (0, 1], got {beta}")
     if not use_hip(target):
-        Xb, act_b, y, idx = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype)
+        res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta)
         if out is not None:
-            for dst, src in zip(out, (Xb, act_b, y, idx)):
+            for dst, src in zip(out, res):
                 if dst is not None:
                     dst.copy_(src)
             return out
-        return Xb, act_b, y, idx
+        return res
     dev = target.device
     D = ring.obs.shape[-1]
     if out is None:
         out = (torch.empty(B, D, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
                torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        if per:
+            out += (torch.empty(B, device=dev), torch.empty(1, device=dev))
+    if out[2].numel() != B:
+        raise ValueError(f"y must hold {B} targets, got {out[2].numel()}")
+    if per:
+        Xb, act_b, y, idx, w, wmax = out
+        if idx is None:
+            raise ValueError("the prioritised form writes idx: it cannot be skipped")
+        hip().dqn_targets_per(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act,
+                              ring.rew, ring.done, tree, int(filled), float(gamma), bool(double_q), float(beta),
+                              int(seed), int(update), Xb, act_b, y, idx, w, wmax)
+        return out
     Xb, act_b, y, idx = out
-    if y.numel() != B:
-        raise ValueError(f"y must hold {B} targets, got {y.numel()}")
     hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
                       ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), Xb, act_b, y, idx)
     return out

@@ -130,17 +130,26 @@ def set_value_grad_mode(mode: int) -> int:
 
 def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=None, adv=None, ret=None,
              logp_old=None, adv_stats=None, inv_B: Optional[float] = None, clip_eps: float = 0.2,
-             ent_coef: float = 0.0, grad_slab=None, loss_slab=None, nvalid=None, inv_B_dev=None):
+             ent_coef: float = 0.0, grad_slab=None, loss_slab=None, nvalid=None, inv_B_dev=None, row_w=None,
+             w_norm=None, td_abs=None):
     """Fused forward+backward.  GPU: fills grad_slab [nslab, P] and loss_slab [nslab, 8] and
     returns them; CPU: returns (grad [1, P], loss stats [1, 8]) computed with autograd.
 
     ``nvalid`` (int32 [1]) / ``inv_B_dev`` (fp32 [1]): the batch shape read from device memory
     -- rows >= nvalid are inert and inv_B_dev replaces inv_B -- so a captured graph can replay
-    a batch whose valid row count changes (agent rows folded into a fixed capacity)."""
+    a batch whose valid row count changes (agent rows folded into a fixed capacity).
+
+    ``row_w`` [B] / ``w_norm`` [1] / ``td_abs`` [B] (the Q_TD head, prioritised replay): row i weighs
+    ``row_w[i] / w_norm`` in the loss and the gradient, and ``td_abs[i]`` receives ``|Q - ret|`` of every
+    valid row (rows past ``nvalid`` are left alone)."""
     X = X.contiguous().float()
     B = X.shape[0]
     if inv_B is None:
         inv_B = 1.0 / max(B, 1)
+    if (row_w is None) != (w_norm is None):
+        raise ValueError("row_w and w_norm come together")
+    if int(head) != GradHead.Q_TD and (row_w is not None or td_abs is not None):
+        raise ValueError("row_w / w_norm / td_abs apply to the Q_TD head only")
     h = _hip_for(X)
     if h is None and (nvalid is not None or inv_B_dev is not None):
         n = B if nvalid is None else int(nvalid.reshape(-1)[0])
@@ -150,10 +159,12 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
             return None if t is None else t[:n]
 
         return mlp_grad(head, params, X[:n], A, H, cut(mask), cut(act), cut(actc), cut(adv), cut(ret), cut(logp_old),
-                        adv_stats, ib, clip_eps, ent_coef)
+                        adv_stats, ib, clip_eps, ent_coef, row_w=cut(row_w), w_norm=w_norm, td_abs=cut(td_abs))
     if h is None:
         g, st = ref.mlp_grad_ref(int(head), params, X, A, H, mask, act, actc, adv, ret, logp_old, adv_stats,
-                                 inv_B, clip_eps, ent_coef)
+                                 inv_B, clip_eps, ent_coef, row_w=row_w, w_norm=w_norm)
+        if td_abs is not None:
+            td_abs.copy_(st["td_abs"])
         ls = torch.zeros(1, 8)
         ls[0, 0] = st.get("loss", 0.0)
         ls[0, 1] = st.get("entropy", 0.0)
@@ -175,6 +186,8 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
     chunks = grad_chunks(B)
     if nvalid is not None and len(chunks) > 1:
         raise ValueError("a device-side row count needs a single-launch batch (< 2^25 rows)")
+    if td_abs is not None and not (td_abs.is_contiguous() and td_abs.dtype == torch.float32):
+        raise ValueError("td_abs is written in place: it must be a contiguous float32 tensor")
     for lo, hi in chunks:
         whole = lo == 0 and hi == B
 
@@ -184,7 +197,7 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
         n = int(h.mlp_grad_slabs(hi - lo))
         h.mlp_grad(int(head), params, rows(X), A, H, rows(mask), rows(act), rows(actc), rows(adv), rows(ret),
                    rows(logp_old), adv_stats, float(inv_B), float(clip_eps), float(ent_coef), grad_slab[off:off + n],
-                   loss_slab[off:off + n], nvalid, inv_B_dev)
+                   loss_slab[off:off + n], nvalid, inv_B_dev, rows(_f32(row_w)), w_norm, rows(td_abs))
         off += n
     return grad_slab[:ns], loss_slab[:ns]
 

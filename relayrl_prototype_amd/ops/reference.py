@@ -147,10 +147,13 @@ def normalize_adv(adv, adv_stats):
 
 
 def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None, ret=None, logp_old=None,
-                 adv_stats=None, inv_B=None, clip_eps=0.2, ent_coef=0.0, dtype=torch.float32):
+                 adv_stats=None, inv_B=None, clip_eps=0.2, ent_coef=0.0, dtype=torch.float32, row_w=None,
+                 w_norm=None):
     """Returns (flat gradient, stats dict) of sum_i loss_i * inv_B (+ entropy bonus);
     ``dtype=torch.float64`` gives the float64 oracle (tools/grad_fuzz_probe.py).
-    ``HEAD_Q_TD``: loss_i = huber(Q(x_i)[act_i] - ret_i, delta) with delta = ``clip_eps``."""
+    ``HEAD_Q_TD``: loss_i = huber(Q(x_i)[act_i] - ret_i, delta) with delta = ``clip_eps``, times
+    ``row_w[i] / w_norm`` where the weights of prioritised replay are given; ``stats["td_abs"]`` is
+    |Q - ret| per row."""
     B, D = X.shape
     gaussian = head in (HEAD_PPO_GAUSS, HEAD_PG_GAUSS)
     Aeff = 1 if head == HEAD_VALUE_MSE else A
@@ -169,8 +172,10 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
         diff = q - ret.to(dtype)
         ad = diff.abs()
         li = torch.where(ad <= clip_eps, 0.5 * diff * diff, clip_eps * (ad - 0.5 * clip_eps))
+        if row_w is not None:
+            li = (row_w.to(dtype) / torch.as_tensor(w_norm).to(dtype).reshape(-1)[0]) * li
         loss = li.sum() * inv_B
-        stats.update(loss=li.sum().item(), v=q.sum().item(), count=B)
+        stats.update(loss=li.sum().item(), v=q.sum().item(), count=B, td_abs=ad.detach())
     else:
         advn = normalize_adv(adv.to(dtype), None if adv_stats is None else adv_stats.to(dtype))
         if not gaussian:

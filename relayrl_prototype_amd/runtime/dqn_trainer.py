@@ -13,9 +13,18 @@ One epoch (single rank, eager launches):
 
 Every random draw is Philox at explicit coordinates (env streams: (env, global step); replay
 samples: (batch row, update)), so a run is a pure function of the seed and ``state_dict()`` /
-``load_state_dict()`` resume it bit for bit.  The API mirrors ``VecTrainer``.  Left for later:
-several ranks, hipGraph capture, prioritised replay, n-step returns, serving the policy to agents
-(the trainer exposes no ``learner``, so a TrainingServer engine publishes no model).
+``load_state_dict()`` resume it bit for bit.  The API mirrors ``VecTrainer``.
+
+``prioritized=True`` is prioritised experience replay (Schaul et al., proportional variant) on the
+device: a priority sum tree over the ring's rows (csrc/kernels/per.hip, ops/per.py) in which every node
+is one fp32 add of its children, so it is reproducible on any grid and rebuilt bit for bit from its
+leaves.  The epoch becomes: rollout, ``per_insert`` of the slots just written (at the running maximum
+priority), and per update ``dqn_targets`` (prioritised: rows from the tree, importance weights w and
+their maximum), ``mlp_grad(Q_TD, row_w, w_norm, td_abs)``, Adam, ``per_update`` of the sampled rows to
+``(|td| + per_eps)^per_alpha``.  The host owns the beta anneal (``beta_at``) like the epsilon schedule.
+
+Left for later: several ranks, hipGraph capture, n-step returns, serving the policy to agents (the
+trainer exposes no ``learner``, so a TrainingServer engine publishes no model).
 """
 from __future__ import annotations
 
@@ -26,6 +35,7 @@ import torch
 
 from ..algorithms.core import FlatNet
 from ..ops import GradHead, MLPSpec, ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_targets, grad_slabs, hip, mlp_grad
+from ..ops import PriorityTree, per_insert, per_update
 from ..parallel.comm import Comm
 from .rollout_learn import episode_metrics
 from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
@@ -52,6 +62,31 @@ class DQNConfig:
     huber_delta: float = 1.0
     seed: int = 1
     max_episode_steps: Optional[int] = None
+    prioritized: bool = False       # prioritised experience replay (proportional variant)
+    per_alpha: float = 0.6          # priority = (|td| + per_eps)^per_alpha
+    per_beta_start: float = 0.4     # importance-weight exponent, annealed linearly by the host
+    per_beta_end: float = 1.0
+    per_beta_epochs: int = 500
+    per_eps: float = 1e-3
+
+    def __post_init__(self):
+        # hyperparameters of a TrainingServer arrive as strings ("true")
+        if isinstance(self.prioritized, str):
+            word = self.prioritized.strip().lower()
+            if word not in ("true", "false", "1", "0", "yes", "no"):
+                raise ValueError(f"prioritized must be a boolean, got {self.prioritized!r}")
+            self.prioritized = word in ("true", "1", "yes")
+        self.prioritized = bool(self.prioritized)
+        for k in ("per_alpha", "per_beta_start", "per_beta_end", "per_eps"):
+            setattr(self, k, float(getattr(self, k)))
+        self.per_beta_epochs = int(self.per_beta_epochs)
+        if not self.per_alpha >= 0.0:
+            raise ValueError(f"per_alpha must be >= 0, got {self.per_alpha}")
+        for k in ("per_beta_start", "per_beta_end"):
+            if not 0.0 < getattr(self, k) <= 1.0:
+                raise ValueError(f"{k} must be in (0, 1], got {getattr(self, k)}")
+        if not self.per_eps > 0.0:
+            raise ValueError(f"per_eps must be > 0, got {self.per_eps}")
 
     def to_dict(self):
         return asdict(self)
@@ -67,6 +102,13 @@ def epsilon_at(cfg: DQNConfig, epoch: int) -> float:
     """The exploration rate of (0-based) epoch ``epoch``: linear from eps_start to eps_end over eps_decay_epochs."""
     frac = min(1.0, epoch / cfg.eps_decay_epochs) if cfg.eps_decay_epochs > 0 else 1.0
     return float(cfg.eps_start + (cfg.eps_end - cfg.eps_start) * frac)
+
+
+def beta_at(cfg: DQNConfig, epoch: int) -> float:
+    """The importance-weight exponent of (0-based) epoch ``epoch``: linear from per_beta_start to per_beta_end
+    over per_beta_epochs."""
+    frac = min(1.0, epoch / cfg.per_beta_epochs) if cfg.per_beta_epochs > 0 else 1.0
+    return float(cfg.per_beta_start + (cfg.per_beta_end - cfg.per_beta_start) * frac)
 
 
 class DQNTrainer:
@@ -109,6 +151,14 @@ class DQNTrainer:
         ns = grad_slabs(B, dev)
         self.slab = torch.zeros(ns, self.q.P, device=dev)
         self.loss = torch.zeros(ns, 8, device=dev)
+        self.per = None
+        if cfg.prioritized:
+            self.per = PriorityTree.allocate(C, N, dev)
+            self.idx = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.w = torch.zeros(B, device=dev)
+            self.wmax = torch.zeros(1, device=dev)
+            self.td_abs = torch.zeros(B, device=dev)
+        self.last_beta = float(cfg.per_beta_start)
         self.env_seed, self.sample_seed, self.eval_seed = dqn_seeds(cfg.seed)
         self.eval_step0 = 0
         self.epoch = 0
@@ -129,11 +179,16 @@ class DQNTrainer:
         cfg = self.cfg
         T = cfg.rollout_len
         self.last_epsilon = self.epsilon()
+        self.last_beta = beta_at(cfg, self.epoch)  # the exponent of this epoch's updates
         rc = dqn_rollout(self.env_id, self.q.params, cfg.hidden, T, self.cursor, self.ring, self.state, self.ep_len,
                          self.ep_ret, self.ep_stats, seed=self.env_seed, step0=self.epoch * T,
                          epsilon=self.last_epsilon, reset_all=self._first, max_steps=self.max_steps)
         if rc != 0:
             raise RuntimeError(f"dqn_rollout refused slot {self.cursor} of {cfg.buffer_slots} (code {rc})")
+        if self.per is not None:  # the new transitions enter at the running maximum priority
+            rc = per_insert(self.per, cfg.buffer_slots, cfg.num_envs, T, self.cursor)
+            if rc != 0:
+                raise RuntimeError(f"per_insert refused slot {self.cursor} of {cfg.buffer_slots} (code {rc})")
         self._first = False
         self.cursor = (self.cursor + T) % cfg.buffer_slots
         self.slots_written += T
@@ -142,11 +197,21 @@ class DQNTrainer:
         """One gradient step on a freshly sampled batch; the target network follows on its schedule."""
         cfg = self.cfg
         filled = min(self.slots_written, cfg.buffer_slots) * cfg.num_envs
-        dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
-                    self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None))
-        mlp_grad(GradHead.Q_TD, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
-                 clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
-        self.q.apply(self.slab)
+        if self.per is None:
+            dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
+                        self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None))
+            mlp_grad(GradHead.Q_TD, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                     clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
+            self.q.apply(self.slab)
+        else:
+            dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
+                        self.sample_seed, self.updates, cfg.batch_size, tree=self.per.tree, beta=self.last_beta,
+                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax))
+            mlp_grad(GradHead.Q_TD, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                     clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
+                     w_norm=self.wmax, td_abs=self.td_abs)
+            self.q.apply(self.slab)
+            per_update(self.per, self.idx, self.td_abs, cfg.per_alpha, cfg.per_eps)
         self.updates += 1
         self._has_loss = True
         if self.updates % cfg.target_update_every == 0:
@@ -194,6 +259,8 @@ class DQNTrainer:
                 loss_q, q_vals = ls[0] / ls[5], ls[4] / ls[5]
         out.update(LossQ=loss_q, QVals=q_vals, Epsilon=self.last_epsilon, Updates=self.updates,
                    EnvSteps=self.env_steps, WorldSize=1)
+        if self.per is not None:
+            out.update(Beta=self.last_beta, PriorityMax=float(self.per.pmax.item()))
         return out
 
     def episode_sums(self) -> tuple:
@@ -208,7 +275,10 @@ class DQNTrainer:
     # ------------------------------------------------------------------ state
     def snapshot_tensors(self):
         q = self.q
-        return [q.params, q.m, q.v, q.step, self.target, *self.ring, self.state, self.ep_len, self.ep_ret]
+        ts = [q.params, q.m, q.v, q.step, self.target, *self.ring, self.state, self.ep_len, self.ep_ret]
+        if self.per is not None:  # at the end: the names of the uniform trainer's tensors keep their places
+            ts += [self.per.tree, self.per.pmax]
+        return ts
 
     def counters(self) -> dict:
         return {"epoch": self.epoch, "env_steps": self.env_steps, "updates": self.updates, "cursor": self.cursor,
@@ -221,12 +291,15 @@ class DQNTrainer:
     def state_dict(self) -> dict:
         """Everything a bit-exact resume needs.  ``learner/pi/params`` is the online network, the
         layout ``launcher.evaluate_checkpoint_state`` reads."""
-        return {"cfg": self.cfg.to_dict(),
-                "learner": {"pi": self.q.state_dict(), "target": {"params": self.target.cpu()}},
-                "ring": {k: t.cpu() for k, t in self.ring._asdict().items()},
-                "epoch": self.epoch, "env_steps": self.env_steps, "updates": self.updates, "cursor": self.cursor,
-                "slots_written": self.slots_written, "eval_step0": self.eval_step0,
-                "env_state": self.state.cpu(), "ep_len": self.ep_len.cpu(), "ep_ret": self.ep_ret.cpu()}
+        sd = {"cfg": self.cfg.to_dict(),
+              "learner": {"pi": self.q.state_dict(), "target": {"params": self.target.cpu()}},
+              "ring": {k: t.cpu() for k, t in self.ring._asdict().items()},
+              "epoch": self.epoch, "env_steps": self.env_steps, "updates": self.updates, "cursor": self.cursor,
+              "slots_written": self.slots_written, "eval_step0": self.eval_step0,
+              "env_state": self.state.cpu(), "ep_len": self.ep_len.cpu(), "ep_ret": self.ep_ret.cpu()}
+        if self.per is not None:  # the tree is a pure function of its leaves: load_state_dict rebuilds it
+            sd["per"] = {"leaves": self.per.leaves.cpu(), "pmax": float(self.per.pmax.item())}
+        return sd
 
     def load_state_dict(self, sd: dict):
         """Resume from ``state_dict()``.  The Philox keys derive from ``cfg.seed``: build the trainer with the
@@ -243,3 +316,7 @@ class DQNTrainer:
         self.state.copy_(sd["env_state"].to(self.device))
         self.ep_len.copy_(sd["ep_len"].to(self.device))
         self.ep_ret.copy_(sd["ep_ret"].to(self.device))
+        if self.per is not None:
+            if "per" not in sd:
+                raise ValueError("a prioritised trainer cannot resume a checkpoint without priorities")
+            self.per.load_leaves(sd["per"]["leaves"], sd["per"]["pmax"])
