@@ -20,6 +20,12 @@ One JSON line:
 microseconds per launch of ``per_insert``, ``dqn_targets_per``, ``mlp_grad_q_td_weighted`` and ``per_update``
 (``per_insert`` and ``per_update`` are one workgroup each: their time is latency, not throughput).  The
 line goes to ``profiles/dqn_per_bench.jsonl`` unless ``--out`` names another file.
+
+``--n-step K [K ...]`` adds, from the same process, what n-step returns cost: the microseconds per launch of
+``dqn_targets`` at ``n_step = 1`` and at every K on the same trained ring, uniform (``targets_n<K>_us``) and
+prioritised (``targets_per_n<K>_us``), and the epoch of both DQN presets at ``n_step = 1`` and at the first K
+(``epoch_n<K>_us`` / ``epoch_per_n<K>_us``).  The line goes to ``profiles/dqn_nstep_bench.jsonl`` unless
+``--out`` names another file.
 """
 import argparse
 import json
@@ -94,6 +100,45 @@ def per_records(a, dev, event_us):
     return rec
 
 
+def nstep_records(a, dev, event_us):
+    """n-step returns against one-step in one process: the targets launch, uniform and prioritised, and the epoch."""
+    from relayrl_prototype_amd.ops import dqn_targets
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    rec = dict(n_steps=list(a.n_step))
+    for preset, tag in (("cartpole-dqn", ""), ("cartpole-dqn-per", "per_")):
+        for n in (1, a.n_step[0]):
+            cfg = DQNConfig(**dict(PRESETS[preset].overrides, n_step=n))
+            tr = DQNTrainer(cfg, device=dev)
+            for _ in range(a.warmup):
+                tr.train_epoch()
+            assert tr.updates > 0, "the warm-up must reach learning_starts"
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.epochs):
+                tr.train_epoch()
+            torch.cuda.synchronize()
+            rec[f"epoch_{tag}n{n}_us"] = round(1e6 * (time.perf_counter() - t0) / a.epochs, 2)
+        # the launch alone, on the ring of the trainer just measured: the same rows are sampled for every n
+        N, B, C = cfg.num_envs, cfg.batch_size, cfg.buffer_slots
+        filled = min(tr.slots_written, C) * N
+        newest = (tr.cursor - 1) % C
+        out = (tr.Xb, tr.act_b, tr.y, tr.idx, tr.w, tr.wmax) if tr.per is not None else (tr.Xb, tr.act_b, tr.y, None)
+        kw = dict(tree=tr.per.tree, beta=0.7) if tr.per is not None else {}
+        for n in [1] + [k for k in a.n_step if k != 1]:
+            def targets():
+                dqn_targets(tr.q.params, tr.target, cfg.hidden, tr.A, tr.ring, filled, cfg.gamma, cfg.double_q,
+                            tr.sample_seed, 7, B, out=out, n_step=n, newest=newest, **kw)
+
+            targets()
+            torch.cuda.synchronize()
+            med, lo, hi = event_us(targets, a.iters, a.reps)
+            rec[f"targets_{tag}n{n}_us"] = med
+            rec[f"targets_{tag}n{n}_us_range"] = [lo, hi]
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2000)
@@ -103,10 +148,14 @@ def main():
     ap.add_argument("--tag", default="")
     ap.add_argument("--out", default="")
     ap.add_argument("--prioritized", action="store_true", help="also measure the cartpole-dqn-per preset")
+    ap.add_argument("--n-step", type=int, nargs="+", default=[], metavar="K",
+                    help="also measure n-step returns at every K against one-step")
     a = ap.parse_args()
-    if a.prioritized and not a.out:
+    if any(k < 1 for k in a.n_step):
+        raise SystemExit("--n-step takes values >= 1")
+    if (a.prioritized or a.n_step) and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                             "dqn_per_bench.jsonl")
+                             "dqn_nstep_bench.jsonl" if a.n_step else "dqn_per_bench.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("dqn_bench needs a GPU: a CPU timing says nothing about the MI355X")
     from relayrl_prototype_amd.ops import GradHead, dqn_rollout, dqn_targets, mlp_grad, set_value_grad_mode
@@ -165,6 +214,8 @@ def main():
         set_value_grad_mode(old)
     if a.prioritized:
         rec.update(per_records(a, dev, event_us))
+    if a.n_step:
+        rec.update(nstep_records(a, dev, event_us))
     rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
     line = json.dumps(rec)
     print(line, flush=True)

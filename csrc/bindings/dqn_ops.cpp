@@ -1,6 +1,7 @@
 // Bindings of the DQN kernels (csrc/kernels/dqn.hip): the epsilon-greedy actor that fills the replay
 // ring and the sample + gather + TD-target kernel, uniform and prioritised, and of the priority sum
 // tree (csrc/kernels/per.hip).  Every tensor is validated before a launch.
+#include <cstdlib>
 #include <tuple>
 
 #include "api.h"
@@ -57,10 +58,15 @@ int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int
   return 0;
 }
 
-void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
-                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
-                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
-                 const OptT& idx) {
+// What every form of the targets launch checks; the ring's N, D, the batch size and the online pointer.
+struct TargetCall {
+  int64_t N, D, B, L;
+  const float* online;
+};
+
+TargetCall check_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
+                         const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled,
+                         bool double_q, const Tensor& Xb, const Tensor& act_b, const Tensor& y) {
   TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
   const int64_t D = obs.size(2);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
@@ -77,10 +83,37 @@ void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A,
   TORCH_CHECK(B >= 1 && B * D < (int64_t)INT32_MAX, "batch size out of range");
   check(Xb, "Xb", at::kFloat, B * D);
   check(act_b, "act_b", at::kInt, B);
-  int* ix = opt_ptr<int>(idx, "idx", at::kInt, B);
-  check_rc(rrl_dqn_targets(on, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
+  return {N, D, B, C * N, on};
+}
+
+// The n-step forms: N is the ring's; n_step, filled % N and newest are the entry point's to refuse.
+void dqn_targets_nstep(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
+                       const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled,
+                       double gamma, bool double_q, int64_t sample_key, int64_t update, int64_t n_step, int64_t newest,
+                       const Tensor& Xb, const Tensor& act_b, const Tensor& y, const OptT& idx, const OptT& last) {
+  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y);
+  TORCH_CHECK(std::abs(n_step) < (int64_t)INT32_MAX && std::abs(newest) < (int64_t)INT32_MAX,
+              "n_step / newest out of range");
+  int* ix = opt_ptr<int>(idx, "idx", at::kInt, c.B);
+  int* la = opt_ptr<int>(last, "last", at::kInt, c.B);
+  check_rc(rrl_dqn_targets_nstep(c.online, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
+                                 act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(),
+                                 (long long)filled, (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0,
+                                 (uint64_t)sample_key, (uint64_t)update, (int)n_step, (int)c.N, (int)newest,
+                                 Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(), ix, la, grid_cus(),
+                                 cur_stream()),
+           "dqn_targets_nstep");
+}
+
+void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
+                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
+                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
+                 const OptT& idx) {
+  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y);
+  int* ix = opt_ptr<int>(idx, "idx", at::kInt, c.B);
+  check_rc(rrl_dqn_targets(c.online, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
                            act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(), (long long)filled,
-                           (int)B, (int)D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0, (uint64_t)sample_key,
+                           (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0, (uint64_t)sample_key,
                            (uint64_t)update, Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(), ix,
                            grid_cus(), cur_stream()),
            "dqn_targets");
@@ -125,34 +158,44 @@ void per_update(const Tensor& tree, const Tensor& pmax, int64_t L, const Tensor&
            "per_update");
 }
 
+void dqn_targets_per_nstep(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
+                           const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done,
+                           const Tensor& tree, int64_t filled, double gamma, bool double_q, double beta,
+                           int64_t sample_key, int64_t update, int64_t n_step, int64_t newest, const Tensor& Xb,
+                           const Tensor& act_b, const Tensor& y, const Tensor& idx, const Tensor& w, const Tensor& wmax,
+                           const OptT& last) {
+  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y);
+  TORCH_CHECK(beta > 0.0 && beta <= 1.0, "beta must be in (0, 1], got ", beta);
+  TORCH_CHECK(std::abs(n_step) < (int64_t)INT32_MAX && std::abs(newest) < (int64_t)INT32_MAX,
+              "n_step / newest out of range");
+  check_tree(tree, wmax, "wmax", c.L);
+  check(idx, "idx", at::kInt, c.B);
+  check(w, "w", at::kFloat, c.B);
+  int* la = opt_ptr<int>(last, "last", at::kInt, c.B);
+  check_rc(rrl_dqn_targets_per_nstep(c.online, target.data_ptr<float>(), obs.data_ptr<float>(),
+                                     nobs.data_ptr<float>(), act.data_ptr<int>(), rew.data_ptr<float>(),
+                                     done.data_ptr<float>(), tree.data_ptr<float>(), (long long)c.L, (long long)filled,
+                                     (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0, (float)beta,
+                                     (uint64_t)sample_key, (uint64_t)update, (int)n_step, (int)c.N, (int)newest,
+                                     Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(),
+                                     idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), la, grid_cus(),
+                                     cur_stream()),
+           "dqn_targets_per_nstep");
+}
+
 void dqn_targets_per(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
                      const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& tree,
                      int64_t filled, double gamma, bool double_q, double beta, int64_t sample_key, int64_t update,
                      const Tensor& Xb, const Tensor& act_b, const Tensor& y, const Tensor& idx, const Tensor& w,
                      const Tensor& wmax) {
-  TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
-  const int64_t D = obs.size(2);
-  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
-  TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
-  TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
+  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y);
   TORCH_CHECK(beta > 0.0 && beta <= 1.0, "beta must be in (0, 1], got ", beta);
-  check_tree(tree, wmax, "wmax", C * N);
-  const int64_t P = H * D + H + H * H + H + A * H + A;
-  check(target, "target", at::kFloat, P);
-  const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
-  TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
-  check(y, "y", at::kFloat);
-  const int64_t B = y.numel();
-  TORCH_CHECK(B >= 1 && B * D < (int64_t)INT32_MAX, "batch size out of range");
-  check(Xb, "Xb", at::kFloat, B * D);
-  check(act_b, "act_b", at::kInt, B);
-  check(idx, "idx", at::kInt, B);
-  check(w, "w", at::kFloat, B);
-  check_rc(rrl_dqn_targets_per(on, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
+  check_tree(tree, wmax, "wmax", c.L);
+  check(idx, "idx", at::kInt, c.B);
+  check(w, "w", at::kFloat, c.B);
+  check_rc(rrl_dqn_targets_per(c.online, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
                                act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(),
-                               tree.data_ptr<float>(), (long long)(C * N), (long long)filled, (int)B, (int)D, (int)A,
+                               tree.data_ptr<float>(), (long long)c.L, (long long)filled, (int)c.B, (int)c.D, (int)A,
                                (int)H, (float)gamma, double_q ? 1 : 0, (float)beta, (uint64_t)sample_key,
                                (uint64_t)update, Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(),
                                idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), grid_cus(),
@@ -183,4 +226,13 @@ void register_dqn_ops(pybind11::module_& m) {
         py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"), py::arg("gamma"),
         py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"),
         py::arg("idx"));
+  m.def("dqn_targets_nstep", &dqn_targets_nstep, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
+        py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"),
+        py::arg("gamma"), py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("n_step"),
+        py::arg("newest"), py::arg("Xb"), py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("last"));
+  m.def("dqn_targets_per_nstep", &dqn_targets_per_nstep, py::arg("online"), py::arg("target"), py::arg("H"),
+        py::arg("A"), py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"),
+        py::arg("tree"), py::arg("filled"), py::arg("gamma"), py::arg("double_q"), py::arg("beta"),
+        py::arg("sample_key"), py::arg("update"), py::arg("n_step"), py::arg("newest"), py::arg("Xb"),
+        py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("w"), py::arg("wmax"), py::arg("last"));
 }

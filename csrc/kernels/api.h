@@ -164,6 +164,25 @@ int rrl_dqn_targets_per(const float* online, const float* target, const float* o
                         long long filled, int B, int D, int A, int H, float gamma, int double_q, float beta,
                         uint64_t sample_key, uint64_t update, float* Xb, int* act_b, float* y, int* idx, float* w,
                         float* wmax, int num_cu, void* stream);
+// The n-step forms of the two above.  The ring is time-major with N envs per slot, `filled` a multiple of N
+// and `newest` the slot written last.  The sampled row r0 walks forward before the bootstrap:
+//   last = r0; G = rew[r0]; disc = gamma; m = 1
+//   while (m < n_step && done[last] == 0 && last / N != newest) {
+//     last += N; if (last >= filled) last -= filled;  G = fma(disc, rew[last], G);  disc *= gamma;  ++m; }
+//   y[b] = G + disc * (done[last] == 1 ? 0 : 1) * Q_target(nobs[last], a*),   a* chosen at nobs[last]
+// in fp32, in this order.  Xb, act_b, idx (and w, wmax) refer to r0 as before; last[b] (may be null) <- last.
+// n_step == 1 launches the one-step kernel (last = idx then: it needs idx).  The codes of the one-step forms,
+// and (nothing written) -2: n_step < 1, N < 1 or filled % N != 0; -4: newest outside [0, filled / N)
+int rrl_dqn_targets_nstep(const float* online, const float* target, const float* obs, const float* nobs,
+                          const int* act, const float* rew, const float* done, long long filled, int B, int D, int A,
+                          int H, float gamma, int double_q, uint64_t sample_key, uint64_t update, int n_step, int N,
+                          int newest, float* Xb, int* act_b, float* y, int* idx, int* last, int num_cu, void* stream);
+int rrl_dqn_targets_per_nstep(const float* online, const float* target, const float* obs, const float* nobs,
+                              const int* act, const float* rew, const float* done, const float* tree, long long L,
+                              long long filled, int B, int D, int A, int H, float gamma, int double_q, float beta,
+                              uint64_t sample_key, uint64_t update, int n_step, int N, int newest, float* Xb,
+                              int* act_b, float* y, int* idx, float* w, float* wmax, int* last, int num_cu,
+                              void* stream);
 
 // ---- per.hip
 // The priority sum tree of prioritised replay over a ring of L = C * N rows: fp32 tree[2 * P2], P2 =

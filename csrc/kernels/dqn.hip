@@ -15,6 +15,8 @@
 //     wraps: C % T == 0, slot0 % T == 0 and slot0 + T <= C, the host advances the cursor.
 //
 // One form only, the tile-stride one (4 tiles per workgroup, one per wave): see docs/KERNELS.md.
+#include <type_traits>
+
 #include "actor_step.h"
 
 namespace rrl {
@@ -97,6 +99,14 @@ __global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(DqnRolloutArgs p) {
 // stages the online net, walks its rows and parks a* in y[b] (as bits; the same thread reads it
 // back), then re-stages the target net over the same LDS image and walks the same rows again.
 // Two H = 128 images (2 x 80 KB) would leave the 160 KB of LDS no margin; see docs/KERNELS.md.
+//
+// The n-step instance (NSTEP = true) first walks the sampled row r0 forward through the time-major ring,
+// same env, next slot (dqn_nstep_walk), and bootstraps from the row `last` the walk ended on:
+//   y[b] = G + disc * (done[last] == 1 ? 0 : 1) * Q_tgt(nobs[last], a*),   a* chosen at nobs[last];
+// Xb, act_b, idx and the priorities still refer to r0.  The walk happens once per batch row: with
+// double_q the online pass parks its length (m - 1) in act_b[b] and G in Xb[b][0], next to a* in y[b]
+// (all three are outputs the same thread overwrites in the target pass), and the target pass rebuilds
+// last = r0 + (m - 1) * N and disc = gamma^m (the walk's own products, no loads) from them.
 struct DqnTargetArgs {
   const float* online;
   const float* target;
@@ -122,6 +132,16 @@ struct DqnTargetArgs {
   float beta = 0.f;
   float* w = nullptr;           // [B] importance weights (filled * leaf / total)^-beta
   int* wmax = nullptr;          // [1] max_b w[b] as float bits, zeroed by the launcher
+};
+
+// The n-step instances take their own argument block, so that the one-step kernels keep theirs (and
+// with it their code, down to the offsets of the launch's implicit arguments).
+struct DqnNStepArgs : DqnTargetArgs {
+  int n_step = 1;
+  uint32_t N = 1;           // envs per slot: the successor of row r is row r + N (mod filled)
+  uint32_t slots = 1;       // filled / N
+  uint32_t newest_row = 0;  // newest * N: the rows [newest_row, newest_row + N) end a walk
+  int* last = nullptr;      // [B] or null: the row the target bootstrapped from
 };
 
 RRL_DEV uint32_t dqn_sample_row(int b, const DqnTargetArgs& p) {
@@ -168,11 +188,45 @@ RRL_DEV uint32_t per_sample_row(int b, const DqnTargetArgs& p) {
   return min(row, p.filled - 1u);
 }
 
+// The n-step walk from the sampled row r0 < filled: while fewer than n_step steps are summed, the row is
+// running (done == 0) and it is not in the newest slot, go to the same env in the next slot (the ring
+// wraps at filled) and add its discounted reward.  G (one fused multiply-add) and disc (one product)
+// are updated in this order, step by step (ops/dqn.py dqn_nstep_walk_ref repeats the order).  N <= filled
+// and last < filled, so last + N < 2^32 and one subtraction wraps it: last stays in [0, filled) whatever
+// the ring holds.
+struct NStepWalk {
+  uint32_t last;
+  float G, disc;
+  int m;  // steps summed, 1 .. n_step
+};
+
+RRL_DEV NStepWalk dqn_nstep_walk(uint32_t r0, const DqnNStepArgs& p) {
+  NStepWalk w{r0, p.rew[r0], p.gamma, 1};
+  while (w.m < p.n_step && p.done[w.last] == 0.f && w.last - p.newest_row >= p.N) {
+    w.last += p.N;
+    if (w.last >= p.filled) w.last -= p.filled;
+    w.G = fmaf(w.disc, p.rew[w.last], w.G);
+    w.disc = w.disc * p.gamma;
+    ++w.m;
+  }
+  return w;
+}
+
+// The row a walk of m1 + 1 steps from r0 ended on.  m1 comes back from memory (parked by the online pass):
+// the clamp to slots - 1 keeps m1 * N < filled, so the sum stays below 2^32 and the row inside the ring.
+RRL_DEV uint32_t dqn_nstep_last(uint32_t r0, uint32_t m1, const DqnNStepArgs& p) {
+  uint32_t last = r0 + min(m1, p.slots - 1u) * p.N;
+  if (last >= p.filled) last -= p.filled;
+  return last;
+}
+
 // PER = false: the uniform sampler.  PER = true: the rows come from the priority tree, and the kernel
 // also writes the importance weight w[b] and raises *wmax to it (a maximum on the bits of non-negative
 // floats).  With double_q the online pass parks the row in idx[b], so the tree is descended once.
-template <int HT, bool PER>
-__global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
+// NSTEP = true: the n-step instance (above); NSTEP = false is the one-step kernel, untouched.
+template <int HT, bool PER, bool NSTEP = false>
+__global__ __launch_bounds__(256, 1) void dqn_targets_kernel(
+    std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int l = lane_id();
   const int j = l & 15, g = l >> 4;
@@ -186,7 +240,17 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
       const bool ok = b < p.B;
       const size_t r = ok ? (PER ? per_sample_row(b, p) : dqn_sample_row(b, p)) : 0;
       float q[kMaxAct];
-      dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, p.A, q);
+      if constexpr (NSTEP) {
+        NStepWalk w{0u, 0.f, 0.f, 1};
+        if (ok) w = dqn_nstep_walk((uint32_t)r, p);
+        dqn_q_values<HT>(lds, p.nobs, w.last, ok, p.D, p.A, q);
+        if (ok && g == 0) {
+          p.act_b[b] = w.m - 1;
+          p.Xb[(size_t)b * p.D] = w.G;
+        }
+      } else {
+        dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, p.A, q);
+      }
       if (ok && g == 0) {
         p.y[b] = __int_as_float(argmax_first(p.A, q));
         if (PER) p.idx[b] = (int)r;
@@ -206,13 +270,33 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgs p) {
       else r = per_sample_row(b, p);
     }
     float q[kMaxAct];
-    dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, p.A, q);
+    size_t last = r;     // the row the target bootstraps from
+    float G = 0.f, disc = p.gamma;
+    if constexpr (NSTEP) {
+      if (ok) {
+        if (p.double_q) {  // parked by this wave's lane g = 0: the walk is not repeated
+          const uint32_t m1 = (uint32_t)p.act_b[b];
+          last = dqn_nstep_last((uint32_t)r, m1, p);
+          for (uint32_t k = 0; k < min(m1, p.slots - 1u); ++k) disc = disc * p.gamma;
+          if (g == 0) G = p.Xb[(size_t)b * p.D];  // before this thread overwrites it below
+        } else {
+          const NStepWalk w = dqn_nstep_walk((uint32_t)r, p);
+          last = w.last, G = w.G, disc = w.disc;
+        }
+      }
+    }
+    dqn_q_values<HT>(lds, p.nobs, last, ok, p.D, p.A, q);
     if (ok) {
       for (int f = g; f < p.D; f += 4) p.Xb[(size_t)b * p.D + f] = p.obs[r * p.D + f];
       if (g == 0) {
         const int astar = p.double_q ? __float_as_int(p.y[b]) : argmax_first(p.A, q);
-        const float boot = (p.done[r] == 1.f) ? 0.f : 1.f;
-        p.y[b] = p.rew[r] + p.gamma * boot * pick_logit(p.A, q, astar);
+        const float boot = (p.done[last] == 1.f) ? 0.f : 1.f;
+        if constexpr (NSTEP) {
+          p.y[b] = G + disc * boot * pick_logit(p.A, q, astar);
+          if (p.last != nullptr) p.last[b] = (int)last;
+        } else {
+          p.y[b] = p.rew[r] + p.gamma * boot * pick_logit(p.A, q, astar);
+        }
         p.act_b[b] = p.act[r];
         if (p.idx != nullptr) p.idx[b] = (int)r;
         if (PER) {
@@ -266,12 +350,13 @@ extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H
   });
 }
 
-template <int HT, bool PER = false>
-static int launch_dqn_targets(const DqnTargetArgs& a, int grid, hipStream_t s) {
+template <int HT, bool PER = false, bool NSTEP = false>
+static int launch_dqn_targets(const std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>& a, int grid,
+                              hipStream_t s) {
   using L = LdsNet<1, HT>;
-  raise_lds_limit<dqn_targets_kernel<HT, PER>>();
+  raise_lds_limit<dqn_targets_kernel<HT, PER, NSTEP>>();
   const size_t bytes = (size_t)L::floats(a.A) * sizeof(float);
-  hipLaunchKernelGGL((dqn_targets_kernel<HT, PER>), dim3(grid), dim3(256), bytes, s, a);
+  hipLaunchKernelGGL((dqn_targets_kernel<HT, PER, NSTEP>), dim3(grid), dim3(256), bytes, s, a);
   return (int)hipGetLastError();
 }
 
@@ -281,19 +366,33 @@ static int dqn_targets_grid(int B, int num_cu) {
   return grid > cap ? cap : grid;
 }
 
+// The checks the n-step entry points add, and the walk's launch arguments.  0, or the code to return.
+static int dqn_nstep_args(DqnNStepArgs& a, const DqnTargetArgs& one, long long filled, int n_step, int N,
+                          int newest, int* last) {
+  if (n_step < 1 || N < 1 || filled % N != 0) return -2;
+  if (newest < 0 || newest >= filled / N) return -4;
+  static_cast<DqnTargetArgs&>(a) = one;
+  a.n_step = n_step;
+  a.N = (uint32_t)N;
+  a.slots = (uint32_t)(filled / N);
+  a.newest_row = (uint32_t)newest * (uint32_t)N;
+  a.last = last;
+  return 0;
+}
+
+// n_step == 1 is the one-step kernel; its target bootstraps from the sampled row itself
+static int dqn_one_step_last(int* last, const int* idx, int B, hipStream_t s) {
+  if (last == nullptr) return 0;
+  return (int)hipMemcpyAsync(last, idx, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s);
+}
+
+// The one-step forms: n_step = 1 over slots of one row (N = 1 divides every filled, newest = 0 is in range).
 extern "C" int rrl_dqn_targets(const float* online, const float* target, const float* obs, const float* nobs,
                                const int* act, const float* rew, const float* done, long long filled, int B, int D,
                                int A, int H, float gamma, int double_q, uint64_t sample_key, uint64_t update,
                                float* Xb, int* act_b, float* y, int* idx, int num_cu, void* stream) {
-  if (!target || (double_q && !online) || !obs || !nobs || !act || !rew || !done || !Xb || !act_b || !y) return -1;
-  if (filled < 1 || filled > 0x7FFFFFFFll || B < 1) return -2;
-  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A > kMaxAct) return -3;
-  DqnTargetArgs a{online, target, obs, nobs, act, rew, done, B, D, A, (uint32_t)filled, gamma, double_q ? 1 : 0,
-                  (uint32_t)sample_key, (uint32_t)(sample_key >> 32), (uint32_t)update, (uint32_t)(update >> 32),
-                  Xb, act_b, y, idx};
-  const int grid = dqn_targets_grid(B, num_cu);
-  hipStream_t s = (hipStream_t)stream;
-  return H == 128 ? launch_dqn_targets<8>(a, grid, s) : launch_dqn_targets<4>(a, grid, s);
+  return rrl_dqn_targets_nstep(online, target, obs, nobs, act, rew, done, filled, B, D, A, H, gamma, double_q,
+                               sample_key, update, 1, 1, 0, Xb, act_b, y, idx, nullptr, num_cu, stream);
 }
 
 extern "C" int rrl_dqn_targets_per(const float* online, const float* target, const float* obs, const float* nobs,
@@ -302,6 +401,40 @@ extern "C" int rrl_dqn_targets_per(const float* online, const float* target, con
                                    int double_q, float beta, uint64_t sample_key, uint64_t update, float* Xb,
                                    int* act_b, float* y, int* idx, float* w, float* wmax, int num_cu,
                                    void* stream) {
+  return rrl_dqn_targets_per_nstep(online, target, obs, nobs, act, rew, done, tree, L, filled, B, D, A, H, gamma,
+                                   double_q, beta, sample_key, update, 1, 1, 0, Xb, act_b, y, idx, w, wmax, nullptr,
+                                   num_cu, stream);
+}
+
+extern "C" int rrl_dqn_targets_nstep(const float* online, const float* target, const float* obs, const float* nobs,
+                                     const int* act, const float* rew, const float* done, long long filled, int B,
+                                     int D, int A, int H, float gamma, int double_q, uint64_t sample_key,
+                                     uint64_t update, int n_step, int N, int newest, float* Xb, int* act_b, float* y,
+                                     int* idx, int* last, int num_cu, void* stream) {
+  if (!target || (double_q && !online) || !obs || !nobs || !act || !rew || !done || !Xb || !act_b || !y) return -1;
+  if (n_step == 1 && last && !idx) return -1;
+  if (filled < 1 || filled > 0x7FFFFFFFll || B < 1) return -2;
+  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A > kMaxAct) return -3;
+  DqnTargetArgs a{online, target, obs, nobs, act, rew, done, B, D, A, (uint32_t)filled, gamma, double_q ? 1 : 0,
+                  (uint32_t)sample_key, (uint32_t)(sample_key >> 32), (uint32_t)update, (uint32_t)(update >> 32),
+                  Xb, act_b, y, idx};
+  DqnNStepArgs na;
+  if (const int rc = dqn_nstep_args(na, a, filled, n_step, N, newest, last)) return rc;
+  const int grid = dqn_targets_grid(B, num_cu);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_step == 1) {
+    const int rc = H == 128 ? launch_dqn_targets<8>(a, grid, s) : launch_dqn_targets<4>(a, grid, s);
+    return rc ? rc : dqn_one_step_last(last, idx, B, s);
+  }
+  return H == 128 ? launch_dqn_targets<8, false, true>(na, grid, s) : launch_dqn_targets<4, false, true>(na, grid, s);
+}
+
+extern "C" int rrl_dqn_targets_per_nstep(const float* online, const float* target, const float* obs,
+                                         const float* nobs, const int* act, const float* rew, const float* done,
+                                         const float* tree, long long L, long long filled, int B, int D, int A, int H,
+                                         float gamma, int double_q, float beta, uint64_t sample_key, uint64_t update,
+                                         int n_step, int N, int newest, float* Xb, int* act_b, float* y, int* idx,
+                                         float* w, float* wmax, int* last, int num_cu, void* stream) {
   if (!target || (double_q && !online) || !obs || !nobs || !act || !rew || !done || !Xb || !act_b || !y) return -1;
   if (!tree || !idx || !w || !wmax) return -1;
   const long long P2 = rrl_per_tree_leaves(L);
@@ -317,9 +450,15 @@ extern "C" int rrl_dqn_targets_per(const float* online, const float* target, con
   a.beta = beta;
   a.w = w;
   a.wmax = reinterpret_cast<int*>(wmax);
+  DqnNStepArgs na;
+  if (const int rc = dqn_nstep_args(na, a, filled, n_step, N, newest, last)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const hipError_t e = hipMemsetAsync(wmax, 0, sizeof(float), s);  // +0.0f: below every weight
   if (e != hipSuccess) return (int)e;
   const int grid = dqn_targets_grid(B, num_cu);
-  return H == 128 ? launch_dqn_targets<8, true>(a, grid, s) : launch_dqn_targets<4, true>(a, grid, s);
+  if (n_step == 1) {
+    const int rc = H == 128 ? launch_dqn_targets<8, true>(a, grid, s) : launch_dqn_targets<4, true>(a, grid, s);
+    return rc ? rc : dqn_one_step_last(last, idx, B, s);
+  }
+  return H == 128 ? launch_dqn_targets<8, true, true>(na, grid, s) : launch_dqn_targets<4, true, true>(na, grid, s);
 }

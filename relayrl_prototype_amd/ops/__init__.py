@@ -70,6 +70,7 @@ from .mlp import (  # noqa: E402
 from .integrity import payload_checksum, payload_verify  # noqa: E402
 from .evaluate import EvalTrace, evaluate_policy_op  # noqa: E402
 from .dqn import ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_sample_rows_ref, dqn_targets, dqn_targets_ref  # noqa: E402
+from .dqn import dqn_nstep_walk_ref  # noqa: E402
 from .per import (  # noqa: E402
     PriorityTree,
     per_insert,
@@ -96,6 +97,7 @@ __all__ = [
     "dqn_rollout",
     "dqn_rollout_grid",
     "dqn_sample_rows_ref",
+    "dqn_nstep_walk_ref",
     "dqn_targets",
     "dqn_targets_ref",
     "hip",

@@ -4,7 +4,10 @@
   ring.  Like ``evaluate_policy_op`` it has no PyTorch path: it needs the HIP extension and GPU tensors.
 * ``dqn_targets``: sample ring rows, gather the batch and build the TD targets from the target (and,
   for double Q-learning, the online) network.  CPU tensors take ``dqn_targets_ref``.
-* ``dqn_sample_rows_ref`` / ``dqn_targets_ref``: the oracles the kernel is held to.
+* ``dqn_sample_rows_ref`` / ``dqn_nstep_walk_ref`` / ``dqn_targets_ref``: the oracles the kernel is held to.
+
+``n_step > 1`` forms the n-step return at sample time: the sampled row walks forward through the ring
+(same env, next slot) before the bootstrap, see ``dqn_nstep_walk_ref``.
 """
 from __future__ import annotations
 
@@ -68,14 +71,69 @@ def dqn_sample_rows_ref(seed: int, update: int, B: int, filled: int) -> np.ndarr
     return ((x.astype(np.uint64) * np.uint64(filled)) >> np.uint64(32)).astype(np.int64)
 
 
+def check_nstep(n_step, newest, num_envs: int, filled: int):
+    """The arguments of an n-step walk, as the kernel's entry point checks them -> ``(n_step, newest)``."""
+    n_step = int(n_step)
+    if n_step < 1:
+        raise ValueError(f"n_step must be >= 1, got {n_step}")
+    if newest is None:
+        raise ValueError("n_step > 1 needs newest, the ring slot written last")
+    if num_envs < 1 or filled < 1 or filled % num_envs:
+        raise ValueError(f"an n-step walk needs whole slots: filled ({filled}) must be a multiple of num_envs ({num_envs})")
+    if not 0 <= int(newest) < filled // num_envs:
+        raise ValueError(f"newest must be in [0, {filled // num_envs}), got {newest}")
+    return n_step, int(newest)
+
+
+def dqn_nstep_walk_ref(rows, ring: ReplayRing, filled: int, newest: int, n_step: int, gamma: float,
+                       dtype=torch.float32):
+    """The n-step walk of ring rows ``rows`` [B] -> ``(last int64 [B], G [B], disc [B], m int64 [B])``:
+
+        last = r0; G = rew[r0]; disc = gamma; m = 1
+        while m < n_step and done[last] == 0 and slot(last) != newest:
+            last += N; if last >= filled: last -= filled      # same env, next slot, ring wrap
+            G += disc * rew[last]; disc *= gamma; m += 1
+
+    in ``dtype``, ``G`` and ``disc`` updated in that order one step at a time.  A terminal (1) or a truncation
+    (2) ends the walk, and so does the newest slot: the row then has an m-step return with m < n_step."""
+    N = int(ring.act.shape[1])
+    n_step, newest = check_nstep(n_step, newest, N, int(filled))
+    np_dtype = {torch.float32: np.float32, torch.float64: np.float64}[dtype]
+    rew = ring.rew.reshape(-1).cpu().numpy().astype(np_dtype)
+    done = ring.done.reshape(-1).cpu().numpy()
+    last = np.asarray(rows, np.int64).copy()
+    g = np_dtype(gamma)
+    G, disc, m = rew[last].copy(), np.full(last.shape, g, np_dtype), np.ones(last.shape, np.int64)
+    for _ in range(n_step - 1):
+        go = (m < n_step) & (done[last] == 0) & (last // N != newest)
+        if not go.any():
+            break
+        nxt = last + N
+        nxt = np.where(nxt >= filled, nxt - filled, nxt)
+        last = np.where(go, nxt, last)
+        G = np.where(go, (G + disc * rew[last]).astype(np_dtype), G)
+        disc = np.where(go, (disc * g).astype(np_dtype), disc)
+        m = m + go
+    return last, G, disc, m
+
+
 @torch.no_grad()
 def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: int, gamma: float, double_q: bool,
-                    seed: int, update: int, B: int, dtype=torch.float32, tree=None, beta: Optional[float] = None):
+                    seed: int, update: int, B: int, dtype=torch.float32, tree=None, beta: Optional[float] = None,
+                    n_step: int = 1, newest: Optional[int] = None):
     """-> ``(Xb [B, D], act_b [B] int32, y [B], idx [B] int64)`` in ``dtype``;
     ``y = rew + gamma * (done == 1 ? 0 : 1) * Q_target(nobs, a*)`` with ``a*`` the lowest-index argmax of the
     target (``double_q`` false) or online net.  With ``tree`` (the priority sum tree of ops/per.py) the rows
     are ``per_sample_rows_ref``'s and two more results follow: ``w [B] = (filled * leaf / total)^-beta`` and
-    ``wmax [1]``, its maximum."""
+    ``wmax [1]``, its maximum.
+
+    ``n_step > 1`` (with ``newest``, the ring slot written last) walks every sampled row forward
+    (``dqn_nstep_walk_ref``) and ``y = G + disc * (done[last] == 1 ? 0 : 1) * Q_target(nobs[last], a*)``, ``a*``
+    chosen at ``nobs[last]``; everything else still refers to the sampled row, and one more result follows at
+    the end: ``last [B]`` int64, the row the target bootstrapped from."""
+    if int(n_step) != 1:
+        return _dqn_targets_nstep_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree,
+                                      beta, n_step, newest)
     D = ring.obs.shape[-1]
     if tree is None:
         rows = dqn_sample_rows_ref(seed, update, B, filled)
@@ -96,21 +154,65 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
     return res if tree is None else res + (w, w.max().reshape(1))
 
 
+def _dqn_targets_nstep_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
+                           n_step, newest):
+    D = ring.obs.shape[-1]
+    dev = ring.obs.device
+    check_nstep(n_step, newest, int(ring.act.shape[1]), int(filled))
+    if tree is None:
+        rows = dqn_sample_rows_ref(seed, update, B, filled)
+    else:
+        from .per import per_sample_rows_ref, per_weights_ref
+
+        rows = per_sample_rows_ref(tree, seed, update, B, filled)
+        w = per_weights_ref(tree, rows, filled, beta, dtype).to(dev)
+    last_np, G, disc, _ = dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)
+    idx, last = torch.from_numpy(rows).to(dev), torch.from_numpy(last_np).to(dev)
+    nobs = ring.nobs.reshape(-1, D)[last].to(dtype)
+    q_t, _ = ref.trunk(target.to(dtype), nobs, D, H, A)
+    sel = ref.trunk(online.to(dtype), nobs, D, H, A)[0] if double_q else q_t
+    astar, _ = ref.greedy_from_logits(sel)
+    boot = (ring.done.reshape(-1)[last] != 1).to(dtype)
+    y = torch.from_numpy(G).to(dev) + torch.from_numpy(disc).to(dev) * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
+    res = (ring.obs.reshape(-1, D)[idx], ring.act.reshape(-1)[idx].to(torch.int32), y, idx)
+    if tree is not None:
+        res += (w, w.max().reshape(1))
+    return res + (last,)
+
+
 def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
                 gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32,
-                tree=None, beta: Optional[float] = None):
+                tree=None, beta: Optional[float] = None, n_step: int = 1, newest: Optional[int] = None):
     """Sample, gather and TD target in one launch -> ``(Xb, act_b, y, idx)``; ``out`` = the four tensors to
     write into (``idx`` int32 on the GPU, or None to skip it).  CPU tensors take the torch reference in
     ``dtype``; a GPU tensor without the extension raises.
 
     ``tree`` (the ``[2 * P2]`` priority sum tree of ops/per.py) selects the prioritised form: the rows come
     from the tree, and the result (and ``out``) is ``(Xb, act_b, y, idx, w, wmax)`` with the importance
-    weights ``w [B] = (filled * leaf / total)^-beta`` and ``wmax [1]`` their maximum; ``idx`` is mandatory."""
+    weights ``w [B] = (filled * leaf / total)^-beta`` and ``wmax [1]`` their maximum; ``idx`` is mandatory.
+
+    ``n_step > 1`` selects the n-step instance of the kernel (``dqn_targets_ref`` has the semantics): it needs
+    ``newest``, the ring slot written last, and takes the envs per slot from the ring.  The result then ends in
+    ``last [B]`` (int32 on the GPU), the row each target bootstrapped from; an ``out`` may carry it as one more
+    trailing tensor, or leave it out (or None) to skip it.  ``n_step == 1`` is the one-step launch as it was."""
     from . import use_hip, hip
 
     per = tree is not None
     if per and not (beta is not None and 0.0 < beta <= 1.0):
         raise ValueError(f"the prioritised form needs beta in (0, 1], got {beta}")
+    n_step = int(n_step)
+    base = 6 if per else 4
+    if n_step == 1 and out is not None and len(out) == base + 1:  # a one-step target bootstraps from its own row
+        dqn_targets(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, tuple(out[:base]), dtype,
+                    tree, beta)
+        if out[base] is not None:
+            if out[3] is None:
+                raise ValueError("at n_step = 1 last is idx: it cannot be written without idx")
+            out[base].copy_(out[3])
+        return out
+    if n_step != 1:
+        return _dqn_targets_nstep(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, out, dtype,
+                                  tree, beta, n_step, newest)
     if not use_hip(target):
         res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta)
         if out is not None:
@@ -139,4 +241,50 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
     Xb, act_b, y, idx = out
     hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
                       ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), Xb, act_b, y, idx)
+    return out
+
+
+def _dqn_targets_nstep(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, out, dtype, tree, beta,
+                       n_step, newest):
+    from . import use_hip, hip
+
+    per = tree is not None
+    base = 6 if per else 4
+    N = int(ring.act.shape[1])
+    n_step, newest = check_nstep(n_step, newest, N, int(filled))
+    if out is not None and len(out) not in (base, base + 1):
+        raise ValueError(f"out must hold {base} tensors, or {base + 1} with a trailing last; got {len(out)}")
+    if not use_hip(target):
+        res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
+                              n_step, newest)
+        if out is not None:
+            for dst, src in zip(out, res):
+                if dst is not None:
+                    dst.copy_(src)
+            return out
+        return res
+    dev = target.device
+    D = ring.obs.shape[-1]
+    if out is None:
+        out = (torch.empty(B, D, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        if per:
+            out += (torch.empty(B, device=dev), torch.empty(1, device=dev))
+        out += (torch.empty(B, dtype=torch.int32, device=dev),)
+    if out[2].numel() != B:
+        raise ValueError(f"y must hold {B} targets, got {out[2].numel()}")
+    last = out[base] if len(out) > base else None
+    if per:
+        Xb, act_b, y, idx, w, wmax = out[:6]
+        if idx is None:
+            raise ValueError("the prioritised form writes idx: it cannot be skipped")
+        hip().dqn_targets_per_nstep(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs,
+                                    ring.act, ring.rew, ring.done, tree, int(filled), float(gamma), bool(double_q),
+                                    float(beta), int(seed), int(update), n_step, newest, Xb, act_b, y, idx, w, wmax,
+                                    last)
+        return out
+    Xb, act_b, y, idx = out[:4]
+    hip().dqn_targets_nstep(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act,
+                            ring.rew, ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update),
+                            n_step, newest, Xb, act_b, y, idx, last)
     return out

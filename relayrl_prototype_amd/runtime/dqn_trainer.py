@@ -23,8 +23,15 @@ priority), and per update ``dqn_targets`` (prioritised: rows from the tree, impo
 their maximum), ``mlp_grad(Q_TD, row_w, w_norm, td_abs)``, Adam, ``per_update`` of the sampled rows to
 ``(|td| + per_eps)^per_alpha``.  The host owns the beta anneal (``beta_at``) like the epsilon schedule.
 
-Left for later: several ranks, hipGraph capture, n-step returns, serving the policy to agents (the
-trainer exposes no ``learner``, so a TrainingServer engine publishes no model).
+``n_step > 1`` turns the TD target into the n-step return.  The ring is time-major, so the successor of a
+transition is the same env in the next slot: ``dqn_targets`` walks the sampled row forward through the ring
+before the bootstrap forward pass, summing discounted rewards until n steps, an episode end (a terminal
+drops the bootstrap, a truncation keeps it) or the newest slot, ``(cursor - 1) % buffer_slots``.  No row is
+excluded from sampling and nothing new is stored: the actor, the ring, the samplers, the tree and the
+checkpoint are those of one-step DQN, and ``n_step = 1`` runs its kernels.
+
+Left for later: several ranks, hipGraph capture, serving the policy to agents (the trainer exposes no
+``learner``, so a TrainingServer engine publishes no model).
 """
 from __future__ import annotations
 
@@ -68,8 +75,18 @@ class DQNConfig:
     per_beta_end: float = 1.0
     per_beta_epochs: int = 500
     per_eps: float = 1e-3
+    n_step: int = 1                 # n-step returns, formed from the ring at sample time (1: one-step TD)
 
     def __post_init__(self):
+        try:  # hyperparameters of a TrainingServer arrive as strings ("3")
+            n = int(self.n_step)
+        except (TypeError, ValueError):
+            raise ValueError(f"n_step must be an integer, got {self.n_step!r}") from None
+        if isinstance(self.n_step, float) and n != self.n_step:
+            raise ValueError(f"n_step must be an integer, got {self.n_step!r}")
+        self.n_step = n
+        if not 1 <= self.n_step <= int(self.buffer_slots):
+            raise ValueError(f"n_step must be in [1, buffer_slots = {self.buffer_slots}], got {self.n_step}")
         # hyperparameters of a TrainingServer arrive as strings ("true")
         if isinstance(self.prioritized, str):
             word = self.prioritized.strip().lower()
@@ -197,16 +214,19 @@ class DQNTrainer:
         """One gradient step on a freshly sampled batch; the target network follows on its schedule."""
         cfg = self.cfg
         filled = min(self.slots_written, cfg.buffer_slots) * cfg.num_envs
+        # n-step walks end at the slot the rollout wrote last: the one before the cursor
+        nstep = dict(n_step=cfg.n_step, newest=(self.cursor - 1) % cfg.buffer_slots) if cfg.n_step > 1 else {}
         if self.per is None:
             dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
-                        self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None))
+                        self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None),
+                        **nstep)
             mlp_grad(GradHead.Q_TD, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
             self.q.apply(self.slab)
         else:
             dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, tree=self.per.tree, beta=self.last_beta,
-                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax))
+                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep)
             mlp_grad(GradHead.Q_TD, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
                      w_norm=self.wmax, td_abs=self.td_abs)
@@ -258,7 +278,7 @@ class DQNTrainer:
             if ls[5] > 0:
                 loss_q, q_vals = ls[0] / ls[5], ls[4] / ls[5]
         out.update(LossQ=loss_q, QVals=q_vals, Epsilon=self.last_epsilon, Updates=self.updates,
-                   EnvSteps=self.env_steps, WorldSize=1)
+                   EnvSteps=self.env_steps, WorldSize=1, NStep=self.cfg.n_step)
         if self.per is not None:
             out.update(Beta=self.last_beta, PriorityMax=float(self.per.pmax.item()))
         return out

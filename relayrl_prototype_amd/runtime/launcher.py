@@ -81,6 +81,14 @@ PRESETS: Dict[str, Preset] = {
                 "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
                 "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
                 "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3}),
+    "cartpole-dqn-nstep": Preset(
+        "cartpole-dqn-nstep", "cartpole-dqn-per with 3-step returns, formed from the replay ring inside the TD-target "
+        "kernel at sample time (--set n_step=3 on either DQN preset is the same mechanism)",
+        "vec", {"env": "CartPole-v1", "algo": "dqn", "num_envs": 1024, "rollout_len": 4, "buffer_slots": 256,
+                "batch_size": 1024, "updates_per_epoch": 4, "gamma": 0.99, "q_lr": 5e-4, "eps_start": 1.0,
+                "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
+                "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
+                "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3}),
 }
 
 
