@@ -26,6 +26,12 @@ line goes to ``profiles/dqn_per_bench.jsonl`` unless ``--out`` names another fil
 prioritised (``targets_per_n<K>_us``), and the epoch of both DQN presets at ``n_step = 1`` and at the first K
 (``epoch_n<K>_us`` / ``epoch_per_n<K>_us``).  The line goes to ``profiles/dqn_nstep_bench.jsonl`` unless
 ``--out`` names another file.
+
+``--dueling`` adds, from the same process, the dueling head against the plain one at the shapes of
+``cartpole-dqn`` (``uniform``) and ``cartpole-dqn-nstep`` (``per_n3``; with the dueling head it is the
+``cartpole-dqn-dueling`` preset): ``epoch_<shape>_<plain|dueling>_us`` and the microseconds per launch of
+``dqn_rollout``, ``dqn_targets`` and ``mlp_grad`` (``<kernel>_<shape>_<plain|dueling>_us``).  The line goes to
+``profiles/dqn_dueling_bench.jsonl`` unless ``--out`` names another file.
 """
 import argparse
 import json
@@ -139,6 +145,65 @@ def nstep_records(a, dev, event_us):
     return rec
 
 
+def dueling_records(a, dev, event_us):
+    """The dueling head against the plain one in one process, at the shapes of ``cartpole-dqn`` (uniform, one-step)
+    and ``cartpole-dqn-nstep`` (prioritised, 3-step: with ``dueling`` it is the ``cartpole-dqn-dueling`` preset):
+    the epoch, and the three launches that stage the Q-network."""
+    from relayrl_prototype_amd.ops import dqn_rollout, dqn_targets, mlp_grad
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    assert PRESETS["cartpole-dqn-dueling"].overrides == dict(PRESETS["cartpole-dqn-nstep"].overrides, dueling=True)
+    rec = {}
+    for preset, tag in (("cartpole-dqn", "uniform"), ("cartpole-dqn-nstep", "per_n3")):
+        for dueling in (False, True):
+            cfg = DQNConfig(**dict(PRESETS[preset].overrides, dueling=dueling))
+            tr = DQNTrainer(cfg, device=dev)
+            for _ in range(a.warmup):
+                tr.train_epoch()
+            assert tr.updates > 0, "the warm-up must reach learning_starts"
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.epochs):
+                tr.train_epoch()
+            torch.cuda.synchronize()
+            key = f"{tag}_{'dueling' if dueling else 'plain'}"
+            rec[f"epoch_{key}_us"] = round(1e6 * (time.perf_counter() - t0) / a.epochs, 2)
+            N, T, B, C = cfg.num_envs, cfg.rollout_len, cfg.batch_size, cfg.buffer_slots
+            filled = min(tr.slots_written, C) * N
+            duel = dict(dueling=True) if dueling else {}
+            tkw = dict(duel)
+            gkw = {}
+            out = (tr.Xb, tr.act_b, tr.y, None)
+            if tr.per is not None:
+                tkw.update(tree=tr.per.tree, beta=0.7)
+                gkw = dict(row_w=tr.w, w_norm=tr.wmax, td_abs=tr.td_abs)
+                out = (tr.Xb, tr.act_b, tr.y, tr.idx, tr.w, tr.wmax)
+            if cfg.n_step > 1:
+                tkw.update(n_step=cfg.n_step, newest=(tr.cursor - 1) % C)
+
+            def rollout():  # the same slot and step every time: timing only
+                dqn_rollout(tr.env_id, tr.q.params, cfg.hidden, T, 0, tr.ring, tr.state, tr.ep_len, tr.ep_ret,
+                            tr.ep_stats, seed=tr.env_seed, step0=0, epsilon=0.1, reset_all=False,
+                            max_steps=tr.max_steps, **duel)
+
+            def targets():
+                dqn_targets(tr.q.params, tr.target, cfg.hidden, tr.A, tr.ring, filled, cfg.gamma, cfg.double_q,
+                            tr.sample_seed, 7, B, out=out, **tkw)
+
+            def grad_q():
+                mlp_grad(tr.head, tr.q.params, tr.Xb, tr.A, cfg.hidden, act=tr.act_b, ret=tr.y,
+                         clip_eps=cfg.huber_delta, grad_slab=tr.slab, loss_slab=tr.loss, **gkw)
+
+            for name, fn in (("dqn_rollout", rollout), ("dqn_targets", targets), ("mlp_grad", grad_q)):
+                fn()
+                torch.cuda.synchronize()
+                med, lo, hi = event_us(fn, a.iters, a.reps)
+                rec[f"{name}_{key}_us"] = med
+                rec[f"{name}_{key}_us_range"] = [lo, hi]
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2000)
@@ -150,11 +215,13 @@ def main():
     ap.add_argument("--prioritized", action="store_true", help="also measure the cartpole-dqn-per preset")
     ap.add_argument("--n-step", type=int, nargs="+", default=[], metavar="K",
                     help="also measure n-step returns at every K against one-step")
+    ap.add_argument("--dueling", action="store_true", help="also measure the dueling head against the plain one")
     a = ap.parse_args()
     if any(k < 1 for k in a.n_step):
         raise SystemExit("--n-step takes values >= 1")
-    if (a.prioritized or a.n_step) and not a.out:
+    if (a.prioritized or a.n_step or a.dueling) and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "dqn_dueling_bench.jsonl" if a.dueling else
                              "dqn_nstep_bench.jsonl" if a.n_step else "dqn_per_bench.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("dqn_bench needs a GPU: a CPU timing says nothing about the MI355X")
@@ -216,6 +283,8 @@ def main():
         rec.update(per_records(a, dev, event_us))
     if a.n_step:
         rec.update(nstep_records(a, dev, event_us))
+    if a.dueling:
+        rec.update(dueling_records(a, dev, event_us))
     rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
     line = json.dumps(rec)
     print(line, flush=True)

@@ -30,17 +30,25 @@ std::tuple<int64_t, int64_t> check_ring(int64_t D, const Tensor& obs, const Tens
   return {C, N};
 }
 
+// Outputs of a Q-network over A actions: the dueling net has one more, the state value, and kMaxAct = 16
+// outputs are what the kernels hold.
+int64_t dueling_outputs(int64_t A, bool dueling) {
+  TORCH_CHECK(!dueling || A <= 15, "a dueling net has A + 1 outputs: act dim must be in [1, 15], got ", A);
+  return A + (dueling ? 1 : 0);
+}
+
 // Returns the kernel's code for a launch that would wrap (-4, nothing written); raises for anything else.
 int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
                     const Tensor& ep_len, const Tensor& ep_ret, const Tensor& obs, const Tensor& nobs,
                     const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& ep_stats, int64_t seed,
-                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps) {
+                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling) {
   int D = 0, A = 0, NS = 0, ms = 0;
   TORCH_CHECK(rrl_env_dims((int)env, &D, &A, &NS, &ms) == 0, "unknown device env id ", env);
   TORCH_CHECK(env != ENV_HALFCHEETAH, "dqn_rollout takes the discrete device envs");
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(T >= 1 && max_steps >= 1, "T and max_steps must be >= 1");
-  check(params, "params", at::kFloat, (int64_t)H * D + H + H * H + H + (int64_t)A * H + A);
+  const int64_t AO = dueling_outputs(A, dueling);
+  check(params, "params", at::kFloat, (int64_t)H * D + H + H * H + H + AO * H + AO);
   auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
   check(state, "state", at::kFloat, N * NS);
   check(ep_len, "ep_len", at::kInt, N);
@@ -52,7 +60,7 @@ int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int
                                  obs.data_ptr<float>(), nobs.data_ptr<float>(), act.data_ptr<int>(),
                                  rew.data_ptr<float>(), done.data_ptr<float>(), ep_stats.data_ptr<float>(),
                                  (uint64_t)seed, (uint64_t)step0, (float)epsilon, reset_all ? 1 : 0, (int)max_steps,
-                                 grid_cus(), cur_stream());
+                                 dueling ? 1 : 0, grid_cus(), cur_stream());
   if (rc == -4) return rc;
   check_rc(rc, "dqn_rollout");
   return 0;
@@ -66,15 +74,16 @@ struct TargetCall {
 
 TargetCall check_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
                          const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled,
-                         bool double_q, const Tensor& Xb, const Tensor& act_b, const Tensor& y) {
+                         bool double_q, const Tensor& Xb, const Tensor& act_b, const Tensor& y, bool dueling) {
   TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
   const int64_t D = obs.size(2);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
+  const int64_t AO = dueling_outputs(A, dueling);
   auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
   TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
-  const int64_t P = H * D + H + H * H + H + A * H + A;
+  const int64_t P = H * D + H + H * H + H + AO * H + AO;
   check(target, "target", at::kFloat, P);
   const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
   TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
@@ -90,8 +99,10 @@ TargetCall check_targets(const OptT& online, const Tensor& target, int64_t H, in
 void dqn_targets_nstep(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
                        const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled,
                        double gamma, bool double_q, int64_t sample_key, int64_t update, int64_t n_step, int64_t newest,
-                       const Tensor& Xb, const Tensor& act_b, const Tensor& y, const OptT& idx, const OptT& last) {
-  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y);
+                       const Tensor& Xb, const Tensor& act_b, const Tensor& y, const OptT& idx, const OptT& last,
+                       bool dueling) {
+  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y,
+                                     dueling);
   TORCH_CHECK(std::abs(n_step) < (int64_t)INT32_MAX && std::abs(newest) < (int64_t)INT32_MAX,
               "n_step / newest out of range");
   int* ix = opt_ptr<int>(idx, "idx", at::kInt, c.B);
@@ -100,22 +111,23 @@ void dqn_targets_nstep(const OptT& online, const Tensor& target, int64_t H, int6
                                  act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(),
                                  (long long)filled, (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0,
                                  (uint64_t)sample_key, (uint64_t)update, (int)n_step, (int)c.N, (int)newest,
-                                 Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(), ix, la, grid_cus(),
-                                 cur_stream()),
+                                 Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(), ix, la,
+                                 dueling ? 1 : 0, grid_cus(), cur_stream()),
            "dqn_targets_nstep");
 }
 
 void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
                  const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
                  int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
-                 const OptT& idx) {
-  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y);
+                 const OptT& idx, bool dueling) {
+  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y,
+                                     dueling);
   int* ix = opt_ptr<int>(idx, "idx", at::kInt, c.B);
   check_rc(rrl_dqn_targets(c.online, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
                            act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(), (long long)filled,
                            (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0, (uint64_t)sample_key,
                            (uint64_t)update, Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(), ix,
-                           grid_cus(), cur_stream()),
+                           dueling ? 1 : 0, grid_cus(), cur_stream()),
            "dqn_targets");
 }
 
@@ -163,8 +175,9 @@ void dqn_targets_per_nstep(const OptT& online, const Tensor& target, int64_t H, 
                            const Tensor& tree, int64_t filled, double gamma, bool double_q, double beta,
                            int64_t sample_key, int64_t update, int64_t n_step, int64_t newest, const Tensor& Xb,
                            const Tensor& act_b, const Tensor& y, const Tensor& idx, const Tensor& w, const Tensor& wmax,
-                           const OptT& last) {
-  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y);
+                           const OptT& last, bool dueling) {
+  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y,
+                                     dueling);
   TORCH_CHECK(beta > 0.0 && beta <= 1.0, "beta must be in (0, 1], got ", beta);
   TORCH_CHECK(std::abs(n_step) < (int64_t)INT32_MAX && std::abs(newest) < (int64_t)INT32_MAX,
               "n_step / newest out of range");
@@ -178,8 +191,8 @@ void dqn_targets_per_nstep(const OptT& online, const Tensor& target, int64_t H, 
                                      (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0, (float)beta,
                                      (uint64_t)sample_key, (uint64_t)update, (int)n_step, (int)c.N, (int)newest,
                                      Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(),
-                                     idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), la, grid_cus(),
-                                     cur_stream()),
+                                     idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), la,
+                                     dueling ? 1 : 0, grid_cus(), cur_stream()),
            "dqn_targets_per_nstep");
 }
 
@@ -187,8 +200,9 @@ void dqn_targets_per(const OptT& online, const Tensor& target, int64_t H, int64_
                      const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& tree,
                      int64_t filled, double gamma, bool double_q, double beta, int64_t sample_key, int64_t update,
                      const Tensor& Xb, const Tensor& act_b, const Tensor& y, const Tensor& idx, const Tensor& w,
-                     const Tensor& wmax) {
-  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y);
+                     const Tensor& wmax, bool dueling) {
+  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y,
+                                     dueling);
   TORCH_CHECK(beta > 0.0 && beta <= 1.0, "beta must be in (0, 1], got ", beta);
   check_tree(tree, wmax, "wmax", c.L);
   check(idx, "idx", at::kInt, c.B);
@@ -198,8 +212,8 @@ void dqn_targets_per(const OptT& online, const Tensor& target, int64_t H, int64_
                                tree.data_ptr<float>(), (long long)c.L, (long long)filled, (int)c.B, (int)c.D, (int)A,
                                (int)H, (float)gamma, double_q ? 1 : 0, (float)beta, (uint64_t)sample_key,
                                (uint64_t)update, Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(),
-                               idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), grid_cus(),
-                               cur_stream()),
+                               idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), dueling ? 1 : 0,
+                               grid_cus(), cur_stream()),
            "dqn_targets_per");
 }
 
@@ -216,23 +230,25 @@ void register_dqn_ops(pybind11::module_& m) {
         py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("tree"),
         py::arg("filled"), py::arg("gamma"), py::arg("double_q"), py::arg("beta"), py::arg("sample_key"),
         py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("w"),
-        py::arg("wmax"));
+        py::arg("wmax"), py::arg("dueling") = false);
   m.def("dqn_rollout_grid", &dqn_rollout_grid);
   m.def("dqn_rollout", &dqn_rollout, py::arg("env"), py::arg("params"), py::arg("H"), py::arg("T"), py::arg("slot0"),
         py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"), py::arg("act"),
         py::arg("rew"), py::arg("done"), py::arg("ep_stats"), py::arg("seed"), py::arg("step0"), py::arg("epsilon"),
-        py::arg("reset_all"), py::arg("max_steps"));
+        py::arg("reset_all"), py::arg("max_steps"), py::arg("dueling") = false);
   m.def("dqn_targets", &dqn_targets, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"), py::arg("obs"),
         py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"), py::arg("gamma"),
         py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"),
-        py::arg("idx"));
+        py::arg("idx"), py::arg("dueling") = false);
   m.def("dqn_targets_nstep", &dqn_targets_nstep, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
         py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"),
         py::arg("gamma"), py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("n_step"),
-        py::arg("newest"), py::arg("Xb"), py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("last"));
+        py::arg("newest"), py::arg("Xb"), py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("last"),
+        py::arg("dueling") = false);
   m.def("dqn_targets_per_nstep", &dqn_targets_per_nstep, py::arg("online"), py::arg("target"), py::arg("H"),
         py::arg("A"), py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"),
         py::arg("tree"), py::arg("filled"), py::arg("gamma"), py::arg("double_q"), py::arg("beta"),
         py::arg("sample_key"), py::arg("update"), py::arg("n_step"), py::arg("newest"), py::arg("Xb"),
-        py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("w"), py::arg("wmax"), py::arg("last"));
+        py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("w"), py::arg("wmax"), py::arg("last"),
+        py::arg("dueling") = false);
 }

@@ -109,13 +109,15 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_TD, "bad head");
+  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_DUEL, "bad head");
   TORCH_CHECK(B * std::max<int64_t>(D, A) < (int64_t)INT32_MAX, "batch too large for 32-bit row indexing");
   const bool gauss = head == HEAD_PPO_GAUSS || head == HEAD_PG_GAUSS;
   const bool cat = head == HEAD_PG_CAT || head == HEAD_PPO_CAT;
   const bool value = head == HEAD_VALUE_MSE;
-  const bool qtd = head == HEAD_Q_TD;  // reads act + ret; no advantages
-  const int64_t P = flat_size(D, H, value ? 1 : A, gauss);
+  const bool duel = head == HEAD_Q_DUEL;       // the net has A + 1 outputs: A advantages and the state value
+  const bool qtd = head == HEAD_Q_TD || duel;  // reads act + ret; no advantages
+  TORCH_CHECK(!duel || A <= 15, "a dueling net has A + 1 outputs: act dim must be in [1, 15], got ", A);
+  const int64_t P = flat_size(D, H, value ? 1 : (duel ? A + 1 : A), gauss);
   check_numel(params, "params", P);
   const int64_t nslab = mlp_grad_slabs(B);
   check(grad_slab, "grad_slab", at::kFloat, nslab * P);
@@ -140,7 +142,7 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   const float* wn = opt_ptr<const float>(w_norm, "w_norm", at::kFloat, 1);
   float* ta = opt_ptr<float>(td_abs, "td_abs", at::kFloat, B);
   TORCH_CHECK((rw == nullptr) == (wn == nullptr), "row_w and w_norm come together");
-  TORCH_CHECK(qtd || (rw == nullptr && ta == nullptr), "row_w / w_norm / td_abs apply to the Q_TD head only");
+  TORCH_CHECK(qtd || (rw == nullptr && ta == nullptr), "row_w / w_norm / td_abs apply to the Q heads only");
   const int rc = rrl_mlp_grad_weighted((int)head, params.data_ptr<float>(), X.data_ptr<float>(), (int)B, (int)D,
                                        (int)A, (int)H, m, a, ac, ad, rt, lpo, st, (float)inv_B, (float)clip_eps,
                                        (float)ent_coef, grad_slab.data_ptr<float>(), loss_slab.data_ptr<float>(),
@@ -442,13 +444,15 @@ EvalShape check_eval_bufs(int64_t D, const Tensor& ep_ret, const Tensor& ep_len,
 // Fused policy evaluation (evaluate.hip): every env runs E complete episodes under fixed weights.
 void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
               const Tensor& ep_code, const OptT& tr_obs, const OptT& tr_act, const OptT& tr_rew, const OptT& tr_done,
-              int64_t seed, int64_t step0, bool greedy, int64_t max_steps) {
+              int64_t seed, int64_t step0, bool greedy, int64_t max_steps, bool dueling) {
   auto [D, A, NS, ms] = env_dims(env);
   (void)NS;
   (void)ms;
   TORCH_CHECK(env != ENV_HALFCHEETAH, "evaluate takes the discrete device envs; use evaluate_cont for env 4");
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  check_exact(params, "params", at::kFloat, flat_size(D, H, A, false));
+  TORCH_CHECK(!dueling || greedy, "a dueling Q-network is evaluated greedily: softmax-of-Q is not its policy");
+  TORCH_CHECK(!dueling || A <= 15, "a dueling net has A + 1 outputs: act dim must be in [1, 15], got ", A);
+  check_exact(params, "params", at::kFloat, flat_size(D, H, A + (dueling ? 1 : 0), false));
   const EvalShape sh = check_eval_bufs(D, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done, at::kInt, 0,
                                        max_steps);
   const bool tr = sh.Tc > 0;
@@ -456,7 +460,8 @@ void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret
                         ep_ret.data_ptr<float>(), ep_len.data_ptr<int>(), ep_code.data_ptr<int>(),
                         tr ? tr_obs->data_ptr<float>() : nullptr, tr ? tr_act->data_ptr<int>() : nullptr,
                         tr ? tr_rew->data_ptr<float>() : nullptr, tr ? tr_done->data_ptr<float>() : nullptr,
-                        (uint64_t)seed, (uint64_t)step0, greedy ? 1 : 0, (int)max_steps, num_cus(), cur_stream()),
+                        (uint64_t)seed, (uint64_t)step0, greedy ? 1 : 0, (int)max_steps, dueling ? 1 : 0, num_cus(),
+                        cur_stream()),
            "evaluate");
 }
 
@@ -547,7 +552,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("evaluate", &evaluate, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("H"),
         pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"), pybind11::arg("tr_obs"),
         pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"), pybind11::arg("seed"),
-        pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"));
+        pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"),
+        pybind11::arg("dueling") = false);
   m.def("evaluate_cont", &evaluate_cont, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("env_consts"),
         pybind11::arg("H"), pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"),
         pybind11::arg("tr_obs"), pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"),
@@ -557,7 +563,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("FWD_MODES") = pybind11::dict(RRL_ENUM(MODE_VALUE), RRL_ENUM(MODE_CAT_SAMPLE), RRL_ENUM(MODE_CAT_EVAL),
                                        RRL_ENUM(MODE_LOGITS), RRL_ENUM(MODE_GAUSS_SAMPLE), RRL_ENUM(MODE_GAUSS_EVAL));
   m.attr("GRAD_HEADS") = pybind11::dict(RRL_ENUM(HEAD_PG_CAT), RRL_ENUM(HEAD_VALUE_MSE), RRL_ENUM(HEAD_PPO_CAT),
-                                        RRL_ENUM(HEAD_PPO_GAUSS), RRL_ENUM(HEAD_PG_GAUSS), RRL_ENUM(HEAD_Q_TD));
+                                        RRL_ENUM(HEAD_PPO_GAUSS), RRL_ENUM(HEAD_PG_GAUSS), RRL_ENUM(HEAD_Q_TD),
+                                        RRL_ENUM(HEAD_Q_DUEL));
   m.attr("ENV_IDS") = pybind11::dict(RRL_ENUM(ENV_CARTPOLE), RRL_ENUM(ENV_MOUNTAINCAR), RRL_ENUM(ENV_ACROBOT),
                                      RRL_ENUM(ENV_LUNARLANDER), RRL_ENUM(ENV_HALFCHEETAH));
 #undef RRL_ENUM

@@ -25,6 +25,7 @@ enum GradHead : int {
   HEAD_PPO_GAUSS = 3,  // PPO clipped surrogate, diagonal Gaussian
   HEAD_PG_GAUSS = 4,   // REINFORCE / A2C with a Gaussian policy
   HEAD_Q_TD = 5,       // DQN: loss = mean(huber(Q(x)[act] - ret, delta)); delta travels in clip_eps
+  HEAD_Q_DUEL = 6,     // HEAD_Q_TD on a dueling net of A + 1 outputs: Q = out[A] + out[act] - mean(out[0 .. A-1])
 };
 
 enum EnvId : int { ENV_CARTPOLE = 0, ENV_MOUNTAINCAR = 1, ENV_ACROBOT = 2, ENV_LUNARLANDER = 3, ENV_HALFCHEETAH = 4 };
@@ -44,12 +45,17 @@ int rrl_set_value_fwd_mode(int mode);
 
 // ---- mlp_grad.hip
 // head: a GradHead.  HEAD_Q_TD reads act and ret (the TD target) and takes its Huber threshold delta
-// from clip_eps, which it has no other use for; mask, adv, logp_old and ent_coef are ignored
+// from clip_eps, which it has no other use for; mask, adv, logp_old and ent_coef are ignored.
+// HEAD_Q_DUEL is HEAD_Q_TD on the dueling net: A stays the number of actions, params / P / the slabs are
+// those of A + 1 outputs (rows 0 .. A-1 the advantages, row A the state value), and in fp32
+//   s = out[0]; s += out[k] (k = 1 .. A-1, ascending);  m = s / A;  Q(a) = (out[A] - m) + out[a].
+// -2: A outside [1, 16] or D outside [1, 32]; -3: H not 64 / 128, or HEAD_Q_DUEL with A > 15; -4: the net
+// and the staging do not fit the LDS
 int rrl_mlp_grad(int head, const float* params, const float* X, int B, int D, int A, int H, const float* mask,
                  const int* act, const float* actc, const float* adv, const float* ret, const float* logp_old,
                  const float* adv_stats, float inv_B, float clip_eps, float ent_coef, float* grad_slab,
                  float* loss_slab, int P, const int* nvalid, const float* inv_B_dev, int num_cu, void* stream);
-// rrl_mlp_grad plus the per-row weights of prioritised replay, read by HEAD_Q_TD alone: with w_i =
+// rrl_mlp_grad plus the per-row weights of prioritised replay, read by HEAD_Q_TD and HEAD_Q_DUEL alone: with w_i =
 // row_w[i] / *w_norm the row's loss is w_i * huber and its gradient is scaled by w_i; td_abs[i] (may be
 // null) receives |Q(x_i)[act_i] - ret_i| of every valid row.  row_w and w_norm come together or not at
 // all (-1); all three null is rrl_mlp_grad
@@ -121,10 +127,12 @@ int rrl_rollout_cont(int env, const float* params, const float* env_consts, int 
 // Every env runs E complete episodes (greedy: argmax / mu instead of the rollout kernels' draws) into
 // ep_ret / ep_len / ep_code [E][N] (code 1 terminal, 2 time limit).  tr_*: optional trace of the first Tc
 // steps, all four pointers or none (then Tc may be 0).  -2: N, E, Tc or max_steps below 1, or
-// E * max_steps >= 2^31; -3: unsupported H or env
+// E * max_steps >= 2^31; -3: unsupported H or env.  dueling != 0 (rrl_evaluate only): params is a dueling
+// Q-network of A + 1 outputs (HEAD_Q_DUEL) and the greedy action is the lowest-index argmax of its A
+// advantage outputs; -3 with greedy == 0, which is not a policy of that net
 int rrl_evaluate(int env, const float* params, int N, int E, int Tc, int H, float* ep_ret, int* ep_len,
                  int* ep_code, float* tr_obs, int* tr_act, float* tr_rew, float* tr_done, uint64_t seed,
-                 uint64_t step0, int greedy, int max_steps, int num_cu, void* stream);
+                 uint64_t step0, int greedy, int max_steps, int dueling, int num_cu, void* stream);
 // continuous-action envs (ENV_HALFCHEETAH); tr_act is [Tc][N][A]
 int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int N, int E, int Tc, int H,
                       float* ep_ret, int* ep_len, int* ep_code, float* tr_obs, float* tr_act, float* tr_rew,
@@ -137,22 +145,26 @@ int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int
 // running, 1 terminal, 2 time limit).  state / ep_len / ep_ret / reset_all / max_steps / ep_stats as
 // rrl_rollout, with ep_stats [rrl_dqn_rollout_grid()][8].  -1: a null pointer; -2: N, T, C or max_steps
 // below 1; -3: unsupported H or env; -4 (nothing written): a launch that would wrap, i.e. unless
-// C % T == 0, slot0 % T == 0 and slot0 + T <= C
+// C % T == 0, slot0 % T == 0 and slot0 + T <= C.  dueling != 0: params is a dueling Q-network of A + 1
+// outputs (HEAD_Q_DUEL) and the greedy action is the lowest-index argmax of its A advantage outputs
 int rrl_dqn_rollout_grid(int N, int num_cu);
 int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, int slot0, float* state, int* ep_len,
                     float* ep_ret, float* obs, float* nobs, int* act, float* rew, float* done, float* ep_stats,
-                    uint64_t seed, uint64_t step0, float epsilon, int reset_all, int max_steps, int num_cu,
-                    void* stream);
+                    uint64_t seed, uint64_t step0, float epsilon, int reset_all, int max_steps, int dueling,
+                    int num_cu, void* stream);
 // Batch row b of update `update` samples ring row r = (philox((b, update, 0), sample_key).x * filled) >> 32
 // of the first `filled` rows ([slot][env] order), gathers obs[r] -> Xb[b], act[r] -> act_b[b], r -> idx[b]
 // (idx may be null) and writes y[b] = rew[r] + gamma * (done[r] == 1 ? 0 : 1) * Q_target(nobs[r], a*), a* =
 // the lowest-index argmax of Q_target (double_q = 0) or Q_online (double_q = 1; online may be null
 // otherwise).  -1: a null pointer; -2: filled < 1 or >= 2^31, or B < 1; -3: H not 64 / 128, D outside
-// [1, 16] or A outside [1, 16]
+// [1, 16] or A outside [1, 16].  dueling != 0 (all four forms): online and target are dueling nets of A + 1
+// outputs (HEAD_Q_DUEL has the combine), a* is the lowest-index argmax of the selecting net's A advantage
+// outputs and Q_target(., a*) the dueling Q of the target net; -3 then also for A > 15.  The sampled rows and
+// every output but y do not depend on it
 int rrl_dqn_targets(const float* online, const float* target, const float* obs, const float* nobs, const int* act,
                     const float* rew, const float* done, long long filled, int B, int D, int A, int H, float gamma,
                     int double_q, uint64_t sample_key, uint64_t update, float* Xb, int* act_b, float* y, int* idx,
-                    int num_cu, void* stream);
+                    int dueling, int num_cu, void* stream);
 // The prioritised form: batch row b descends the sum tree of per.hip (L = the ring's C * N rows, leaf of
 // row r at tree[P2 + r]) with m = (b + u01(philox((b, update, 1), sample_key).x)) * (tree[1] / B), exactly
 // log2(P2) steps `if (m >= left && right > 0) { m -= left; go right } else go left`, and clamps the row to
@@ -163,7 +175,7 @@ int rrl_dqn_targets_per(const float* online, const float* target, const float* o
                         const int* act, const float* rew, const float* done, const float* tree, long long L,
                         long long filled, int B, int D, int A, int H, float gamma, int double_q, float beta,
                         uint64_t sample_key, uint64_t update, float* Xb, int* act_b, float* y, int* idx, float* w,
-                        float* wmax, int num_cu, void* stream);
+                        float* wmax, int dueling, int num_cu, void* stream);
 // The n-step forms of the two above.  The ring is time-major with N envs per slot, `filled` a multiple of N
 // and `newest` the slot written last.  The sampled row r0 walks forward before the bootstrap:
 //   last = r0; G = rew[r0]; disc = gamma; m = 1
@@ -176,13 +188,14 @@ int rrl_dqn_targets_per(const float* online, const float* target, const float* o
 int rrl_dqn_targets_nstep(const float* online, const float* target, const float* obs, const float* nobs,
                           const int* act, const float* rew, const float* done, long long filled, int B, int D, int A,
                           int H, float gamma, int double_q, uint64_t sample_key, uint64_t update, int n_step, int N,
-                          int newest, float* Xb, int* act_b, float* y, int* idx, int* last, int num_cu, void* stream);
+                          int newest, float* Xb, int* act_b, float* y, int* idx, int* last, int dueling, int num_cu,
+                          void* stream);
 int rrl_dqn_targets_per_nstep(const float* online, const float* target, const float* obs, const float* nobs,
                               const int* act, const float* rew, const float* done, const float* tree, long long L,
                               long long filled, int B, int D, int A, int H, float gamma, int double_q, float beta,
                               uint64_t sample_key, uint64_t update, int n_step, int N, int newest, float* Xb,
-                              int* act_b, float* y, int* idx, float* w, float* wmax, int* last, int num_cu,
-                              void* stream);
+                              int* act_b, float* y, int* idx, float* w, float* wmax, int* last, int dueling,
+                              int num_cu, void* stream);
 
 // ---- per.hip
 // The priority sum tree of prioritised replay over a ring of L = C * N rows: fp32 tree[2 * P2], P2 =

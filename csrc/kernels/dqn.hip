@@ -15,6 +15,10 @@
 //     wraps: C % T == 0, slot0 % T == 0 and slot0 + T <= C, the host advances the cursor.
 //
 // One form only, the tile-stride one (4 tiles per workgroup, one per wave): see docs/KERNELS.md.
+//
+// Both kernels have a DUEL instance for the dueling Q-network (heads.h: A + 1 outputs, Q = V + adv - mean adv):
+// it stages and evaluates A + 1 outputs, acts on the argmax of the A advantages and bootstraps from the
+// dueling Q.  The DUEL = false instances are the kernels as they were.
 #include <type_traits>
 
 #include "actor_step.h"
@@ -40,14 +44,18 @@ struct DqnRolloutArgs {
   int max_steps;
 };
 
-template <class Env, int HT>
+// DUEL = true: the dueling Q-network (heads.h), Env::A + 1 outputs staged and evaluated; the greedy action
+// is the argmax of the A advantage outputs.  The draws, the ring writes and the episode slots do not change.
+template <class Env, int HT, bool DUEL = false>
 __global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(DqnRolloutArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = 1;
   constexpr int D = Env::D, A = Env::A;
+  constexpr int AO = A + (DUEL ? 1 : 0);  // outputs of the net
   static_assert(D <= 16, "device envs use one input tile");
+  static_assert(Env::A + 1 <= kMaxAct, "the dueling net has one output more than actions");
   const TileCtx c = tile_ctx(p);
-  stage_net<DT, HT>(lds, p.params, D, A, false);
+  stage_net<DT, HT>(lds, p.params, D, AO, false);
   __syncthreads();
 
   EpStats st;
@@ -62,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(DqnRolloutArgs p) {
       pack_obs<Env, DT>(e.s, c.g, x);
       if (e.valid) store_obs_row<D, DT>(p.obs + base * D, c.g, x);
       float q[kMaxAct];
-      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), A, q);
+      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), AO, q);
       const uint4 rnd = step_draw(e.envc, gstep, c.key);
       const bool explore = u01(rnd.z) < p.epsilon;
       const int a_rand = min(A - 1, (int)floorf(u01(rnd.w) * (float)A));
@@ -224,16 +232,20 @@ RRL_DEV uint32_t dqn_nstep_last(uint32_t r0, uint32_t m1, const DqnNStepArgs& p)
 // also writes the importance weight w[b] and raises *wmax to it (a maximum on the bits of non-negative
 // floats).  With double_q the online pass parks the row in idx[b], so the tree is descended once.
 // NSTEP = true: the n-step instance (above); NSTEP = false is the one-step kernel, untouched.
-template <int HT, bool PER, bool NSTEP = false>
+// DUEL = true: both nets are dueling (heads.h) with p.A + 1 outputs; a* is the argmax of the selecting
+// net's ADVANTAGES and the bootstrap is the dueling Q of the target net at a*.  What is parked between
+// the two passes does not change.
+template <int HT, bool PER, bool NSTEP = false, bool DUEL = false>
 __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(
     std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int l = lane_id();
   const int j = l & 15, g = l >> 4;
   const int wave = threadIdx.x >> 6;
+  const int AO = p.A + (DUEL ? 1 : 0);  // outputs of the nets
 
   if (p.double_q) {
-    stage_net<1, HT>(lds, p.online, p.D, p.A, false);
+    stage_net<1, HT>(lds, p.online, p.D, AO, false);
     __syncthreads();
     for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
       const int b = base + 16 * wave + j;
@@ -243,13 +255,13 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(
       if constexpr (NSTEP) {
         NStepWalk w{0u, 0.f, 0.f, 1};
         if (ok) w = dqn_nstep_walk((uint32_t)r, p);
-        dqn_q_values<HT>(lds, p.nobs, w.last, ok, p.D, p.A, q);
+        dqn_q_values<HT>(lds, p.nobs, w.last, ok, p.D, AO, q);
         if (ok && g == 0) {
           p.act_b[b] = w.m - 1;
           p.Xb[(size_t)b * p.D] = w.G;
         }
       } else {
-        dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, p.A, q);
+        dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, AO, q);
       }
       if (ok && g == 0) {
         p.y[b] = __int_as_float(argmax_first(p.A, q));
@@ -258,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(
     }
     __syncthreads();  // every wave is done with the online image
   }
-  stage_net<1, HT>(lds, p.target, p.D, p.A, false);
+  stage_net<1, HT>(lds, p.target, p.D, AO, false);
   __syncthreads();
   for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
     const int b = base + 16 * wave + j;
@@ -285,17 +297,20 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(
         }
       }
     }
-    dqn_q_values<HT>(lds, p.nobs, last, ok, p.D, p.A, q);
+    dqn_q_values<HT>(lds, p.nobs, last, ok, p.D, AO, q);
     if (ok) {
       for (int f = g; f < p.D; f += 4) p.Xb[(size_t)b * p.D + f] = p.obs[r * p.D + f];
       if (g == 0) {
         const int astar = p.double_q ? __float_as_int(p.y[b]) : argmax_first(p.A, q);
         const float boot = (p.done[last] == 1.f) ? 0.f : 1.f;
+        float qstar;
+        if constexpr (DUEL) qstar = dueling_q(p.A, q, astar);
+        else qstar = pick_logit(p.A, q, astar);
         if constexpr (NSTEP) {
-          p.y[b] = G + disc * boot * pick_logit(p.A, q, astar);
+          p.y[b] = G + disc * boot * qstar;
           if (p.last != nullptr) p.last[b] = (int)last;
         } else {
-          p.y[b] = p.rew[r] + p.gamma * boot * pick_logit(p.A, q, astar);
+          p.y[b] = p.rew[r] + p.gamma * boot * qstar;
         }
         p.act_b[b] = p.act[r];
         if (p.idx != nullptr) p.idx[b] = (int)r;
@@ -318,25 +333,25 @@ using namespace rrl;
 // 4 tiles per workgroup, one per wave; at most two workgroups per CU, beyond that the waves stride.
 extern "C" int rrl_dqn_rollout_grid(int N, int num_cu) { return tile_stride_grid(N, num_cu); }
 
-template <class Env, int HT>
+template <class Env, int HT, bool DUEL = false>
 static int launch_dqn_rollout(DqnRolloutArgs a, int slot0, int grid, hipStream_t s) {
   using L = LdsNet<1, HT>;
-  raise_lds_limit<dqn_rollout_kernel<Env, HT>>();
+  raise_lds_limit<dqn_rollout_kernel<Env, HT, DUEL>>();
   const size_t off = (size_t)slot0 * a.N;
   a.obs += off * Env::D;
   a.nobs += off * Env::D;
   a.act += off;
   a.rew += off;
   a.done += off;
-  const size_t bytes = (size_t)L::floats(Env::A) * sizeof(float);
-  hipLaunchKernelGGL((dqn_rollout_kernel<Env, HT>), dim3(grid), dim3(256), bytes, s, a);
+  const size_t bytes = (size_t)L::floats(Env::A + (DUEL ? 1 : 0)) * sizeof(float);
+  hipLaunchKernelGGL((dqn_rollout_kernel<Env, HT, DUEL>), dim3(grid), dim3(256), bytes, s, a);
   return (int)hipGetLastError();
 }
 
 extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, int slot0, float* state,
                                int* ep_len, float* ep_ret, float* obs, float* nobs, int* act, float* rew,
                                float* done, float* ep_stats, uint64_t seed, uint64_t step0, float epsilon,
-                               int reset_all, int max_steps, int num_cu, void* stream) {
+                               int reset_all, int max_steps, int dueling, int num_cu, void* stream) {
   if (!params || !state || !ep_len || !ep_ret || !obs || !nobs || !act || !rew || !done || !ep_stats) return -1;
   if (N <= 0 || T <= 0 || C <= 0 || max_steps < 1) return -2;
   if (slot0 < 0 || C % T != 0 || slot0 % T != 0 || (long long)slot0 + T > C) return -4;
@@ -346,18 +361,29 @@ extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H
   const int grid = rrl_dqn_rollout_grid(N, num_cu);
   return dispatch_env_h(env, H, [&](auto k) {
     using K = decltype(k);
+    if (dueling) return launch_dqn_rollout<typename K::Env, K::HT, true>(a, slot0, grid, (hipStream_t)stream);
     return launch_dqn_rollout<typename K::Env, K::HT>(a, slot0, grid, (hipStream_t)stream);
   });
 }
 
-template <int HT, bool PER = false, bool NSTEP = false>
+template <int HT, bool PER = false, bool NSTEP = false, bool DUEL = false>
 static int launch_dqn_targets(const std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>& a, int grid,
                               hipStream_t s) {
   using L = LdsNet<1, HT>;
-  raise_lds_limit<dqn_targets_kernel<HT, PER, NSTEP>>();
-  const size_t bytes = (size_t)L::floats(a.A) * sizeof(float);
-  hipLaunchKernelGGL((dqn_targets_kernel<HT, PER, NSTEP>), dim3(grid), dim3(256), bytes, s, a);
+  raise_lds_limit<dqn_targets_kernel<HT, PER, NSTEP, DUEL>>();
+  const size_t bytes = (size_t)L::floats(a.A + (DUEL ? 1 : 0)) * sizeof(float);
+  hipLaunchKernelGGL((dqn_targets_kernel<HT, PER, NSTEP, DUEL>), dim3(grid), dim3(256), bytes, s, a);
   return (int)hipGetLastError();
+}
+
+// The instance of (PER, NSTEP) for H in {64, 128} and a plain or a dueling pair of nets.
+template <bool PER, bool NSTEP>
+static int dispatch_dqn_targets(const std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>& a, int H, int dueling,
+                                int grid, hipStream_t s) {
+  if (dueling)
+    return H == 128 ? launch_dqn_targets<8, PER, NSTEP, true>(a, grid, s)
+                    : launch_dqn_targets<4, PER, NSTEP, true>(a, grid, s);
+  return H == 128 ? launch_dqn_targets<8, PER, NSTEP>(a, grid, s) : launch_dqn_targets<4, PER, NSTEP>(a, grid, s);
 }
 
 static int dqn_targets_grid(int B, int num_cu) {
@@ -390,31 +416,31 @@ static int dqn_one_step_last(int* last, const int* idx, int B, hipStream_t s) {
 extern "C" int rrl_dqn_targets(const float* online, const float* target, const float* obs, const float* nobs,
                                const int* act, const float* rew, const float* done, long long filled, int B, int D,
                                int A, int H, float gamma, int double_q, uint64_t sample_key, uint64_t update,
-                               float* Xb, int* act_b, float* y, int* idx, int num_cu, void* stream) {
+                               float* Xb, int* act_b, float* y, int* idx, int dueling, int num_cu, void* stream) {
   return rrl_dqn_targets_nstep(online, target, obs, nobs, act, rew, done, filled, B, D, A, H, gamma, double_q,
-                               sample_key, update, 1, 1, 0, Xb, act_b, y, idx, nullptr, num_cu, stream);
+                               sample_key, update, 1, 1, 0, Xb, act_b, y, idx, nullptr, dueling, num_cu, stream);
 }
 
 extern "C" int rrl_dqn_targets_per(const float* online, const float* target, const float* obs, const float* nobs,
                                    const int* act, const float* rew, const float* done, const float* tree,
                                    long long L, long long filled, int B, int D, int A, int H, float gamma,
                                    int double_q, float beta, uint64_t sample_key, uint64_t update, float* Xb,
-                                   int* act_b, float* y, int* idx, float* w, float* wmax, int num_cu,
+                                   int* act_b, float* y, int* idx, float* w, float* wmax, int dueling, int num_cu,
                                    void* stream) {
   return rrl_dqn_targets_per_nstep(online, target, obs, nobs, act, rew, done, tree, L, filled, B, D, A, H, gamma,
                                    double_q, beta, sample_key, update, 1, 1, 0, Xb, act_b, y, idx, w, wmax, nullptr,
-                                   num_cu, stream);
+                                   dueling, num_cu, stream);
 }
 
 extern "C" int rrl_dqn_targets_nstep(const float* online, const float* target, const float* obs, const float* nobs,
                                      const int* act, const float* rew, const float* done, long long filled, int B,
                                      int D, int A, int H, float gamma, int double_q, uint64_t sample_key,
                                      uint64_t update, int n_step, int N, int newest, float* Xb, int* act_b, float* y,
-                                     int* idx, int* last, int num_cu, void* stream) {
+                                     int* idx, int* last, int dueling, int num_cu, void* stream) {
   if (!target || (double_q && !online) || !obs || !nobs || !act || !rew || !done || !Xb || !act_b || !y) return -1;
   if (n_step == 1 && last && !idx) return -1;
   if (filled < 1 || filled > 0x7FFFFFFFll || B < 1) return -2;
-  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A > kMaxAct) return -3;
+  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A + (dueling ? 1 : 0) > kMaxAct) return -3;
   DqnTargetArgs a{online, target, obs, nobs, act, rew, done, B, D, A, (uint32_t)filled, gamma, double_q ? 1 : 0,
                   (uint32_t)sample_key, (uint32_t)(sample_key >> 32), (uint32_t)update, (uint32_t)(update >> 32),
                   Xb, act_b, y, idx};
@@ -423,10 +449,10 @@ extern "C" int rrl_dqn_targets_nstep(const float* online, const float* target, c
   const int grid = dqn_targets_grid(B, num_cu);
   hipStream_t s = (hipStream_t)stream;
   if (n_step == 1) {
-    const int rc = H == 128 ? launch_dqn_targets<8>(a, grid, s) : launch_dqn_targets<4>(a, grid, s);
+    const int rc = dispatch_dqn_targets<false, false>(a, H, dueling, grid, s);
     return rc ? rc : dqn_one_step_last(last, idx, B, s);
   }
-  return H == 128 ? launch_dqn_targets<8, false, true>(na, grid, s) : launch_dqn_targets<4, false, true>(na, grid, s);
+  return dispatch_dqn_targets<false, true>(na, H, dueling, grid, s);
 }
 
 extern "C" int rrl_dqn_targets_per_nstep(const float* online, const float* target, const float* obs,
@@ -434,12 +460,12 @@ extern "C" int rrl_dqn_targets_per_nstep(const float* online, const float* targe
                                          const float* tree, long long L, long long filled, int B, int D, int A, int H,
                                          float gamma, int double_q, float beta, uint64_t sample_key, uint64_t update,
                                          int n_step, int N, int newest, float* Xb, int* act_b, float* y, int* idx,
-                                         float* w, float* wmax, int* last, int num_cu, void* stream) {
+                                         float* w, float* wmax, int* last, int dueling, int num_cu, void* stream) {
   if (!target || (double_q && !online) || !obs || !nobs || !act || !rew || !done || !Xb || !act_b || !y) return -1;
   if (!tree || !idx || !w || !wmax) return -1;
   const long long P2 = rrl_per_tree_leaves(L);
   if (P2 < 1 || filled < 1 || filled > L || B < 1) return -2;
-  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A > kMaxAct) return -3;
+  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A + (dueling ? 1 : 0) > kMaxAct) return -3;
   DqnTargetArgs a{online, target, obs, nobs, act, rew, done, B, D, A, (uint32_t)filled, gamma, double_q ? 1 : 0,
                   (uint32_t)sample_key, (uint32_t)(sample_key >> 32), (uint32_t)update, (uint32_t)(update >> 32),
                   Xb, act_b, y, idx};
@@ -457,8 +483,8 @@ extern "C" int rrl_dqn_targets_per_nstep(const float* online, const float* targe
   if (e != hipSuccess) return (int)e;
   const int grid = dqn_targets_grid(B, num_cu);
   if (n_step == 1) {
-    const int rc = H == 128 ? launch_dqn_targets<8, true>(a, grid, s) : launch_dqn_targets<4, true>(a, grid, s);
+    const int rc = dispatch_dqn_targets<true, false>(a, H, dueling, grid, s);
     return rc ? rc : dqn_one_step_last(last, idx, B, s);
   }
-  return H == 128 ? launch_dqn_targets<8, true, true>(na, grid, s) : launch_dqn_targets<4, true, true>(na, grid, s);
+  return dispatch_dqn_targets<true, true>(na, H, dueling, grid, s);
 }

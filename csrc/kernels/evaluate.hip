@@ -47,14 +47,18 @@ RRL_DEV void store_episode(const EvalArgs& p, const EnvSlot<Env>& e, int ep, int
   p.ep_code[o] = code;
 }
 
-template <class Env, int HT>
+// DUEL = true: a dueling Q-network (heads.h) of Env::A + 1 outputs, scored greedily: the action is the
+// argmax of the A advantage outputs.  The host refuses greedy = 0 for it.
+template <class Env, int HT, bool DUEL = false>
 __global__ __launch_bounds__(256, 2) void evaluate_kernel(EvalArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = 1;
   constexpr int D = Env::D, A = Env::A;
+  constexpr int AO = A + (DUEL ? 1 : 0);  // outputs of the net
   static_assert(D <= 16, "device envs use one input tile");
+  static_assert(Env::A + 1 <= kMaxAct, "the dueling net has one output more than actions");
   const TileCtx c = tile_ctx(p);
-  stage_net<DT, HT>(lds, p.params, D, A, false);
+  stage_net<DT, HT>(lds, p.params, D, AO, false);
   __syncthreads();
 
   const int tmax = p.E * p.max_steps;  // < 2^31: checked by the host entry point
@@ -76,10 +80,10 @@ __global__ __launch_bounds__(256, 2) void evaluate_kernel(EvalArgs p) {
       pack_obs<Env, DT>(e.s, c.g, x);
       if (tr) store_obs_row<D, DT>(p.tr_obs + base * D, c.g, x);
       float logits[kMaxAct];
-      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), A, logits);
+      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), AO, logits);
       const uint4 rnd = step_draw(e.envc, gstep, c.key);
       int a;
-      if (p.greedy) {
+      if (DUEL || p.greedy) {
         a = argmax_first(A, logits);
       } else {
         const CatStats cs = cat_stats(A, logits);
@@ -199,14 +203,14 @@ int eval_args_bad(int N, int E, int Tc, int max_steps, const void* tr_obs, const
   return 0;
 }
 
-template <class Env, int HT>
+template <class Env, int HT, bool DUEL = false>
 int launch_evaluate(const EvalArgs& a, int num_cu, hipStream_t s) {
   using L = LdsNet<1, HT>;
-  raise_lds_limit<evaluate_kernel<Env, HT>>();
+  raise_lds_limit<evaluate_kernel<Env, HT, DUEL>>();
   int grid, block;
   eval_geometry(a.N, num_cu, &grid, &block);
-  const size_t bytes = (size_t)L::floats(Env::A) * sizeof(float);
-  hipLaunchKernelGGL((evaluate_kernel<Env, HT>), dim3(grid), dim3(block), bytes, s, a);
+  const size_t bytes = (size_t)L::floats(Env::A + (DUEL ? 1 : 0)) * sizeof(float);
+  hipLaunchKernelGGL((evaluate_kernel<Env, HT, DUEL>), dim3(grid), dim3(block), bytes, s, a);
   return (int)hipGetLastError();
 }
 
@@ -226,13 +230,15 @@ int launch_evaluate_cont(const EvalArgs& a, int num_cu, hipStream_t s) {
 
 extern "C" int rrl_evaluate(int env, const float* params, int N, int E, int Tc, int H, float* ep_ret, int* ep_len,
                             int* ep_code, float* tr_obs, int* tr_act, float* tr_rew, float* tr_done, uint64_t seed,
-                            uint64_t step0, int greedy, int max_steps, int num_cu, void* stream) {
+                            uint64_t step0, int greedy, int max_steps, int dueling, int num_cu, void* stream) {
   if (const int bad = eval_args_bad(N, E, Tc, max_steps, tr_obs, tr_act, tr_rew, tr_done)) return bad;
+  if (dueling && !greedy) return -3;  // softmax-of-Q is not a DQN policy
   EvalArgs a{params, nullptr, N, E, Tc, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done,
              (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step0, (uint32_t)(step0 >> 32), greedy ? 1 : 0,
              max_steps};
   return dispatch_env_h(env, H, [&](auto k) {
     using K = decltype(k);
+    if (dueling) return launch_evaluate<typename K::Env, K::HT, true>(a, num_cu, (hipStream_t)stream);
     return launch_evaluate<typename K::Env, K::HT>(a, num_cu, (hipStream_t)stream);
   });
 }

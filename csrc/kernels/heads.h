@@ -92,6 +92,23 @@ RRL_DEV float pick_logit(int A, const float (&logits)[kMaxAct], int act) {
   return v;
 }
 
+// Dueling head (Wang et al. 2016) over A + 1 outputs: out[0 .. A-1] are the advantages, out[A] the state
+// value, and Q(a) = V + adv[a] - mean adv.  dueling_base is the per-row constant V - mean: the advantages
+// are summed ascending, one add each, then one division (reference.dueling_q repeats the order).  The greedy
+// action is argmax_first over the ADVANTAGES: adding the constant in fp32 could create ties they do not have.
+RRL_DEV float dueling_base(int A, const float (&out)[kMaxAct]) {
+  float s = out[0];
+#pragma unroll
+  for (int k = 1; k < kMaxAct; ++k)
+    if (k < A) s += out[k];
+  const float m = s / (float)A;
+  return pick_logit(A + 1, out, A) - m;
+}
+// Q of action act: (V - mean) + adv[act]; the unrolled select of pick_logit keeps `out` in registers.
+RRL_DEV float dueling_q(int A, const float (&out)[kMaxAct], int act) {
+  return dueling_base(A, out) + pick_logit(A, out, act);
+}
+
 // Gaussian head: log N(x; mu, sigma) summed over dims.
 constexpr float kHalfLog2Pi = 0.91893853320467274f;
 

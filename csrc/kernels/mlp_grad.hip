@@ -101,7 +101,7 @@ RRL_DEV void stage_x_tiles(float* __restrict__ St, int wave, const floatx4 (&v)[
 // a 16-row MFMA tile that would be 1/16 (value) or 1/8 (CartPole policy) useful; this
 // also removes one staging phase and two workgroup barriers per 64-row slab.
 //
-// WEIGHTED (HEAD_Q_TD only): the prioritised-replay instance.  Row i weighs row_w[i] / *w_norm in
+// WEIGHTED (HEAD_Q_TD and HEAD_Q_DUEL only): the prioritised-replay instance.  Row i weighs row_w[i] / *w_norm in
 // the loss and in dq (row_w may be null: weight 1), and td_abs[i] (may be null) receives |diff| of
 // every valid row.  The unweighted instance reads none of the three pointers.
 template <int DT, int HT, int HEAD, int A3, int EARLY, bool WEIGHTED = false>
@@ -113,7 +113,8 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
   constexpr bool kCat = (HEAD == HEAD_PG_CAT || HEAD == HEAD_PPO_CAT);
   constexpr int TO = HT / 4;  // dW2 / dW1 output tiles per wave
   constexpr int TI3 = HT / 4; // dW3 input tiles per wave
-  const int A = (HEAD == HEAD_VALUE_MSE) ? 1 : p.A;
+  // A: the outputs of the net.  The dueling Q head has one more than actions (p.A), the state value
+  const int A = (HEAD == HEAD_VALUE_MSE) ? 1 : (HEAD == HEAD_Q_DUEL) ? p.A + 1 : p.A;
   const int net_floats = (L::floats(A) + 3) & ~3;
   float* st0 = lds + net_floats;        // [H][68]
   float* st1 = st0 + H * kStageLd;      // [H][68]
@@ -233,12 +234,15 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
         if (p.logp_old) s_kl += p.logp_old[row] - logp;
         s_cnt += 1.f;
       }
-    } else if (HEAD == HEAD_Q_TD) {
-      // Q-learning: Huber loss on Q(x)[act] - target, threshold delta = clip_eps
+    } else if (HEAD == HEAD_Q_TD || HEAD == HEAD_Q_DUEL) {
+      // Q-learning: Huber loss on Q(x)[act] - target, threshold delta = clip_eps.  HEAD_Q_DUEL: Q is the
+      // dueling combine (heads.h) of the p.A advantage outputs and the value output qs[p.A]
       float qs[kMaxAct];
       policy_logits<HT>(lds + L::W3, lds + L::B3, A, H, h2, qs);
       const int act = valid ? p.act[row] : 0;
-      const float q = pick_logit(A, qs, act);
+      float q;
+      if constexpr (HEAD == HEAD_Q_DUEL) q = dueling_q(p.A, qs, act);
+      else q = pick_logit(A, qs, act);
       const float diff = valid ? q - p.ret[row] : 0.f;
       const float delta = p.clip_eps;
       const float ad = fabsf(diff);
@@ -249,9 +253,17 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
         dq = (valid ? invB : 0.f) * wi * fminf(fmaxf(diff, -delta), delta);
         loss_i = wi * loss_i;
       }
+      if constexpr (HEAD == HEAD_Q_DUEL) {
+        // dQ/dadv[k] = [k == act] - 1/A, dQ/dV = 1
+        const float share = dq / (float)p.A;
 #pragma unroll
-      for (int a = 0; a < kMaxAct; ++a)
-        if (a < A) dout[a] = (a == act) ? dq : 0.f;
+        for (int a = 0; a < kMaxAct; ++a)
+          if (a < A) dout[a] = (a == p.A) ? dq : ((a == act) ? dq - share : -share);
+      } else {
+#pragma unroll
+        for (int a = 0; a < kMaxAct; ++a)
+          if (a < A) dout[a] = (a == act) ? dq : 0.f;
+      }
       if (count) {
         s_loss += loss_i;
         s_val += q;
@@ -473,7 +485,7 @@ using namespace rrl;
 template <int DT, int HT, int HEAD, int A3, int EARLY, bool WEIGHTED = false>
 static int launch_grad_v(const GradArgs& a, int grid, hipStream_t s) {
   using L = LdsNet<DT, HT>;
-  const int A = (HEAD == HEAD_VALUE_MSE) ? 1 : a.A;
+  const int A = (HEAD == HEAD_VALUE_MSE) ? 1 : (HEAD == HEAD_Q_DUEL) ? a.A + 1 : a.A;  // outputs, as the kernel
   const size_t floats = (size_t)((L::floats(A) + 3) & ~3) + 2 * (size_t)L::H * kStageLd;
   const size_t bytes = floats * sizeof(float);
   if (bytes > 163840) return -4;
@@ -489,17 +501,24 @@ static int launch_grad_v(const GradArgs& a, int grid, hipStream_t s) {
 
 template <int DT, int HT, int HEAD, int A3>
 static int launch_grad(const GradArgs& a, int grid, hipStream_t s) {
-  if constexpr (HEAD == HEAD_Q_TD) {  // prioritised replay: the weighted instance
+  if constexpr (HEAD == HEAD_Q_TD || HEAD == HEAD_Q_DUEL) {  // prioritised replay: the weighted instance
     if (a.row_w != nullptr || a.td_abs != nullptr) return launch_grad_v<DT, HT, HEAD, A3, 1, true>(a, grid, s);
   }
   return launch_grad_v<DT, HT, HEAD, A3, 1>(a, grid, s);
 }
 
+// Keyed on the outputs of the last layer: 1 or 2 take the VALU dW3 path, more the MFMA tile.  The
+// dueling head has a.A + 1 of them, so only a one-action net (2 outputs) takes the VALU path.
 template <int DT, int HT, int HEAD>
 static int dispatch_a3(const GradArgs& a, int grid, hipStream_t s) {
-  if (HEAD == HEAD_VALUE_MSE || a.A == 1) return launch_grad<DT, HT, HEAD, 1>(a, grid, s);
-  if (a.A == 2) return launch_grad<DT, HT, HEAD, 2>(a, grid, s);
-  return launch_grad<DT, HT, HEAD, 0>(a, grid, s);
+  if constexpr (HEAD == HEAD_Q_DUEL) {
+    if (a.A == 1) return launch_grad<DT, HT, HEAD, 2>(a, grid, s);
+    return launch_grad<DT, HT, HEAD, 0>(a, grid, s);
+  } else {
+    if (HEAD == HEAD_VALUE_MSE || a.A == 1) return launch_grad<DT, HT, HEAD, 1>(a, grid, s);
+    if (a.A == 2) return launch_grad<DT, HT, HEAD, 2>(a, grid, s);
+    return launch_grad<DT, HT, HEAD, 0>(a, grid, s);
+  }
 }
 
 template <int DT, int HT>
@@ -511,6 +530,7 @@ static int dispatch_head(int head, const GradArgs& a, int grid, hipStream_t s) {
     case HEAD_PPO_GAUSS: return dispatch_a3<DT, HT, HEAD_PPO_GAUSS>(a, grid, s);
     case HEAD_PG_GAUSS: return dispatch_a3<DT, HT, HEAD_PG_GAUSS>(a, grid, s);
     case HEAD_Q_TD: return dispatch_a3<DT, HT, HEAD_Q_TD>(a, grid, s);
+    case HEAD_Q_DUEL: return dispatch_a3<DT, HT, HEAD_Q_DUEL>(a, grid, s);
   }
   return -1;
 }
@@ -552,8 +572,9 @@ extern "C" int rrl_mlp_grad_weighted(int head, const float* params, const float*
                                      const int* nvalid, const float* inv_B_dev, const float* row_w,
                                      const float* w_norm, float* td_abs, int num_cu, void* stream) {
   if (A < 1 || A > kMaxAct || D < 1 || D > 32) return -2;
+  if (head == HEAD_Q_DUEL && A + 1 > kMaxAct) return -3;  // the net has A + 1 outputs
   if ((row_w == nullptr) != (w_norm == nullptr)) return -1;
-  if ((row_w != nullptr || td_abs != nullptr) && head != HEAD_Q_TD) return -1;
+  if ((row_w != nullptr || td_abs != nullptr) && head != HEAD_Q_TD && head != HEAD_Q_DUEL) return -1;
   GradArgs a{params, X, B, D, A, mask, act, actc, adv, ret, logp_old, adv_stats, inv_B, clip_eps,
              ent_coef, grad_slab, loss_slab, P};
   a.nvalid = nvalid;

@@ -42,17 +42,39 @@ def dqn_rollout_grid(num_envs: int) -> int:
     return int(hip().dqn_rollout_grid(int(num_envs)))
 
 
+def check_q_params(params, D: int, H: int, A: int, dueling: bool, name: str = "params"):
+    """A Q-network over ``A`` actions is ``MLPSpec(D, H, A)``, a dueling one ``MLPSpec(D, H, A + 1)`` (at most
+    16 outputs, so ``A <= 15``): ``params`` must have exactly that many floats."""
+    from .mlp import MLPSpec
+
+    if dueling and not 1 <= int(A) <= 15:
+        raise ValueError(f"a dueling net has A + 1 <= 16 outputs: A must be in [1, 15], got {A}")
+    want = MLPSpec(int(D), int(H), int(A) + (1 if dueling else 0)).P
+    if params is not None and params.numel() != want:
+        raise ValueError(f"{name} has {params.numel()} floats; a {'dueling' if dueling else 'plain'} Q-network of "
+                         f"D = {D}, H = {H}, A = {A} has {want} (dueling = {bool(dueling)})")
+
+
 def dqn_rollout(env_id: int, params: torch.Tensor, hidden: int, rollout_len: int, slot0: int, ring: ReplayRing,
                 state, ep_len, ep_ret, ep_stats, *, seed: int, step0: int, epsilon: float, reset_all: bool,
-                max_steps: int) -> int:
+                max_steps: int, dueling: bool = False) -> int:
     """T = ``rollout_len`` epsilon-greedy steps of every env into ring slots ``slot0 .. slot0 + T - 1``.
     Returns 0, or the kernel's negative code (nothing written) for a launch that would wrap: unless
-    ``C % T == 0``, ``slot0 % T == 0`` and ``slot0 + T <= C``.  Asynchronous on the current stream."""
+    ``C % T == 0``, ``slot0 % T == 0`` and ``slot0 + T <= C``.  Asynchronous on the current stream.
+
+    ``dueling``: ``params`` is a dueling net of ``A + 1`` outputs (``reference.dueling_q``); a greedy step
+    takes the lowest-index argmax of its ``A`` advantage outputs.  The draws and the ring do not change."""
     from . import hip
 
     h = hip()  # raises NativeExtensionMissing: there is no fallback
     if not params.is_cuda:
         raise ValueError("dqn_rollout runs the HIP kernel only: params must be a GPU tensor")
+    if dueling:
+        D, A, _, _ = h.env_dims(int(env_id))
+        check_q_params(params, D, hidden, A, True)
+        return int(h.dqn_rollout(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len,
+                                 ep_ret, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed),
+                                 int(step0), float(epsilon), bool(reset_all), int(max_steps), True))
     return int(h.dqn_rollout(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len, ep_ret,
                              ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed), int(step0),
                              float(epsilon), bool(reset_all), int(max_steps)))
@@ -120,7 +142,7 @@ def dqn_nstep_walk_ref(rows, ring: ReplayRing, filled: int, newest: int, n_step:
 @torch.no_grad()
 def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: int, gamma: float, double_q: bool,
                     seed: int, update: int, B: int, dtype=torch.float32, tree=None, beta: Optional[float] = None,
-                    n_step: int = 1, newest: Optional[int] = None):
+                    n_step: int = 1, newest: Optional[int] = None, dueling: bool = False):
     """-> ``(Xb [B, D], act_b [B] int32, y [B], idx [B] int64)`` in ``dtype``;
     ``y = rew + gamma * (done == 1 ? 0 : 1) * Q_target(nobs, a*)`` with ``a*`` the lowest-index argmax of the
     target (``double_q`` false) or online net.  With ``tree`` (the priority sum tree of ops/per.py) the rows
@@ -130,11 +152,15 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
     ``n_step > 1`` (with ``newest``, the ring slot written last) walks every sampled row forward
     (``dqn_nstep_walk_ref``) and ``y = G + disc * (done[last] == 1 ? 0 : 1) * Q_target(nobs[last], a*)``, ``a*``
     chosen at ``nobs[last]``; everything else still refers to the sampled row, and one more result follows at
-    the end: ``last [B]`` int64, the row the target bootstrapped from."""
+    the end: ``last [B]`` int64, the row the target bootstrapped from.
+
+    ``dueling``: both nets are dueling nets of ``A + 1`` outputs; ``a*`` is the lowest-index argmax of the
+    selecting net's advantages and ``Q_target`` is ``reference.dueling_q`` of the target net."""
+    D = ring.obs.shape[-1]
+    _check_q_nets(online if double_q else None, target, D, H, A, dueling)
     if int(n_step) != 1:
         return _dqn_targets_nstep_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree,
-                                      beta, n_step, newest)
-    D = ring.obs.shape[-1]
+                                      beta, n_step, newest, dueling)
     if tree is None:
         rows = dqn_sample_rows_ref(seed, update, B, filled)
     else:
@@ -145,17 +171,34 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
     idx = torch.from_numpy(rows).to(ring.obs.device)
     obs = ring.obs.reshape(-1, D)[idx]
     nobs = ring.nobs.reshape(-1, D)[idx].to(dtype)
-    q_t, _ = ref.trunk(target.to(dtype), nobs, D, H, A)
-    sel = ref.trunk(online.to(dtype), nobs, D, H, A)[0] if double_q else q_t
-    astar, _ = ref.greedy_from_logits(sel)
+    q_t, astar = _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype)
     boot = (ring.done.reshape(-1)[idx] != 1).to(dtype)
     y = ring.rew.reshape(-1)[idx].to(dtype) + gamma * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
     res = (obs, ring.act.reshape(-1)[idx].to(torch.int32), y, idx)
     return res if tree is None else res + (w, w.max().reshape(1))
 
 
+def _check_q_nets(online, target, D, H, A, dueling):
+    """The sizes of the nets a targets call reads.  A hidden size the kernels do not have is the launch's to
+    refuse (a GPU call), so it is not judged here."""
+    if target.is_cuda and int(H) not in (64, 128):
+        return
+    check_q_params(target, D, H, A, dueling, "target")
+    check_q_params(online, D, H, A, dueling, "online")
+
+
+def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
+    """(Q_target [B, A], a* [B]) at ``nobs``: the selecting net is the online one with ``double_q``, else the
+    target; a dueling net selects on its advantage outputs and evaluates ``reference.dueling_q``."""
+    AO = A + 1 if dueling else A
+    out_t = ref.trunk(target.to(dtype), nobs, D, H, AO)[0]
+    sel = ref.trunk(online.to(dtype), nobs, D, H, AO)[0] if double_q else out_t
+    astar, _ = ref.greedy_from_logits(sel[..., :A])
+    return (ref.dueling_q(out_t, A) if dueling else out_t), astar
+
+
 def _dqn_targets_nstep_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
-                           n_step, newest):
+                           n_step, newest, dueling=False):
     D = ring.obs.shape[-1]
     dev = ring.obs.device
     check_nstep(n_step, newest, int(ring.act.shape[1]), int(filled))
@@ -169,9 +212,7 @@ def _dqn_targets_nstep_ref(online, target, H, A, ring, filled, gamma, double_q, 
     last_np, G, disc, _ = dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)
     idx, last = torch.from_numpy(rows).to(dev), torch.from_numpy(last_np).to(dev)
     nobs = ring.nobs.reshape(-1, D)[last].to(dtype)
-    q_t, _ = ref.trunk(target.to(dtype), nobs, D, H, A)
-    sel = ref.trunk(online.to(dtype), nobs, D, H, A)[0] if double_q else q_t
-    astar, _ = ref.greedy_from_logits(sel)
+    q_t, astar = _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype)
     boot = (ring.done.reshape(-1)[last] != 1).to(dtype)
     y = torch.from_numpy(G).to(dev) + torch.from_numpy(disc).to(dev) * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
     res = (ring.obs.reshape(-1, D)[idx], ring.act.reshape(-1)[idx].to(torch.int32), y, idx)
@@ -182,7 +223,8 @@ def _dqn_targets_nstep_ref(online, target, H, A, ring, filled, gamma, double_q, 
 
 def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
                 gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32,
-                tree=None, beta: Optional[float] = None, n_step: int = 1, newest: Optional[int] = None):
+                tree=None, beta: Optional[float] = None, n_step: int = 1, newest: Optional[int] = None,
+                dueling: bool = False):
     """Sample, gather and TD target in one launch -> ``(Xb, act_b, y, idx)``; ``out`` = the four tensors to
     write into (``idx`` int32 on the GPU, or None to skip it).  CPU tensors take the torch reference in
     ``dtype``; a GPU tensor without the extension raises.
@@ -194,17 +236,24 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
     ``n_step > 1`` selects the n-step instance of the kernel (``dqn_targets_ref`` has the semantics): it needs
     ``newest``, the ring slot written last, and takes the envs per slot from the ring.  The result then ends in
     ``last [B]`` (int32 on the GPU), the row each target bootstrapped from; an ``out`` may carry it as one more
-    trailing tensor, or leave it out (or None) to skip it.  ``n_step == 1`` is the one-step launch as it was."""
+    trailing tensor, or leave it out (or None) to skip it.  ``n_step == 1`` is the one-step launch as it was.
+
+    ``dueling`` selects the dueling instances: ``A`` stays the action count, ``online`` / ``target`` are
+    ``MLPSpec(D, H, A + 1)`` nets (``dqn_targets_ref`` has the semantics).  The sampled rows and every result
+    but ``y`` are those of the plain launch on the same ring."""
     from . import use_hip, hip
 
     per = tree is not None
+    dueling = bool(dueling)
+    duel = (True,) if dueling else ()  # a plain launch passes what it always passed
+    _check_q_nets(online if double_q else None, target, ring.obs.shape[-1], H, A, dueling)
     if per and not (beta is not None and 0.0 < beta <= 1.0):
         raise ValueError(f"the prioritised form needs beta in (0, 1], got {beta}")
     n_step = int(n_step)
     base = 6 if per else 4
     if n_step == 1 and out is not None and len(out) == base + 1:  # a one-step target bootstraps from its own row
         dqn_targets(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, tuple(out[:base]), dtype,
-                    tree, beta)
+                    tree, beta, dueling=dueling)
         if out[base] is not None:
             if out[3] is None:
                 raise ValueError("at n_step = 1 last is idx: it cannot be written without idx")
@@ -212,9 +261,10 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
         return out
     if n_step != 1:
         return _dqn_targets_nstep(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, out, dtype,
-                                  tree, beta, n_step, newest)
+                                  tree, beta, n_step, newest, dueling)
     if not use_hip(target):
-        res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta)
+        res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
+                              dueling=dueling)
         if out is not None:
             for dst, src in zip(out, res):
                 if dst is not None:
@@ -236,19 +286,21 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
             raise ValueError("the prioritised form writes idx: it cannot be skipped")
         hip().dqn_targets_per(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act,
                               ring.rew, ring.done, tree, int(filled), float(gamma), bool(double_q), float(beta),
-                              int(seed), int(update), Xb, act_b, y, idx, w, wmax)
+                              int(seed), int(update), Xb, act_b, y, idx, w, wmax, *duel)
         return out
     Xb, act_b, y, idx = out
     hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
-                      ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), Xb, act_b, y, idx)
+                      ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), Xb, act_b, y, idx,
+                      *duel)
     return out
 
 
 def _dqn_targets_nstep(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, out, dtype, tree, beta,
-                       n_step, newest):
+                       n_step, newest, dueling=False):
     from . import use_hip, hip
 
     per = tree is not None
+    duel = (True,) if dueling else ()
     base = 6 if per else 4
     N = int(ring.act.shape[1])
     n_step, newest = check_nstep(n_step, newest, N, int(filled))
@@ -256,7 +308,7 @@ def _dqn_targets_nstep(online, target, H, A, ring, filled, gamma, double_q, seed
         raise ValueError(f"out must hold {base} tensors, or {base + 1} with a trailing last; got {len(out)}")
     if not use_hip(target):
         res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
-                              n_step, newest)
+                              n_step, newest, dueling)
         if out is not None:
             for dst, src in zip(out, res):
                 if dst is not None:
@@ -281,10 +333,10 @@ def _dqn_targets_nstep(online, target, H, A, ring, filled, gamma, double_q, seed
         hip().dqn_targets_per_nstep(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs,
                                     ring.act, ring.rew, ring.done, tree, int(filled), float(gamma), bool(double_q),
                                     float(beta), int(seed), int(update), n_step, newest, Xb, act_b, y, idx, w, wmax,
-                                    last)
+                                    last, *duel)
         return out
     Xb, act_b, y, idx = out[:4]
     hip().dqn_targets_nstep(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act,
                             ring.rew, ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update),
-                            n_step, newest, Xb, act_b, y, idx, last)
+                            n_step, newest, Xb, act_b, y, idx, last, *duel)
     return out

@@ -24,12 +24,15 @@ class EvalTrace(NamedTuple):
 def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes: int, num_envs: int, *,
                        greedy: bool = True, seed: int = 0, step0: int = 0, max_steps: Optional[int] = None,
                        env_consts: Optional[torch.Tensor] = None, trace_steps: int = 0, out=None,
-                       trace: Optional[EvalTrace] = None):
+                       trace: Optional[EvalTrace] = None, dueling: bool = False):
     """-> ``(ep_ret, ep_len, ep_code, trace-or-None)``: float32 / int32 / int32 ``[episodes, num_envs]``
     (code 1 terminal, 2 time limit).  ``out`` = the three tensors to write into; ``trace`` = an
     ``EvalTrace`` to write into, or ``trace_steps`` > 0 to have one allocated (zero-filled).
     ``env_consts`` is required for the continuous env (``_native.env_constants(name)``).
-    Asynchronous on the current stream, like the other ops."""
+    Asynchronous on the current stream, like the other ops.
+
+    ``dueling`` (discrete envs, ``greedy`` only): ``params`` is a dueling Q-network of ``A + 1`` outputs and
+    the action is the lowest-index argmax of its ``A`` advantage outputs."""
     from . import hip
 
     h = hip()  # raises NativeExtensionMissing: there is no fallback
@@ -39,6 +42,14 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     continuous = int(env_id) == h.ENV_IDS["ENV_HALFCHEETAH"]
     if continuous and env_consts is None:
         raise ValueError("the continuous device env needs env_consts")
+    if dueling:
+        from .dqn import check_q_params
+
+        if continuous:
+            raise ValueError("a dueling Q-network needs a discrete action space")
+        if not greedy:
+            raise ValueError("a dueling Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
+        check_q_params(params, D, hidden, A, True)
     E, N = int(episodes), int(num_envs)
     if E < 1 or N < 1:
         raise ValueError(f"episodes and num_envs must be >= 1, got {E} and {N}")
@@ -59,6 +70,8 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     args = (int(hidden), ep_ret, ep_len, ep_code, *tr, int(seed), int(step0), bool(greedy), max_steps)
     if continuous:
         h.evaluate_cont(int(env_id), params, env_consts, *args)
+    elif dueling:
+        h.evaluate(int(env_id), params, *args, True)
     else:
         h.evaluate(int(env_id), params, *args)
     return ep_ret, ep_len, ep_code, trace

@@ -32,6 +32,7 @@ class GradHead(IntEnum):
     PPO_GAUSS = 3
     PG_GAUSS = 4
     Q_TD = 5  # DQN: Huber loss on Q(x)[act] - ret; the threshold delta travels in clip_eps
+    Q_DUEL = 6  # Q_TD on a dueling net of A + 1 outputs: Q = V + adv[act] - mean(adv) (reference.dueling_q)
 
 
 from ..models.mlp_spec import MLPSpec  # noqa: E402,F401 -- torch-free (CPU agents import it)
@@ -139,17 +140,22 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
     -- rows >= nvalid are inert and inv_B_dev replaces inv_B -- so a captured graph can replay
     a batch whose valid row count changes (agent rows folded into a fixed capacity).
 
-    ``row_w`` [B] / ``w_norm`` [1] / ``td_abs`` [B] (the Q_TD head, prioritised replay): row i weighs
-    ``row_w[i] / w_norm`` in the loss and the gradient, and ``td_abs[i]`` receives ``|Q - ret|`` of every
-    valid row (rows past ``nvalid`` are left alone)."""
+    ``row_w`` [B] / ``w_norm`` [1] / ``td_abs`` [B] (the Q_TD and Q_DUEL heads, prioritised replay): row i
+    weighs ``row_w[i] / w_norm`` in the loss and the gradient, and ``td_abs[i]`` receives ``|Q - ret|`` of
+    every valid row (rows past ``nvalid`` are left alone).
+
+    ``Q_DUEL``: ``A`` stays the number of actions (at most 15); ``params`` and the gradient slab are those
+    of ``MLPSpec(D, H, A + 1)``."""
     X = X.contiguous().float()
     B = X.shape[0]
     if inv_B is None:
         inv_B = 1.0 / max(B, 1)
     if (row_w is None) != (w_norm is None):
         raise ValueError("row_w and w_norm come together")
-    if int(head) != GradHead.Q_TD and (row_w is not None or td_abs is not None):
-        raise ValueError("row_w / w_norm / td_abs apply to the Q_TD head only")
+    if int(head) not in (GradHead.Q_TD, GradHead.Q_DUEL) and (row_w is not None or td_abs is not None):
+        raise ValueError("row_w / w_norm / td_abs apply to the Q_TD and Q_DUEL heads only")
+    if int(head) == GradHead.Q_DUEL and not 1 <= int(A) <= 15:
+        raise ValueError(f"a dueling net has A + 1 <= 16 outputs: A must be in [1, 15], got {A}")
     h = _hip_for(X)
     if h is None and (nvalid is not None or inv_B_dev is not None):
         n = B if nvalid is None else int(nvalid.reshape(-1)[0])
@@ -174,7 +180,7 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
         ls[0, 5] = st.get("count", B)
         return g.view(1, -1), ls
     gaussian = int(head) in (GradHead.PPO_GAUSS, GradHead.PG_GAUSS)
-    Aeff = 1 if int(head) == GradHead.VALUE_MSE else A
+    Aeff = 1 if int(head) == GradHead.VALUE_MSE else A + 1 if int(head) == GradHead.Q_DUEL else A
     P = MLPSpec(X.shape[1], H, Aeff, gaussian).P
     ns = grad_slabs(B, X.device)
     if grad_slab is None:

@@ -14,7 +14,7 @@ import torch
 from . import philox
 
 MODE_VALUE, MODE_CAT_SAMPLE, MODE_CAT_EVAL, MODE_LOGITS, MODE_GAUSS_SAMPLE, MODE_GAUSS_EVAL = range(6)
-HEAD_PG_CAT, HEAD_VALUE_MSE, HEAD_PPO_CAT, HEAD_PPO_GAUSS, HEAD_PG_GAUSS, HEAD_Q_TD = range(6)
+HEAD_PG_CAT, HEAD_VALUE_MSE, HEAD_PPO_CAT, HEAD_PPO_GAUSS, HEAD_PG_GAUSS, HEAD_Q_TD, HEAD_Q_DUEL = range(7)
 HALF_LOG_2PI = 0.91893853320467274
 
 
@@ -126,6 +126,24 @@ def greedy_from_logits(logits: torch.Tensor):
     return act, two[..., 0] - two[..., 1]
 
 
+def dueling_q(out: torch.Tensor, A: int) -> torch.Tensor:
+    """The dueling combine of ``out`` [..., A + 1] (columns 0 .. A-1 the advantages, column A the state
+    value) -> Q [..., A], in the kernels' operation order (rrl::dueling_q), in ``out``'s dtype:
+
+        s = out[0]; s += out[k] for k = 1 .. A-1 (ascending, one add each);  m = s / A
+        Q(a) = (out[A] - m) + out[a]
+
+    The greedy action of a dueling net is the argmax of the ADVANTAGES ``out[..., :A]``, not of Q."""
+    A = int(A)
+    if out.shape[-1] != A + 1:
+        raise ValueError(f"a dueling net over {A} actions has {A + 1} outputs, got {out.shape[-1]}")
+    s = out[..., 0]
+    for k in range(1, A):
+        s = s + out[..., k]
+    m = s / torch.tensor(float(A), dtype=out.dtype, device=out.device)
+    return (out[..., A] - m).unsqueeze(-1) + out[..., :A]
+
+
 @torch.no_grad()
 def greedy_actions_ref(params, obs, A, H, dtype=torch.float64):
     """The greedy action of the categorical policy at ``obs`` [..., D] and the gap between its two
@@ -153,10 +171,11 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
     ``dtype=torch.float64`` gives the float64 oracle (tools/grad_fuzz_probe.py).
     ``HEAD_Q_TD``: loss_i = huber(Q(x_i)[act_i] - ret_i, delta) with delta = ``clip_eps``, times
     ``row_w[i] / w_norm`` where the weights of prioritised replay are given; ``stats["td_abs"]`` is
-    |Q - ret| per row."""
+    |Q - ret| per row.  ``HEAD_Q_DUEL`` is the same loss on a dueling net: ``A`` stays the number of
+    actions, ``params`` has ``A + 1`` outputs and Q is ``dueling_q`` of them."""
     B, D = X.shape
     gaussian = head in (HEAD_PPO_GAUSS, HEAD_PG_GAUSS)
-    Aeff = 1 if head == HEAD_VALUE_MSE else A
+    Aeff = 1 if head == HEAD_VALUE_MSE else A + 1 if head == HEAD_Q_DUEL else A
     if inv_B is None:
         inv_B = 1.0 / max(B, 1)
     p = params.detach().to(dtype).clone().requires_grad_(True)
@@ -167,8 +186,9 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
         li = (v - ret) ** 2
         loss = li.sum() * inv_B
         stats.update(loss=li.sum().item(), v=v.sum().item(), count=B)
-    elif head == HEAD_Q_TD:
-        q = out.gather(-1, act.long().unsqueeze(-1)).squeeze(-1)
+    elif head in (HEAD_Q_TD, HEAD_Q_DUEL):
+        qs = dueling_q(out, A) if head == HEAD_Q_DUEL else out
+        q = qs.gather(-1, act.long().unsqueeze(-1)).squeeze(-1)
         diff = q - ret.to(dtype)
         ad = diff.abs()
         li = torch.where(ad <= clip_eps, 0.5 * diff * diff, clip_eps * (ad - 0.5 * clip_eps))

@@ -30,6 +30,16 @@ drops the bootstrap, a truncation keeps it) or the newest slot, ``(cursor - 1) %
 excluded from sampling and nothing new is stored: the actor, the ring, the samplers, the tree and the
 checkpoint are those of one-step DQN, and ``n_step = 1`` runs its kernels.
 
+``dueling=True`` is the dueling network of Wang et al. 2016: Q(s, a) = V(s) + A(s, a) - mean_a' A(s, a').  The
+online and target nets are ``MLPSpec(D, H, A + 1)`` (output rows 0 .. A-1 the advantages, row A the state
+value, so A <= 15); the actor and the evaluator act on the argmax of the advantage outputs, ``dqn_targets``
+bootstraps from the dueling Q of the target net and the update is ``mlp_grad(Q_DUEL)``.  Both streams are
+LINEAR on the shared trunk h2 (no separate stream hidden layers), so such a head folds exactly into a plain
+A-output layer, ``W3'[a] = W3[a] + W3[A] - mean_k W3[k]`` (and ``b3'`` alike): the function class is that of
+the plain net and what changes is the gradient, which moves the state value of every action with each sampled
+transition.  Separate stream layers are left out.  It composes with ``double_q``, ``prioritized`` and
+``n_step``; ``dueling=False`` launches the kernels it always launched.
+
 Left for later: several ranks, hipGraph capture, serving the policy to agents (the trainer exposes no
 ``learner``, so a TrainingServer engine publishes no model).
 """
@@ -46,6 +56,19 @@ from ..ops import PriorityTree, per_insert, per_update
 from ..parallel.comm import Comm
 from .rollout_learn import episode_metrics
 from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
+
+
+def _as_bool(name: str, value) -> bool:
+    """A boolean field; hyperparameters of a TrainingServer arrive as strings ("true")."""
+    if isinstance(value, str):
+        word = value.strip().lower()
+        if word not in ("true", "false", "1", "0", "yes", "no"):
+            raise ValueError(f"{name} must be a boolean, got {value!r}")
+        return word in ("true", "1", "yes")
+    return bool(value)
+
+
+MAX_DUELING_ACTIONS = 15  # the kernels hold 16 outputs, and the dueling net has one more than actions
 
 
 @dataclass
@@ -76,8 +99,10 @@ class DQNConfig:
     per_beta_epochs: int = 500
     per_eps: float = 1e-3
     n_step: int = 1                 # n-step returns, formed from the ring at sample time (1: one-step TD)
+    dueling: bool = False           # dueling head: A + 1 outputs, Q = V + A - mean A (needs A <= 15)
 
     def __post_init__(self):
+        self.dueling = _as_bool("dueling", self.dueling)
         try:  # hyperparameters of a TrainingServer arrive as strings ("3")
             n = int(self.n_step)
         except (TypeError, ValueError):
@@ -87,13 +112,7 @@ class DQNConfig:
         self.n_step = n
         if not 1 <= self.n_step <= int(self.buffer_slots):
             raise ValueError(f"n_step must be in [1, buffer_slots = {self.buffer_slots}], got {self.n_step}")
-        # hyperparameters of a TrainingServer arrive as strings ("true")
-        if isinstance(self.prioritized, str):
-            word = self.prioritized.strip().lower()
-            if word not in ("true", "false", "1", "0", "yes", "no"):
-                raise ValueError(f"prioritized must be a boolean, got {self.prioritized!r}")
-            self.prioritized = word in ("true", "1", "yes")
-        self.prioritized = bool(self.prioritized)
+        self.prioritized = _as_bool("prioritized", self.prioritized)
         for k in ("per_alpha", "per_beta_start", "per_beta_end", "per_eps"):
             setattr(self, k, float(getattr(self, k)))
         self.per_beta_epochs = int(self.per_beta_epochs)
@@ -152,9 +171,15 @@ class DQNTrainer:
         D, A, NS, max_steps = hip().env_dims(self.env_id)
         self.D, self.A, self.NS = D, A, NS
         self.max_steps = cfg.max_episode_steps or max_steps
-        # the online net: the seeded init of PGLearner's policy, with its fused-Adam state
+        if cfg.dueling and A > MAX_DUELING_ACTIONS:
+            raise ValueError(f"dueling needs A + 1 <= 16 outputs: {cfg.env!r} has {A} actions, at most "
+                             f"{MAX_DUELING_ACTIONS} are supported")
+        # the online net: the seeded init of PGLearner's policy, with its fused-Adam state; the dueling net
+        # has one output more, the state value (row A)
         g = torch.Generator().manual_seed(int(cfg.seed))
-        self.q = FlatNet(MLPSpec(D, H, A), cfg.q_lr, dev, g)
+        self.q = FlatNet(MLPSpec(D, H, A + 1 if cfg.dueling else A), cfg.q_lr, dev, g)
+        self.head = GradHead.Q_DUEL if cfg.dueling else GradHead.Q_TD
+        self._duel = dict(dueling=True) if cfg.dueling else {}  # a plain trainer passes what it always passed
         self.target = self.q.params.clone()
         self.ring = ReplayRing.allocate(C, N, D, dev)
         self.state = torch.zeros(N, NS, device=dev)
@@ -199,7 +224,7 @@ class DQNTrainer:
         self.last_beta = beta_at(cfg, self.epoch)  # the exponent of this epoch's updates
         rc = dqn_rollout(self.env_id, self.q.params, cfg.hidden, T, self.cursor, self.ring, self.state, self.ep_len,
                          self.ep_ret, self.ep_stats, seed=self.env_seed, step0=self.epoch * T,
-                         epsilon=self.last_epsilon, reset_all=self._first, max_steps=self.max_steps)
+                         epsilon=self.last_epsilon, reset_all=self._first, max_steps=self.max_steps, **self._duel)
         if rc != 0:
             raise RuntimeError(f"dqn_rollout refused slot {self.cursor} of {cfg.buffer_slots} (code {rc})")
         if self.per is not None:  # the new transitions enter at the running maximum priority
@@ -219,15 +244,15 @@ class DQNTrainer:
         if self.per is None:
             dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None),
-                        **nstep)
-            mlp_grad(GradHead.Q_TD, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                        **nstep, **self._duel)
+            mlp_grad(self.head, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
             self.q.apply(self.slab)
         else:
             dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, tree=self.per.tree, beta=self.last_beta,
-                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep)
-            mlp_grad(GradHead.Q_TD, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep, **self._duel)
+            mlp_grad(self.head, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
                      w_norm=self.wmax, td_abs=self.td_abs)
             self.q.apply(self.slab)
@@ -259,7 +284,8 @@ class DQNTrainer:
         E, N = int(episodes), int(num_envs or self.cfg.num_envs)
         step0 = self.eval_step0
         ep_ret, ep_len, ep_code, _ = evaluate_policy_op(self.env_id, self.q.params, self.cfg.hidden, E, N, greedy=True,
-                                                        seed=self.eval_seed, step0=step0, max_steps=self.max_steps)
+                                                        seed=self.eval_seed, step0=step0, max_steps=self.max_steps,
+                                                        **self._duel)
         self.eval_step0 += E * self.max_steps
         return EvalResult(ep_ret, ep_len, ep_code, True, self.eval_seed, step0)
 
@@ -278,7 +304,7 @@ class DQNTrainer:
             if ls[5] > 0:
                 loss_q, q_vals = ls[0] / ls[5], ls[4] / ls[5]
         out.update(LossQ=loss_q, QVals=q_vals, Epsilon=self.last_epsilon, Updates=self.updates,
-                   EnvSteps=self.env_steps, WorldSize=1, NStep=self.cfg.n_step)
+                   EnvSteps=self.env_steps, WorldSize=1, NStep=self.cfg.n_step, Dueling=bool(self.cfg.dueling))
         if self.per is not None:
             out.update(Beta=self.last_beta, PriorityMax=float(self.per.pmax.item()))
         return out
@@ -324,6 +350,13 @@ class DQNTrainer:
     def load_state_dict(self, sd: dict):
         """Resume from ``state_dict()``.  The Philox keys derive from ``cfg.seed``: build the trainer with the
         checkpoint's config (the launcher does, from the preset and its overrides) for a bit-exact resume."""
+        mine = bool(self.cfg.dueling)
+        theirs = sd.get("cfg", {}).get("dueling")  # absent in a checkpoint from before the dueling head: plain
+        got = int(sd["learner"]["pi"]["params"].numel())
+        if got != self.q.P or (theirs is not None and bool(theirs) != mine):
+            raise ValueError(f"this trainer has dueling={mine} ({self.q.P} parameters); the checkpoint has "
+                             f"dueling={bool(theirs)} ({got} parameters): build the trainer with the checkpoint's "
+                             "dueling setting")
         self.q.load_state_dict(sd["learner"]["pi"])
         self.target.copy_(sd["learner"]["target"]["params"].to(self.device))
         for k, t in self.ring._asdict().items():

@@ -56,14 +56,22 @@ class EvalResult:
 
 
 def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, num_envs: int, greedy: bool = True,
-                    seed: int = 0, step0: int = 0, max_episode_steps: Optional[int] = None, device=None) -> EvalResult:
+                    seed: int = 0, step0: int = 0, max_episode_steps: Optional[int] = None, device=None,
+                    dueling: bool = False) -> EvalResult:
     """Score the flat policy weights ``params`` on the device env ``env``: ``num_envs`` envs x
     ``episodes`` complete episodes each, greedy (argmax / mean action) or sampled like training.
-    Env resets and env noise come from the Philox stream ``(seed, step0 + t)``."""
+    Env resets and env noise come from the Philox stream ``(seed, step0 + t)``.
+
+    ``dueling``: ``params`` is a dueling Q-network (``A + 1`` outputs) of a discrete env, scored greedily on
+    its advantage outputs; ``greedy=False`` raises."""
     from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
 
     if env not in DEVICE_ENVS:
         raise ValueError(f"no device implementation of env {env!r}; have {list(DEVICE_ENVS)}")
+    if dueling and env in CONTINUOUS_DEVICE_ENVS:
+        raise ValueError(f"a dueling Q-network needs a discrete action space; {env!r} is continuous")
+    if dueling and not greedy:
+        raise ValueError("a dueling Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
     if device is None:
         device = params.device if params.is_cuda else torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -75,7 +83,7 @@ def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, 
         consts = torch.tensor(_native.env_constants(env), dtype=torch.float32, device=device)
     ep_ret, ep_len, ep_code, _ = evaluate_policy_op(DEVICE_ENVS[env], p, hidden, episodes, num_envs, greedy=greedy,
                                                     seed=seed, step0=step0, max_steps=max_episode_steps,
-                                                    env_consts=consts)
+                                                    env_consts=consts, dueling=bool(dueling))
     return EvalResult(ep_ret, ep_len, ep_code, greedy, seed, step0)
 
 

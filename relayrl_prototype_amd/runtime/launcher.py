@@ -89,6 +89,15 @@ PRESETS: Dict[str, Preset] = {
                 "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
                 "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
                 "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3}),
+    "cartpole-dqn-dueling": Preset(
+        "cartpole-dqn-dueling", "cartpole-dqn-nstep with the dueling head: the Q-network has A + 1 outputs and "
+        "Q = V + A - mean A in the actor, the TD-target and the Q-head kernels (--set dueling=true on any DQN preset "
+        "is the same mechanism)",
+        "vec", {"env": "CartPole-v1", "algo": "dqn", "num_envs": 1024, "rollout_len": 4, "buffer_slots": 256,
+                "batch_size": 1024, "updates_per_epoch": 4, "gamma": 0.99, "q_lr": 5e-4, "eps_start": 1.0,
+                "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
+                "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
+                "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "dueling": True}),
 }
 
 
@@ -560,8 +569,9 @@ def evaluate_checkpoint_state(st, checkpoint: str = "<state>", episodes: int = 1
     if pixel:
         return _evaluate_pixel_checkpoint(st, tr, per_env, n, stochastic, seed, max_episode_steps)
     limit = max_episode_steps or cfg.get("max_episode_steps")
+    # a checkpoint from before the dueling head has no such key: a plain net
     res = evaluate_policy(cfg["env"], params, int(cfg["hidden"]), per_env, n, greedy=not stochastic, seed=seed,
-                          max_episode_steps=int(limit) if limit else None)
+                          max_episode_steps=int(limit) if limit else None, dueling=bool(cfg.get("dueling", False)))
     out = res.to_dict()
     out.update(env=cfg["env"], hidden=int(cfg["hidden"]), num_envs=n, episodes_per_env=per_env,
                checkpoint_epoch=int(tr.get("epoch", st.get("epoch", 0))))

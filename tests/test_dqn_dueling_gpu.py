@@ -1,0 +1,468 @@
+"""The dueling head on the GPU: the DUEL instances of the actor, the evaluator and the targets kernel
+(csrc/kernels/dqn.hip, evaluate.hip), the HEAD_Q_DUEL gradient head (mlp_grad.hip) and the dueling
+DQNTrainer, against the float64 host oracles (ops/reference.py, ops/dqn.py, tests/dqn_dueling_oracle.py).
+Every output buffer of a kernel under test is guarded."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from relayrl_prototype_amd.ops import EvalTrace, GradHead, MLPSpec, dqn_nstep_walk_ref, dqn_rollout, dqn_rollout_grid
+from relayrl_prototype_amd.ops import dqn_sample_rows_ref, dqn_targets, evaluate_policy_op, hip, mlp_grad
+from relayrl_prototype_amd.ops import per_sample_rows_ref, reduce_slabs
+from relayrl_prototype_amd.ops import reference as ref
+from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+
+import dqn_dueling_oracle as dd
+import dqn_oracle as do
+import rollout_oracle as ro
+from guarded import INT_SENTINEL, Guarded
+from test_dqn_gpu import FWD_TOL, RING_SEED, TGT_C, TGT_N, TGT_T, TRAINER, _bits, cu_limit, guarded_ring, random_ring
+from test_per_gpu import guarded_tree, random_leaves
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+
+
+def same_bits(a, b):
+    return np.array_equal(_bits(a.t.cpu().numpy()), _bits(b.t.cpu().numpy()))
+
+
+def duel_params(e, H):
+    return MLPSpec(e.D, H, e.A + 1).init(torch.Generator().manual_seed(3 + e.env_id))
+
+
+# ------------------------------------------------------------------ 6. actor
+ACT_T, ACT_STEP0 = 3, 5
+
+
+def actor_launch(e, pdev, H, N, eps):
+    g, ring = guarded_ring(ACT_T, N, e.D)
+    persist = (Guarded((N, e.NS)), Guarded((N,), torch.int32), Guarded((N,)))
+    stats = Guarded((dqn_rollout_grid(N), 8), fill=float(INT_SENTINEL))
+    rc = dqn_rollout(e.env_id, pdev, H, ACT_T, 0, ring, persist[0].t, persist[1].t, persist[2].t, stats.t,
+                     seed=RING_SEED, step0=ACT_STEP0, epsilon=eps, reset_all=True, max_steps=e.max_steps, dueling=True)
+    torch.cuda.synchronize()
+    assert rc == 0
+    bufs = dict(g, state=persist[0], ep_len=persist[1], ep_ret=persist[2], ep_stats=stats)
+    for k, b in bufs.items():
+        assert b.guards_intact(), f"{k}: the kernel wrote outside its buffer"
+    return bufs
+
+
+@pytest.mark.parametrize("name,H,N", [(name, H, N) for name in ("CartPole-v1", "LunarLanderSynth-v0")
+                                      for H in (64, 128) for N in (17, 1400)])
+def test_dueling_actor_acts_on_the_advantages(cuda, name, H, N):
+    """T = 3 steps from the Philox reset into a ring of 3 slots; N = 17 is a ragged tile, N = 1400 is 88 tiles."""
+    e = ro.env_of(name)
+    params = duel_params(e, H)
+    pdev = params.to(DEV)
+    envs = np.arange(N)
+    for eps in (0.0, 0.3, 1.0):
+        bufs = actor_launch(e, pdev, H, N, eps)
+        run = {k: bufs[k].t.cpu().numpy() for k in ("obs", "nobs", "act", "rew", "done")}
+        obs, nobs, act, rew, done = (run[k] for k in ("obs", "nobs", "act", "rew", "done"))
+        assert int(act.min()) >= 0 and int(act.max()) < e.A
+        skipped = 0
+        for t in range(ACT_T):
+            explore, a_rand, _ = do.explore_draws(RING_SEED, ACT_STEP0 + t, envs, eps, e.A)
+            assert explore.all() == (eps == 1.0) and (eps > 0.0 or not explore.any())
+            a64, gap, tol = dd.adv_gap_tolerance(params, obs[t], e.A, H)
+            np.testing.assert_array_equal(act[t][explore], a_rand[explore])
+            clear = ~explore & (gap >= tol)
+            np.testing.assert_array_equal(act[t][clear], a64[clear])
+            skipped += int((~explore & (gap < tol)).sum())
+        assert skipped <= ro.MAX_SKIP_SHARE * ACT_T * N, (skipped, ACT_T * N)
+        # the transitions do not depend on the net's shape: test_rollout_into_the_ring's checks
+        rp = ro.replay(e, run, RING_SEED, ACT_STEP0, e.max_steps)
+        ro._all(np.isin(done, (0, 1, 2)), "done codes")
+        ro._all(np.abs(obs[0] - rp["obs0"]) <= 1e-6, "obs[0] vs the Philox reset")
+        ro._all(ro.obs_close(e, nobs, rp["pred_obs"]), "nobs vs the oracle step, every row")
+        ro._all(ro.rew_close(e, rew, rp["rew"]), "reward")
+        sure = rp["margin"] > ro.EPS
+        ro._all((done == rp["code"])[sure], "done code")
+        assert int((~sure).sum()) <= ro.MAX_SKIP_SHARE * ACT_T * N
+        live = done[:-1] == 0
+        assert np.array_equal(_bits(obs[1:])[live], _bits(nobs[:-1])[live]), "obs[c+1] != nobs[c] on a running row"
+        ro._all((np.abs(obs[1:] - rp["reset_obs"][:-1]) <= 1e-6)[~live], "obs[c+1] vs the Philox reset (done rows)")
+        again = actor_launch(e, pdev, H, N, eps)
+        for k in bufs:
+            assert same_bits(bufs[k], again[k]), f"{k}: two launches differ"
+
+
+def test_dueling_actor_checks_the_parameter_count(cuda):
+    e, H, N = ro.CartPole, 64, 17
+    g, ring = guarded_ring(ACT_T, N, e.D)
+    persist = (Guarded((N, e.NS)), Guarded((N,), torch.int32), Guarded((N,)))
+    stats = Guarded((dqn_rollout_grid(N), 8), fill=float(INT_SENTINEL))
+    plain = MLPSpec(e.D, H, e.A).init(torch.Generator().manual_seed(1)).to(DEV)
+    with pytest.raises(ValueError, match=f"{plain.numel()} floats.*{MLPSpec(e.D, H, e.A + 1).P}"):
+        dqn_rollout(e.env_id, plain, H, ACT_T, 0, ring, persist[0].t, persist[1].t, persist[2].t, stats.t, seed=1,
+                    step0=0, epsilon=0.1, reset_all=True, max_steps=10, dueling=True)
+    with pytest.raises(RuntimeError):  # the binding's own check
+        hip().dqn_rollout(e.env_id, plain, H, ACT_T, 0, persist[0].t, persist[1].t, persist[2].t, ring.obs, ring.nobs,
+                          ring.act, ring.rew, ring.done, stats.t, 1, 0, 0.1, True, 10, True)
+    torch.cuda.synchronize()
+    assert all(bool(torch.isnan(b.big).all()) for b in (g["obs"], g["nobs"], g["rew"], g["done"], persist[0]))
+
+
+# ------------------------------------------------------------------ 7. evaluator
+@pytest.mark.parametrize("name,H", [(name, H) for name in ("CartPole-v1", "LunarLanderSynth-v0") for H in (64, 128)])
+def test_dueling_evaluator_acts_on_the_advantages(cuda, name, H):
+    e = ro.env_of(name)
+    N, E, Tc = 33, 1, 8
+    params = duel_params(e, H)
+    out = (Guarded((E, N)), Guarded((E, N), torch.int32), Guarded((E, N), torch.int32))
+    tr = (Guarded((Tc, N, e.D)), Guarded((Tc, N), torch.int32), Guarded((Tc, N)), Guarded((Tc, N)))
+    kw = dict(seed=RING_SEED, step0=7, out=tuple(o.t for o in out), trace=EvalTrace(*(t.t for t in tr)))
+    evaluate_policy_op(e.env_id, params.to(DEV), H, E, N, greedy=True, dueling=True, **kw)
+    torch.cuda.synchronize()
+    assert all(b.guards_intact() for b in out + tr)
+    ep_ret, ep_len, ep_code = (o.t.cpu().numpy() for o in out)
+    assert np.isin(ep_code, (1, 2)).all() and (ep_len >= 1).all() and np.isfinite(ep_ret).all()
+    tr_obs, tr_act = tr[0].t.cpu().numpy(), tr[1].t.cpu().numpy()
+    written = np.arange(Tc)[:, None] < ep_len[0][None, :]  # E = 1: an env steps until its episode ends
+    assert np.array_equal(tr_act != INT_SENTINEL, written), "tr_act rows"
+    a64, gap, tol = dd.adv_gap_tolerance(params, tr_obs[written], e.A, H)
+    clear = gap >= tol
+    assert np.array_equal(tr_act[written][clear], a64[clear]), "tr_act vs the float64 argmax of the advantages"
+    assert int((~clear).sum()) <= ro.MAX_SKIP_SHARE * Tc * N, int((~clear).sum())
+    with pytest.raises(ValueError, match="greedily"):
+        evaluate_policy_op(e.env_id, params.to(DEV), H, E, N, greedy=False, dueling=True, **kw)
+    with pytest.raises(RuntimeError):  # the binding refuses it too
+        hip().evaluate(e.env_id, params.to(DEV), H, out[0].t, out[1].t, out[2].t, *(t.t for t in tr), 1, 0, False,
+                       e.max_steps, True)
+    with pytest.raises(ValueError, match="floats"):  # a plain net is not a dueling one
+        evaluate_policy_op(e.env_id, ro.case_params(e, H, DEV), H, E, N, dueling=True)
+
+
+# ------------------------------------------------------------------ 8. targets
+SEED, GAMMA, BETA = (3 << 32) | 5, 0.97, 0.7
+TGT_CASES = [(H, A) for H in (64, 128) for A in (2, 3, 4, 15)]  # A = 15: 16 outputs, the edge of kMaxAct
+
+
+def _check_y(y, host, rows, last, G, disc, online, target, D, H, A, double_q):
+    """y against float64: any action within FWD_TOL of the selecting net's top ADVANTAGE may be a*, and y lies
+    within FWD_TOL of that candidate's value.  No row is skipped."""
+    la = torch.from_numpy(np.asarray(last))
+    nobs = host.nobs.reshape(-1, D)[la].double()
+    out_t = ref.trunk(target.double(), nobs, D, H, A + 1)[0]
+    sel = (ref.trunk(online.double(), nobs, D, H, A + 1)[0] if double_q else out_t)[:, :A]
+    top = sel.max(-1, keepdim=True).values
+    cand = sel >= top - (FWD_TOL["atol"] + FWD_TOL["rtol"] * top.abs())
+    boot = (host.done.reshape(-1)[la] != 1).double()
+    ys = G.unsqueeze(-1) + (disc * boot).unsqueeze(-1) * ref.dueling_q(out_t, A)
+    ok = ((y.double().unsqueeze(-1) - ys).abs() <= FWD_TOL["atol"] + FWD_TOL["rtol"] * ys.abs()) & cand
+    assert bool(ok.any(-1).all()), int((~ok.any(-1)).sum())
+
+
+@pytest.mark.parametrize("double_q", [False, True])
+@pytest.mark.parametrize("form", ["uniform", "prioritised", "nstep"])
+@pytest.mark.parametrize("H,A", TGT_CASES)
+def test_dueling_targets(cuda, H, A, form, double_q):
+    D = min(2 * A, 16)
+    L = TGT_C * TGT_N
+    host, g, ring = random_ring(D, A, 100 * H + A)
+    online = MLPSpec(D, H, A + 1).init(torch.Generator().manual_seed(11))
+    target = MLPSpec(D, H, A + 1).init(torch.Generator().manual_seed(12))
+    plain = tuple(MLPSpec(D, H, A).init(torch.Generator().manual_seed(s)).to(DEV) for s in (11, 12))
+    don, dtg = online.to(DEV), target.to(DEV)
+    per, nstep = form == "prioritised", form == "nstep"
+    rew, done = host.rew.reshape(-1).double(), host.done.reshape(-1)
+
+    def launch(nets, dueling, B, filled, upd, tree):
+        out = (Guarded((B, D)), Guarded((B,), torch.int32), Guarded((B,)), Guarded((B,), torch.int32))
+        kw = {}
+        if per:
+            out += (Guarded((B,)), Guarded((1,)))
+            kw = dict(tree=tree, beta=BETA)
+        if nstep:
+            out += (Guarded((B,), torch.int32),)
+            kw = dict(n_step=3, newest=filled // TGT_N - 1)
+        dqn_targets(nets[0], nets[1], H, A, ring, filled, GAMMA, double_q, SEED, upd, B, out=tuple(o.t for o in out),
+                    dueling=dueling, **kw)
+        torch.cuda.synchronize()
+        assert all(o.guards_intact() for o in out) and all(b.guards_intact() for b in g.values())
+        return out
+
+    for B in (1, 63, 65, 1000):
+        for filled in ((TGT_N * TGT_T, L) if nstep else (1, TGT_N * TGT_T, L)):  # the n-step form: whole slots
+            upd = 2 ** 32 - 1 + B  # the update counter's high word matters
+            tree = guarded_tree(random_leaves(L, filled, filled + B), 1.0)[2].tree if per else None
+            out = launch((don, dtg), True, B, filled, upd, tree)
+            base = launch(plain, False, B, filled, upd, tree)
+            for i in range(len(out)):  # sampling does not see the nets: everything but y is the plain launch's
+                if i != 2:
+                    assert same_bits(out[i], base[i]), (i, B, filled)
+            rows = per_sample_rows_ref(tree, SEED, upd, B, filled) if per else dqn_sample_rows_ref(SEED, upd, B, filled)
+            np.testing.assert_array_equal(out[3].t.cpu().numpy(), rows)
+            if nstep:
+                last, G, disc, _ = dqn_nstep_walk_ref(rows, host, filled, filled // TGT_N - 1, 3, GAMMA, torch.float64)
+                np.testing.assert_array_equal(out[-1].t.cpu().numpy(), last)
+                G, disc = torch.from_numpy(G), torch.from_numpy(disc)
+            else:
+                last, G, disc = rows, rew[torch.from_numpy(rows)], torch.full((B,), GAMMA, dtype=torch.float64)
+            _check_y(out[2].t.cpu(), host, rows, last, G, disc, online, target, D, H, A, double_q)
+            if B == 1000:  # two workgroups stride over the 16 slabs: the same bits
+                with cu_limit(2):
+                    again = launch((don, dtg), True, B, filled, upd, tree)
+                assert all(same_bits(a, b) for a, b in zip(out, again))
+    for k, b in g.items():  # the ring is an input: not one bit of it changed
+        assert np.array_equal(_bits(b.t.cpu().numpy()), _bits(getattr(host, k).numpy())), k
+
+
+def test_dueling_targets_refuse_bad_arguments(cuda):
+    """16 actions with dueling (17 outputs), a missing online net with double Q, a plain net: refused, and
+    nothing is written."""
+    D, H, B = 4, 64, 8
+    _, _, ring = random_ring(D, 2, 1)
+    L = TGT_C * TGT_N
+    h = hip()
+    big = MLPSpec(D, H, 17).init(torch.Generator().manual_seed(1)).to(DEV)
+    duel = MLPSpec(D, H, 3).init(torch.Generator().manual_seed(1)).to(DEV)
+    plain = MLPSpec(D, H, 2).init(torch.Generator().manual_seed(1)).to(DEV)
+    tree = guarded_tree(random_leaves(L, L, 1), 1.0)[2].tree
+    out = (Guarded((B, D)), Guarded((B,), torch.int32), Guarded((B,)), Guarded((B,), torch.int32), Guarded((B,), torch.int32))
+    w, wmax = Guarded((B,)), Guarded((1,))
+    o = tuple(x.t for x in out)
+    r = (ring.obs, ring.nobs, ring.act, ring.rew, ring.done)
+    for net, A, online in ((big, 16, big), (duel, 2, None), (plain, 2, plain)):
+        with pytest.raises(RuntimeError):
+            h.dqn_targets(online, net, H, A, *r, L, 0.9, True, 1, 0, *o[:4], True)
+        with pytest.raises(RuntimeError):
+            h.dqn_targets_nstep(online, net, H, A, *r, L, 0.9, True, 1, 0, 3, 2, *o, True)
+        with pytest.raises(RuntimeError):
+            h.dqn_targets_per(online, net, H, A, *r, tree, L, 0.9, True, 0.5, 1, 0, *o[:4], w.t, wmax.t, True)
+        with pytest.raises(RuntimeError):
+            h.dqn_targets_per_nstep(online, net, H, A, *r, tree, L, 0.9, True, 0.5, 1, 0, 3, 2, *o[:4], w.t, wmax.t,
+                                    o[4], True)
+    with pytest.raises(ValueError, match="15"):
+        dqn_targets(big, big, H, 16, ring, L, 0.9, True, 1, 0, B, out=o[:4], dueling=True)
+    with pytest.raises(ValueError, match="floats"):
+        dqn_targets(plain, plain, H, 2, ring, L, 0.9, True, 1, 0, B, out=o[:4], dueling=True)
+    torch.cuda.synchronize()
+    for b in out + (w, wmax):
+        whole = b.big.cpu()
+        assert bool(torch.isnan(whole).all()) if whole.dtype.is_floating_point else bool((whole == INT_SENTINEL).all())
+    dqn_targets(duel, duel, H, 2, ring, L, 0.9, True, 1, 0, B, out=o[:4], dueling=True)  # the sound call
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(out[2].t).all())
+
+
+# ------------------------------------------------------------------ 9. gradient head
+def _q_duel_case(D, H, A, B, delta, seed):
+    gen = torch.Generator().manual_seed(seed)
+    pp = MLPSpec(D, H, A + 1).init(torch.Generator().manual_seed(6))
+    X = torch.randn(B, D, generator=gen)
+    act = torch.randint(0, A, (B,), generator=gen, dtype=torch.int32)
+    q = ref.dueling_q(ref.trunk(pp, X, D, H, A + 1)[0], A).gather(-1, act.long().unsqueeze(-1)).squeeze(-1)
+    # |diff| on both sides of delta, both signs, and 0
+    y = q + torch.tensor([0.3, -0.3, 1.7, -1.7, 0.0])[torch.arange(B) % 5] * delta
+    return pp, X, act, y
+
+
+def _assert_q_duel(slab, loss, pp, X, act, y, A, H, delta, inv_B, row_w=None, w_norm=None):
+    """test_dqn_gpu._assert_q_td for HEAD_Q_DUEL, its tolerances unchanged, plus the head's two invariants:
+    the b3 gradient of the advantage rows sums to 0 and the value row's is sum(dq)."""
+    n, D = X.shape
+    g64, st = ref.mlp_grad_ref(int(GradHead.Q_DUEL), pp, X, A, H, act=act, ret=y, inv_B=inv_B, clip_eps=delta,
+                               dtype=torch.float64, row_w=row_w, w_norm=w_norm)
+    g = reduce_slabs(slab).cpu().double()
+    scale = g64.abs().max().item() + 1e-12
+    err = (g - g64).abs().max().item()
+    assert err <= 2e-4 * scale + 1e-6, (err, scale)  # test_kernels_gpu.test_grad_matches_autograd
+    ls = loss.sum(0).cpu()
+    assert abs(ls[0].item() - st["loss"]) <= 1e-3 * (abs(st["loss"]) + 1)
+    assert abs(ls[4].item() - st["v"]) <= 1e-3 * (abs(st["v"]) + 1)
+    assert int(ls[5].item()) == n and (ls[1:4] == 0).all()
+    b3 = MLPSpec(D, H, A + 1).offsets()["b3"]
+    q = ref.dueling_q(ref.trunk(pp.double(), X.double(), D, H, A + 1)[0], A).gather(-1, act.long().unsqueeze(-1)).squeeze(-1)
+    dq = (q - y.double()).clamp(-delta, delta) * inv_B
+    if row_w is not None:
+        dq = dq * row_w.double() / float(w_norm)
+    assert abs(g[b3:b3 + A].sum().item()) <= 2e-4 * scale + 1e-6
+    assert abs(g[b3 + A].item() - dq.sum().item()) <= 2e-4 * scale + 1e-6
+    return st
+
+
+@pytest.mark.parametrize("H,A", [(H, A) for H in (64, 128) for A in (1, 2, 3, 15)])
+def test_q_duel_head_matches_float64_autograd(cuda, H, A):
+    """A = 1 (2 outputs) takes the VALU dW3 path, A >= 2 the MFMA tile path, A = 15 fills its 16 rows;
+    B = 65 and 4100 end in a partial slab.  Unweighted and weighted (row_w, w_norm, td_abs)."""
+    delta = 0.75
+    for D in (2, 4, 8):
+        for B in (1, 64, 65, 4100):
+            pp, X, act, y = _q_duel_case(D, H, A, B, delta, 1000 * D + B)
+            args = (GradHead.Q_DUEL, pp.to(DEV), X.to(DEV), A, H)
+            kw = dict(act=act.to(DEV), ret=y.to(DEV), clip_eps=delta)
+            ns = int(hip().mlp_grad_slabs(B))
+            gs, gl = Guarded((ns, pp.numel())), Guarded((ns, 8), fill=float(INT_SENTINEL))
+            slab, loss = mlp_grad(*args, **kw, grad_slab=gs.t, loss_slab=gl.t)
+            torch.cuda.synchronize()
+            assert gs.guards_intact() and gl.guards_intact() and bool((gl.t[:, 6:] == INT_SENTINEL).all())
+            _assert_q_duel(slab, loss[:, :6], pp, X, act, y, A, H, delta, 1.0 / B)
+            slab2, loss2 = mlp_grad(*args, **kw)
+            assert torch.equal(slab, slab2) and torch.equal(loss[:, :6], loss2[:, :6]), "two launches differ"
+            # the weighted instance
+            w = torch.rand(B, generator=torch.Generator().manual_seed(B + D)) * 3.0 + 0.05
+            wn = w.max().reshape(1)
+            ws, wl, gtd = Guarded((ns, pp.numel())), Guarded((ns, 8), fill=float(INT_SENTINEL)), Guarded((B,))
+            wkw = dict(kw, row_w=w.to(DEV), w_norm=wn.to(DEV))
+            slab, loss = mlp_grad(*args, **wkw, grad_slab=ws.t, loss_slab=wl.t, td_abs=gtd.t)
+            torch.cuda.synchronize()
+            assert ws.guards_intact() and wl.guards_intact() and gtd.guards_intact()
+            assert bool((wl.t[:, 6:] == INT_SENTINEL).all())
+            st = _assert_q_duel(slab, loss[:, :6], pp, X, act, y, A, H, delta, 1.0 / B, w, wn)
+            torch.testing.assert_close(gtd.t.cpu().double(), st["td_abs"], **FWD_TOL)
+            td2 = torch.zeros(B, device=DEV)
+            slab2, loss2 = mlp_grad(*args, **wkw, td_abs=td2)
+            assert torch.equal(slab, slab2) and torch.equal(loss[:, :6], loss2[:, :6]) and torch.equal(td2, gtd.t)
+
+
+@pytest.mark.parametrize("H,A,D", [(128, 1, 4), (64, 3, 2), (128, 15, 8)])
+def test_q_duel_head_device_side_batch_shape_and_slab_loop(cuda, H, A, D):
+    """nvalid < B with poisoned rows past it, inv_B from device memory, and (2 CUs) workgroups that walk
+    several 64-row slabs; td_abs past nvalid is left alone."""
+    delta, B, nv = 1.0, 4100, 3001
+    pp, X, act, y = _q_duel_case(D, H, A, B, delta, 5)
+    w = torch.rand(B, generator=torch.Generator().manual_seed(2)) + 0.5
+    Xp, actp, yp, wp = X.clone(), act.clone(), y.clone(), w.clone()
+    Xp[nv:], yp[nv:], actp[nv:], wp[nv:] = float("nan"), float("nan"), 99, float("nan")
+    nvalid = torch.tensor([nv], dtype=torch.int32, device=DEV)
+    inv_dev = torch.tensor([1.0 / 777], device=DEV)
+    wn = w[:nv].max().reshape(1)
+    for cus in (0, 2):
+        with cu_limit(cus):
+            slab, loss = mlp_grad(GradHead.Q_DUEL, pp.to(DEV), Xp.to(DEV), A, H, act=actp.to(DEV), ret=yp.to(DEV),
+                                  clip_eps=delta, nvalid=nvalid, inv_B_dev=inv_dev)
+            assert slab.shape[0] == (2 if cus else min(65, hip().num_cus()))
+            assert bool(torch.isfinite(slab).all())
+            _assert_q_duel(slab, loss[:, :6], pp, X[:nv], act[:nv], y[:nv], A, H, delta, 1.0 / 777)
+            gtd = Guarded((B,))
+            slab, loss = mlp_grad(GradHead.Q_DUEL, pp.to(DEV), Xp.to(DEV), A, H, act=actp.to(DEV), ret=yp.to(DEV),
+                                  clip_eps=delta, nvalid=nvalid, inv_B_dev=inv_dev, row_w=wp.to(DEV), w_norm=wn.to(DEV),
+                                  td_abs=gtd.t)
+            torch.cuda.synchronize()
+            td = gtd.t.cpu()
+            assert gtd.guards_intact() and bool(torch.isnan(td[nv:]).all()), "a row past nvalid wrote td_abs"
+            st = _assert_q_duel(slab, loss[:, :6], pp, X[:nv], act[:nv], y[:nv], A, H, delta, 1.0 / 777, w[:nv], wn)
+            torch.testing.assert_close(td[:nv].double(), st["td_abs"], **FWD_TOL)
+
+
+def test_q_duel_head_refuses_sixteen_actions(cuda):
+    D, H, B = 4, 64, 8
+    p = MLPSpec(D, H, 17).init(torch.Generator().manual_seed(1)).to(DEV)
+    X, act, y = torch.zeros(B, D, device=DEV), torch.zeros(B, dtype=torch.int32, device=DEV), torch.zeros(B, device=DEV)
+    gs, gl = Guarded((1, p.numel())), Guarded((1, 8))
+    with pytest.raises(RuntimeError):
+        hip().mlp_grad(int(GradHead.Q_DUEL), p, X, 16, H, None, act, None, None, y, None, None, 1.0 / B, 1.0, 0.0, gs.t,
+                       gl.t, None, None, None, None, None)
+    with pytest.raises(ValueError, match="15"):
+        mlp_grad(GradHead.Q_DUEL, p, X, 16, H, act=act, ret=y, grad_slab=gs.t, loss_slab=gl.t)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(gs.big).all()) and bool(torch.isnan(gl.big).all())
+
+
+# ------------------------------------------------------------------ 10. trainer
+NAMES = ["online", "m", "v", "step", "target", "obs", "nobs", "act", "rew", "done", "state", "ep_len", "ep_ret", "tree",
+         "pmax"]
+
+
+def _state(tr):
+    return [t.clone() for t in tr.snapshot_tensors()], dict(tr.counters())
+
+
+@pytest.mark.parametrize("extra", [{}, dict(prioritized=True, n_step=3, per_beta_epochs=4)], ids=["uniform", "per-nstep"])
+def test_dueling_trainer_resume_is_bitwise_and_evaluate_touches_nothing(cuda, extra):
+    kw = dict(TRAINER, dueling=True, **extra)
+    a = DQNTrainer(DQNConfig(**kw), device=cuda)
+    assert a.q.P == MLPSpec(a.D, kw["hidden"], a.A + 1).P and a.target.numel() == a.q.P and a.slab.shape[1] == a.q.P
+    for _ in range(6):
+        a.train_epoch()
+    b = DQNTrainer(DQNConfig(**kw), device=cuda)
+    for _ in range(3):
+        b.train_epoch()
+    before, counters = _state(b)
+    res = b.evaluate(episodes=2, num_envs=33)
+    assert res.stats()["episodes"] == 66
+    after, counters2 = _state(b)
+    assert counters == counters2 and all(torch.equal(x, y) for x, y in zip(before, after)), "evaluate() changed state"
+    with pytest.raises(ValueError):
+        b.evaluate(greedy=False)
+    sd = b.state_dict()
+    assert sd["cfg"]["dueling"] is True and DQNConfig(**sd["cfg"]).dueling is True
+    c = DQNTrainer(DQNConfig(**kw), device=cuda)
+    c.q.params.add_(1.0)  # other weights until the load
+    c.target.zero_()
+    c.load_state_dict(sd)
+    for _ in range(3):
+        c.train_epoch()
+    torch.cuda.synchronize()
+    assert a.counters() == c.counters() and a.updates == 12 and a.cursor == 0 and a.slots_written == 24
+    for n, x, y in zip(NAMES, a.snapshot_tensors(), c.snapshot_tensors()):
+        assert torch.equal(x, y), f"{n} differs after the resume"
+    assert int(a.q.step.item()) == 12 and not torch.equal(a.q.params, b.q.params)
+    m = a.metrics()
+    assert m["Dueling"] is True and m["Updates"] == 12 and np.isfinite(m["LossQ"]) and np.isfinite(m["QVals"])
+    # a dueling checkpoint and a plain trainer refuse each other by name
+    plain = DQNTrainer(DQNConfig(**dict(TRAINER, **extra)), device=cuda)
+    assert plain.metrics()["Dueling"] is False and plain.state_dict()["cfg"]["dueling"] is False
+    with pytest.raises(ValueError, match="dueling"):
+        plain.load_state_dict(sd)
+    with pytest.raises(ValueError, match="dueling"):
+        c.load_state_dict(plain.state_dict())
+
+
+def test_dueling_trainer_target_network_follows_its_schedule(cuda):
+    tr = DQNTrainer(DQNConfig(**TRAINER, dueling=True), device=cuda)
+    tr.rollout()
+    init = tr.target.clone()
+    assert torch.equal(init, tr.q.params)
+    prev = init
+    for u in range(1, 8):
+        tr.update()
+        if u % 3 == 0:
+            assert torch.equal(tr.target, tr.q.params) and not torch.equal(tr.target, prev)
+            prev = tr.target.clone()
+        else:
+            assert torch.equal(tr.target, prev) and not torch.equal(tr.target, tr.q.params)
+
+
+# ------------------------------------------------------------------ 11. CLI
+def test_dueling_preset_trains_evaluates_and_checkpoints(cuda, tmp_path):
+    from relayrl_prototype_amd.runtime.launcher import EVAL_COLUMNS, ckpt_dir, run_evaluate, run_preset
+
+    small = {k: v for k, v in TRAINER.items() if k != "max_episode_steps"}
+    rows = []
+    last = run_preset("cartpole-dqn-dueling", 4, str(tmp_path), overrides=small, eval_every=2, checkpoint_every=4,
+                      eval_episodes=1, eval_envs=32, on_metrics=rows.append)
+    assert len(rows) == 4 and last["Epoch"] == 4 and last["Updates"] == 8
+    assert last["Dueling"] is True and last["NStep"] == 3 and 0.4 <= last["Beta"] <= 1.0
+    for k in EVAL_COLUMNS:
+        assert np.isfinite(rows[1][k]) and np.isfinite(last[k]), k
+    ck = ckpt_dir(str(tmp_path), "cartpole-dqn-dueling", 0)
+    assert os.path.exists(os.path.join(ck, "state.json"))
+    out = run_evaluate(ck, episodes=64, num_envs=32)
+    assert out["env"] == "CartPole-v1" and out["hidden"] == 64 and out["episodes"] == 64 and out["greedy"]
+    assert out["checkpoint_epoch"] == 4 and 8.0 <= out["mean_return"] <= 500.0
+    with pytest.raises(ValueError):
+        run_evaluate(ck, episodes=4, num_envs=4, stochastic=True)
+
+
+# ------------------------------------------------------------------ 12. learning
+def test_dueling_trainer_learns_cartpole_like_the_cpu_oracle(cuda):
+    """The CPU oracle loop with the dueling net (tests/dqn_dueling_oracle.py: the same algorithm and Philox
+    draws, float64 networks) at the small shape.  At 600 epochs its five seeds score 167.91, 160.96, 240.57,
+    500.00 and 9.26, and 80 % of the lowest is below twice a random policy's 22, so both sides run 1,200 epochs
+    = 2394 updates, where the oracle scores 151.12, 134.50, 253.68, 472.31 and 495.76.  The GPU trainer after
+    the same number of updates must reach 80 % of the lowest."""
+    tr = DQNTrainer(DQNConfig(**do.SMALL, seed=1, dueling=True), device=cuda)
+    for _ in range(dd.DUEL_EPOCHS):
+        tr.train_epoch()
+    assert tr.updates == dd.DUEL_UPDATES == 2394
+    got = tr.evaluate(episodes=1, num_envs=do.EVAL_EPISODES).stats()["mean_return"]
+    floor = 0.8 * min(dd.ORACLE_RETURNS_DUEL.values())
+    print(f"GPU greedy mean return {got:.2f}, floor {floor:.2f}, oracle {dd.ORACLE_RETURNS_DUEL}")
+    assert floor >= 44.0 and got >= floor, (got, floor)
