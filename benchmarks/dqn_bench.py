@@ -32,6 +32,13 @@ prioritised (``targets_per_n<K>_us``), and the epoch of both DQN presets at ``n_
 ``cartpole-dqn-dueling`` preset): ``epoch_<shape>_<plain|dueling>_us`` and the microseconds per launch of
 ``dqn_rollout``, ``dqn_targets`` and ``mlp_grad`` (``<kernel>_<shape>_<plain|dueling>_us``).  The line goes to
 ``profiles/dqn_dueling_bench.jsonl`` unless ``--out`` names another file.
+
+``--noisy`` adds, from the same process, NoisyNet exploration: the microseconds per launch of ``noisy_compose``
+with one job (the actor's, per rollout) and with three (per update) and of ``noisy_grad``, at the net of the
+``cartpole-dqn-noisy`` preset, and the epoch of that preset against ``cartpole-dqn-dueling``
+(``epoch_noisy_us`` / ``epoch_dueling_us``).  The line goes to ``profiles/dqn_noisy_bench.jsonl`` unless ``--out``
+names another file.  ``--noisy-learning EPOCHS`` instead records, for seeds 1..3 of both presets, the greedy mean
+return over 256 episodes every 100 epochs: one line per run in ``profiles/dqn_noisy_learning.jsonl``.
 """
 import argparse
 import json
@@ -204,6 +211,76 @@ def dueling_records(a, dev, event_us):
     return rec
 
 
+def noisy_records(a, dev, event_us):
+    """NoisyNet exploration in one process: the two new launches at the preset's net, and the epoch of
+    ``cartpole-dqn-noisy`` against ``cartpole-dqn-dueling``."""
+    from relayrl_prototype_amd.ops import noisy_compose, noisy_grad
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    assert PRESETS["cartpole-dqn-noisy"].overrides == dict(PRESETS["cartpole-dqn-dueling"].overrides, noisy=True,
+                                                           eps_start=0.0, eps_end=0.0)
+    rec = {}
+    for preset, tag in (("cartpole-dqn-dueling", "dueling"), ("cartpole-dqn-noisy", "noisy")):
+        cfg = DQNConfig(**PRESETS[preset].overrides)
+        tr = DQNTrainer(cfg, device=dev)
+        for _ in range(a.warmup):
+            tr.train_epoch()
+        assert tr.updates > 0, "the warm-up must reach learning_starts"
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.epochs):
+            tr.train_epoch()
+        torch.cuda.synchronize()
+        rec[f"epoch_{tag}_us"] = round(1e6 * (time.perf_counter() - t0) / a.epochs, 2)
+    spec, key = tr.q.spec, tr.noise_seed  # the noisy trainer's
+    rec.update(noisy_params=spec.P, noisy_slabs=int(tr.slab.shape[0]), noisy_sigma_mean_abs=tr.metrics()["SigmaMeanAbs"])
+
+    def compose1():  # the same draw every time: timing only
+        noisy_compose(tr.theta, (0,), (7,), spec, key, out=tr.actor_w)
+
+    def compose3():
+        noisy_compose((tr.theta, tr.target, tr.theta), (1, 2, 3), (7, 7, 7), spec, key, out=tr.update_w)
+
+    def grad():
+        noisy_grad(tr.slab, 1, 7, spec, key, out=tr.theta_grad)
+
+    for name, fn in (("noisy_compose_1job", compose1), ("noisy_compose_3jobs", compose3), ("noisy_grad", grad)):
+        fn()
+        torch.cuda.synchronize()
+        med, lo, hi = event_us(fn, a.iters, a.reps)
+        rec[name + "_us"] = med
+        rec[name + "_us_range"] = [lo, hi]
+    return rec
+
+
+def noisy_learning(a, dev):
+    """Greedy mean return over 256 episodes every 100 epochs, seeds 1..3, ``cartpole-dqn-dueling`` and
+    ``cartpole-dqn-noisy``: one JSON line per run."""
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    lines = []
+    for preset in ("cartpole-dqn-dueling", "cartpole-dqn-noisy"):
+        for seed in (1, 2, 3):
+            cfg = DQNConfig(**dict(PRESETS[preset].overrides, seed=seed))
+            tr = DQNTrainer(cfg, device=dev)
+            curve = []
+            for epoch in range(1, a.noisy_learning + 1):
+                tr.train_epoch()
+                if epoch % 100 == 0:
+                    curve.append(round(tr.evaluate(episodes=1, num_envs=256).stats()["mean_return"], 1))
+            rec = dict(preset=preset, noisy=bool(cfg.noisy), dueling=bool(cfg.dueling), n_step=cfg.n_step, seed=seed,
+                       eval_every=100, env_steps_per_epoch=cfg.num_envs * cfg.rollout_len, greedy_mean_return_256=curve)
+            if cfg.noisy:
+                rec["sigma_mean_abs"] = round(tr.metrics()["SigmaMeanAbs"], 5)
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2000)
@@ -216,11 +293,16 @@ def main():
     ap.add_argument("--n-step", type=int, nargs="+", default=[], metavar="K",
                     help="also measure n-step returns at every K against one-step")
     ap.add_argument("--dueling", action="store_true", help="also measure the dueling head against the plain one")
+    ap.add_argument("--noisy", action="store_true", help="also measure NoisyNet exploration against cartpole-dqn-dueling")
+    ap.add_argument("--noisy-learning", type=int, default=0, metavar="EPOCHS",
+                    help="record greedy-return curves of cartpole-dqn-noisy and cartpole-dqn-dueling instead")
     a = ap.parse_args()
     if any(k < 1 for k in a.n_step):
         raise SystemExit("--n-step takes values >= 1")
-    if (a.prioritized or a.n_step or a.dueling) and not a.out:
+    if (a.prioritized or a.n_step or a.dueling or a.noisy or a.noisy_learning) and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "dqn_noisy_learning.jsonl" if a.noisy_learning else
+                             "dqn_noisy_bench.jsonl" if a.noisy else
                              "dqn_dueling_bench.jsonl" if a.dueling else
                              "dqn_nstep_bench.jsonl" if a.n_step else "dqn_per_bench.jsonl")
     if not torch.cuda.is_available():
@@ -231,6 +313,8 @@ def main():
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if a.noisy_learning:
+        return noisy_learning(a, dev)
     cfg = DQNConfig(**PRESETS["cartpole-dqn"].overrides)
     tr = DQNTrainer(cfg, device=dev)
     for _ in range(a.warmup):
@@ -285,6 +369,8 @@ def main():
         rec.update(nstep_records(a, dev, event_us))
     if a.dueling:
         rec.update(dueling_records(a, dev, event_us))
+    if a.noisy:
+        rec.update(noisy_records(a, dev, event_us))
     rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
     line = json.dumps(rec)
     print(line, flush=True)

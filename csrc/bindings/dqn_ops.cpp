@@ -1,8 +1,11 @@
 // Bindings of the DQN kernels (csrc/kernels/dqn.hip): the epsilon-greedy actor that fills the replay
-// ring and the sample + gather + TD-target kernel, uniform and prioritised, and of the priority sum
-// tree (csrc/kernels/per.hip).  Every tensor is validated before a launch.
+// ring and the sample + gather + TD-target kernel, uniform and prioritised, of the priority sum
+// tree (csrc/kernels/per.hip) and of the noisy layers (csrc/kernels/noisy.hip).  Every tensor is
+// validated before a launch.
+#include <algorithm>
 #include <cstdlib>
 #include <tuple>
+#include <vector>
 
 #include "api.h"
 #include "check.h"
@@ -217,10 +220,72 @@ void dqn_targets_per(const OptT& online, const Tensor& target, int64_t H, int64_
            "dqn_targets_per");
 }
 
+// ------------------------------------------------------------------ noisy layers (noisy.hip)
+// A shape the entry points refuse is theirs to refuse (the code comes back, nothing is launched); for a shape
+// they take, every tensor is sized here first.  Returns 0 or the negative code; a HIP error raises.
+bool noisy_shape_ok(int64_t D, int64_t H, int64_t A_out) {
+  return D >= 1 && D <= 16 && A_out >= 1 && A_out <= 16 && (H == 64 || H == 128);
+}
+
+int narrow(int64_t v) { return v < -1 || v > (int64_t)INT32_MAX ? -1 : (int)v; }
+
+int64_t noisy_compose(const std::vector<OptT>& thetas, const std::vector<int64_t>& roles,
+                      const std::vector<int64_t>& draws, int64_t D, int64_t H, int64_t A_out, int64_t key,
+                      const OptT& out, const OptT& units_out) {
+  const int64_t njobs = (int64_t)roles.size();
+  TORCH_CHECK((int64_t)thetas.size() == njobs && (int64_t)draws.size() == njobs,
+              "noisy_compose takes one theta, role and draw per job");
+  const bool ok = noisy_shape_ok(D, H, A_out) && njobs >= 1 && njobs <= 3;
+  const int64_t P = H * D + H + H * H + H + A_out * H + A_out, U = D + 4 * H + A_out;
+  std::vector<const float*> tp;
+  std::vector<int> rl;
+  std::vector<uint64_t> dr;
+  for (int64_t k = 0; k < njobs; ++k) {
+    tp.push_back(ok ? opt_ptr<const float>(thetas[k], "theta", at::kFloat, 2 * P) : nullptr);
+    rl.push_back(narrow(roles[k]));
+    dr.push_back((uint64_t)draws[k]);
+  }
+  float* o = ok ? opt_ptr<float>(out, "out", at::kFloat, njobs * P) : nullptr;
+  float* uo = ok ? opt_ptr<float>(units_out, "units_out", at::kFloat, njobs * U) : nullptr;
+  static const float dummy = 0.f;  // a refused shape never dereferences its pointers: they only must not be null
+  if (!ok) {
+    tp.assign((size_t)std::max<int64_t>(njobs, 1), &dummy);
+    o = const_cast<float*>(&dummy);
+    if (njobs == 0) {
+      rl.push_back(0);
+      dr.push_back(0);
+    }
+  }
+  const int rc = rrl_noisy_compose(tp.data(), narrow(njobs), rl.data(), dr.data(), narrow(D),
+                                   narrow(H), narrow(A_out), (uint64_t)key, o, uo, grid_cus(), cur_stream());
+  if (rc < 0) return rc;
+  check_rc(rc, "noisy_compose");
+  return 0;
+}
+
+int64_t noisy_grad(const OptT& slab, int64_t role, int64_t draw, int64_t D, int64_t H, int64_t A_out, int64_t key,
+                   const OptT& grad_out, int64_t nslab) {
+  const bool ok = noisy_shape_ok(D, H, A_out) && nslab >= 1;
+  const int64_t P = H * D + H + H * H + H + A_out * H + A_out;
+  TORCH_CHECK(nslab < (int64_t)INT32_MAX / std::max<int64_t>(P, 1), "too many slabs");
+  static const float dummy = 0.f;
+  const float* s = ok ? opt_ptr<const float>(slab, "slab", at::kFloat, nslab * P) : &dummy;
+  float* g = ok ? opt_ptr<float>(grad_out, "grad_out", at::kFloat, 2 * P) : const_cast<float*>(&dummy);
+  const int rc = rrl_noisy_grad(s, narrow(nslab), narrow(P), narrow(role), (uint64_t)draw, narrow(D), narrow(H),
+                                narrow(A_out), (uint64_t)key, g, grid_cus(), cur_stream());
+  if (rc < 0) return rc;
+  check_rc(rc, "noisy_grad");
+  return 0;
+}
+
 }  // namespace
 
 void register_dqn_ops(pybind11::module_& m) {
   namespace py = pybind11;
+  m.def("noisy_compose", &noisy_compose, py::arg("thetas"), py::arg("roles"), py::arg("draws"), py::arg("D"),
+        py::arg("H"), py::arg("A_out"), py::arg("key"), py::arg("out"), py::arg("units_out"));
+  m.def("noisy_grad", &noisy_grad, py::arg("slab"), py::arg("role"), py::arg("draw"), py::arg("D"), py::arg("H"),
+        py::arg("A_out"), py::arg("key"), py::arg("grad_out"), py::arg("nslab"));
   m.def("per_tree_leaves", &per_tree_leaves);
   m.def("per_insert", &per_insert, py::arg("tree"), py::arg("pmax"), py::arg("C"), py::arg("N"), py::arg("T"),
         py::arg("slot0"));

@@ -214,6 +214,28 @@ int rrl_per_insert(float* tree, const float* pmax, int C, int N, int T, int slot
 int rrl_per_update(float* tree, float* pmax, const int* idx, const float* td_abs, int B, long long L, float alpha,
                    float prio_eps, void* stream);
 
+// ---- noisy.hip
+// NoisyNet layers (factorised Gaussian noise) for a Q-network MLPSpec(D, H, A_out) of P parameters.  Unit i
+// of (role r in [0, 3], layer l = 1..3, side s = 0 in / 1 out) at the 64-bit draw d:
+//   w = philox((i, lo32(d), hi32(d), 16 + 8 r + 2 (l - 1) + s), key)
+//   n = sqrtf(-2 logf(1 - u01(w.x))) * cosf(6.283185307179586f * u01(w.y));  f = copysignf(sqrtf(fabsf(n)), n)
+// (the precise functions), eps_W[j][i] = f_out[j] * f_in[i], eps_b[j] = f_out[j], every product and sum one
+// rounded fp32 operation, never an fma.  The U = D + 4 H + A_out unit factors of one (role, draw) are laid out
+// [in1 (D), out1 (H), in2 (H), out2 (H), in3 (H), out3 (A_out)].
+//
+// Job k < njobs (theta / roles / draws: HOST arrays of njobs entries) reads theta[k] = [mu (P); sigma (P)] and
+// writes out[k][p] = mu[p] + sigma[p] * eps(roles[k], draws[k])[p]; all jobs are one launch.  units_out (may be
+// null) [njobs][U] receives the unit factors f.  Both entry points, nothing written on a refusal: -1 a null
+// pointer; -2 D or A_out outside [1, 16], njobs outside [1, 3], nslab < 1, a role outside [0, 3] or P not the
+// net's; -3 H not 64 / 128.  No output depends on the grid
+int rrl_noisy_compose(const float* const* theta, int njobs, const int* roles, const uint64_t* draws, int D, int H,
+                      int A_out, uint64_t key, float* out, float* units_out, int num_cu, void* stream);
+// slab [nslab][P]: g = slab[0][p], then g = g + slab[s][p] for s = 1 .. nslab - 1 in this order;
+// grad_out[p] = g, grad_out[P + p] = g * eps(role, draw)[p]: the gradient of [mu; sigma] from the gradient
+// slabs of the effective parameters
+int rrl_noisy_grad(const float* slab, int nslab, int P, int role, uint64_t draw, int D, int H, int A_out,
+                   uint64_t key, float* grad_out, int num_cu, void* stream);
+
 // ---- cnn.hip (bf16 tensors as uint16_t)
 int rrl_conv_fwd(const void* x, int x_u8, const uint16_t* w, const float* b, uint16_t* y, int N, int H, int W,
                  int C, int KH, int KW, int S, int Cout, int relu, float* work, long long work_elems, void* stream);

@@ -80,8 +80,26 @@ from .per import (  # noqa: E402
     per_update,
     per_weights_ref,
 )
+from .noisy import (  # noqa: E402
+    noisy_compose,
+    noisy_compose_ref,
+    noisy_eps_ref,
+    noisy_grad,
+    noisy_grad_ref,
+    noisy_num_units,
+    noisy_sigma_init,
+    noisy_units_ref,
+)
 
 __all__ = [
+    "noisy_compose",
+    "noisy_compose_ref",
+    "noisy_eps_ref",
+    "noisy_grad",
+    "noisy_grad_ref",
+    "noisy_num_units",
+    "noisy_sigma_init",
+    "noisy_units_ref",
     "PriorityTree",
     "per_insert",
     "per_sample_rows_ref",

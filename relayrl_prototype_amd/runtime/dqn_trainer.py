@@ -40,7 +40,18 @@ the plain net and what changes is the gradient, which moves the state value of e
 transition.  Separate stream layers are left out.  It composes with ``double_q``, ``prioritized`` and
 ``n_step``; ``dueling=False`` launches the kernels it always launched.
 
-Left for later: several ranks, hipGraph capture, serving the policy to agents (the trainer exposes no
+``noisy=True`` is NoisyNet exploration (Fortunato et al. 2018, factorised Gaussian noise; ops/noisy.py has the
+contract): all three layers are ``W = mu + sigma * eps``, ``theta = [mu; sigma]`` (2P, with Adam state of 2P) is what
+is trained and ``target`` is a 2P copy.  The big kernels do not change: ``rollout()`` composes the role-0 sample
+of draw = epoch (one for all envs and all T steps) into a buffer and hands that to ``dqn_rollout``; ``update()``
+composes roles 1, 2 and 3 (the loss, the target net, the selecting net of double Q) at draw = updates in one
+launch, and after ``dqn_targets`` and ``mlp_grad`` on those buffers ``noisy_grad`` turns the slabs into the
+gradient of ``theta`` for Adam's ``grad=`` path.  ``epsilon`` still applies (the ``cartpole-dqn-noisy`` preset sets
+it to 0), ``evaluate()`` scores ``mu``, and a checkpoint keeps ``mu`` where the plain parameters were
+(``learner/pi``, ``learner/target``) and sigma with its Adam moments under ``noisy``.  ``noisy=False`` calls none of
+this and launches the kernels it always launched.
+
+Left for later: per-env noise, several ranks, hipGraph capture, serving the policy to agents (the trainer exposes no
 ``learner``, so a TrainingServer engine publishes no model).
 """
 from __future__ import annotations
@@ -53,6 +64,7 @@ import torch
 from ..algorithms.core import FlatNet
 from ..ops import GradHead, MLPSpec, ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_targets, grad_slabs, hip, mlp_grad
 from ..ops import PriorityTree, per_insert, per_update
+from ..ops import adam_step, noisy_compose, noisy_grad, noisy_sigma_init
 from ..parallel.comm import Comm
 from .rollout_learn import episode_metrics
 from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
@@ -100,9 +112,18 @@ class DQNConfig:
     per_eps: float = 1e-3
     n_step: int = 1                 # n-step returns, formed from the ring at sample time (1: one-step TD)
     dueling: bool = False           # dueling head: A + 1 outputs, Q = V + A - mean A (needs A <= 15)
+    noisy: bool = False             # NoisyNet exploration: W = mu + sigma * eps in all three layers
+    noisy_sigma0: float = 0.5       # sigma starts at noisy_sigma0 / sqrt(fan_in)
 
     def __post_init__(self):
         self.dueling = _as_bool("dueling", self.dueling)
+        self.noisy = _as_bool("noisy", self.noisy)
+        try:
+            self.noisy_sigma0 = float(self.noisy_sigma0)
+        except (TypeError, ValueError):
+            raise ValueError(f"noisy_sigma0 must be a number, got {self.noisy_sigma0!r}") from None
+        if not self.noisy_sigma0 >= 0.0:
+            raise ValueError(f"noisy_sigma0 must be >= 0, got {self.noisy_sigma0}")
         try:  # hyperparameters of a TrainingServer arrive as strings ("3")
             n = int(self.n_step)
         except (TypeError, ValueError):
@@ -132,6 +153,11 @@ def dqn_seeds(seed: int) -> tuple:
     """(env, replay-sample, evaluation) Philox keys of a run: three streams that never share draws."""
     env = (int(seed) * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
     return env, (env ^ 0x2545F4914F6CDD1D) & 0x7FFFFFFFFFFFFFFF, (env ^ 0x5851F42D4C957F2D) & 0x7FFFFFFFFFFFFFFF
+
+
+def dqn_noise_seed(seed: int) -> int:
+    """The fourth Philox key of a run: the NoisyNet unit normals (ops/noisy.py), a stream of their own."""
+    return (dqn_seeds(seed)[0] ^ 0x14057B7EF767814F) & 0x7FFFFFFFFFFFFFFF
 
 
 def epsilon_at(cfg: DQNConfig, epoch: int) -> float:
@@ -181,6 +207,17 @@ class DQNTrainer:
         self.head = GradHead.Q_DUEL if cfg.dueling else GradHead.Q_TD
         self._duel = dict(dueling=True) if cfg.dueling else {}  # a plain trainer passes what it always passed
         self.target = self.q.params.clone()
+        self.theta = None
+        if cfg.noisy:  # theta = [mu; sigma] with Adam state of 2P; the net's own tensors are its mu half
+            P = self.q.P
+            self.theta = torch.cat([self.q.params, noisy_sigma_init(self.q.spec, cfg.noisy_sigma0).to(dev)])
+            self.theta_m, self.theta_v = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+            self.theta_grad = torch.zeros_like(self.theta)
+            self.q.params, self.q.m, self.q.v = self.theta[:P], self.theta_m[:P], self.theta_v[:P]
+            self.target = self.theta.clone()
+            self.actor_w = torch.zeros(1, P, device=dev)   # role 0, composed once per rollout
+            self.update_w = torch.zeros(3, P, device=dev)  # roles 1, 2 (and 3), composed once per update
+            self.noise_seed = dqn_noise_seed(cfg.seed)
         self.ring = ReplayRing.allocate(C, N, D, dev)
         self.state = torch.zeros(N, NS, device=dev)
         self.ep_len = torch.zeros(N, dtype=torch.int32, device=dev)
@@ -222,8 +259,8 @@ class DQNTrainer:
         T = cfg.rollout_len
         self.last_epsilon = self.epsilon()
         self.last_beta = beta_at(cfg, self.epoch)  # the exponent of this epoch's updates
-        rc = dqn_rollout(self.env_id, self.q.params, cfg.hidden, T, self.cursor, self.ring, self.state, self.ep_len,
-                         self.ep_ret, self.ep_stats, seed=self.env_seed, step0=self.epoch * T,
+        rc = dqn_rollout(self.env_id, self._actor_params(), cfg.hidden, T, self.cursor, self.ring, self.state,
+                         self.ep_len, self.ep_ret, self.ep_stats, seed=self.env_seed, step0=self.epoch * T,
                          epsilon=self.last_epsilon, reset_all=self._first, max_steps=self.max_steps, **self._duel)
         if rc != 0:
             raise RuntimeError(f"dqn_rollout refused slot {self.cursor} of {cfg.buffer_slots} (code {rc})")
@@ -235,32 +272,62 @@ class DQNTrainer:
         self.cursor = (self.cursor + T) % cfg.buffer_slots
         self.slots_written += T
 
+    def _actor_params(self) -> torch.Tensor:
+        """What the actor acts on: the online net, or (noisy) its role-0 sample of this epoch, shared by all
+        envs and all T steps of the launch."""
+        if self.theta is None:
+            return self.q.params
+        noisy_compose(self.theta, (0,), (self.epoch,), self.q.spec, self.noise_seed, out=self.actor_w)
+        return self.actor_w[0]
+
+    def _update_params(self):
+        """(selecting online net, target net, online net of the loss): the nets themselves, or (noisy) three
+        independent samples at draw = the update index from one compose launch."""
+        if self.theta is None:
+            return self.q.params, self.target, self.q.params
+        n = 3 if self.cfg.double_q else 2
+        noisy_compose((self.theta, self.target, self.theta)[:n], (1, 2, 3)[:n], (self.updates,) * n, self.q.spec,
+                      self.noise_seed, out=self.update_w[:n])
+        select = self.update_w[2] if self.cfg.double_q else self.update_w[0]  # read only with double_q
+        return select, self.update_w[1], self.update_w[0]
+
+    def _apply(self):
+        """One Adam step from the gradient slabs; (noisy) on [mu; sigma] from the slabs of the role-1 sample."""
+        if self.theta is None:
+            return self.q.apply(self.slab)
+        q = self.q
+        noisy_grad(self.slab, 1, self.updates, q.spec, self.noise_seed, out=self.theta_grad)
+        adam_step(self.theta, self.theta_m, self.theta_v, q.step, q.ticket, q.lr, grad=self.theta_grad,
+                  beta1=q.betas[0], beta2=q.betas[1], eps=q.eps, weight_decay=q.weight_decay)
+        q.version += 1
+
     def update(self):
         """One gradient step on a freshly sampled batch; the target network follows on its schedule."""
         cfg = self.cfg
+        online, target, params = self._update_params()
         filled = min(self.slots_written, cfg.buffer_slots) * cfg.num_envs
         # n-step walks end at the slot the rollout wrote last: the one before the cursor
         nstep = dict(n_step=cfg.n_step, newest=(self.cursor - 1) % cfg.buffer_slots) if cfg.n_step > 1 else {}
         if self.per is None:
-            dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
+            dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None),
                         **nstep, **self._duel)
-            mlp_grad(self.head, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+            mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
-            self.q.apply(self.slab)
+            self._apply()
         else:
-            dqn_targets(self.q.params, self.target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
+            dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, tree=self.per.tree, beta=self.last_beta,
                         out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep, **self._duel)
-            mlp_grad(self.head, self.q.params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+            mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
                      w_norm=self.wmax, td_abs=self.td_abs)
-            self.q.apply(self.slab)
+            self._apply()
             per_update(self.per, self.idx, self.td_abs, cfg.per_alpha, cfg.per_eps)
         self.updates += 1
         self._has_loss = True
         if self.updates % cfg.target_update_every == 0:
-            self.target.copy_(self.q.params)
+            self.target.copy_(self.q.params if self.theta is None else self.theta)
 
     def train_epoch(self):
         cfg = self.cfg
@@ -275,7 +342,8 @@ class DQNTrainer:
     def evaluate(self, episodes: int = 1, num_envs: Optional[int] = None, greedy: bool = True):
         """Score the greedy policy of the online network: ``num_envs`` fresh envs x ``episodes`` whole
         episodes (the evaluator's argmax over "logits" is the greedy Q-policy).  It reads the weights
-        and touches none of the training state or the ring; its Philox stream is its own."""
+        and touches none of the training state or the ring; its Philox stream is its own.  A noisy net is
+        scored at zero noise: on ``mu``, which ``self.q.params`` is."""
         if not greedy:
             raise ValueError("a DQN policy is evaluated greedily: softmax-of-Q is not this algorithm's policy")
         from ..ops import evaluate_policy_op
@@ -304,7 +372,10 @@ class DQNTrainer:
             if ls[5] > 0:
                 loss_q, q_vals = ls[0] / ls[5], ls[4] / ls[5]
         out.update(LossQ=loss_q, QVals=q_vals, Epsilon=self.last_epsilon, Updates=self.updates,
-                   EnvSteps=self.env_steps, WorldSize=1, NStep=self.cfg.n_step, Dueling=bool(self.cfg.dueling))
+                   EnvSteps=self.env_steps, WorldSize=1, NStep=self.cfg.n_step, Dueling=bool(self.cfg.dueling),
+                   Noisy=bool(self.cfg.noisy))
+        if self.theta is not None:
+            out.update(SigmaMeanAbs=float(self.theta[self.q.P:].abs().mean().item()))
         if self.per is not None:
             out.update(Beta=self.last_beta, PriorityMax=float(self.per.pmax.item()))
         return out
@@ -321,9 +392,13 @@ class DQNTrainer:
     # ------------------------------------------------------------------ state
     def snapshot_tensors(self):
         q = self.q
-        ts = [q.params, q.m, q.v, q.step, self.target, *self.ring, self.state, self.ep_len, self.ep_ret]
+        P = q.P  # of a noisy trainer q.params / q.m / q.v and target[:P] are the mu halves
+        target = self.target if self.theta is None else self.target[:P]
+        ts = [q.params, q.m, q.v, q.step, target, *self.ring, self.state, self.ep_len, self.ep_ret]
         if self.per is not None:  # at the end: the names of the uniform trainer's tensors keep their places
             ts += [self.per.tree, self.per.pmax]
+        if self.theta is not None:  # and the sigma halves after those
+            ts += [self.theta[P:], self.theta_m[P:], self.theta_v[P:], self.target[P:]]
         return ts
 
     def counters(self) -> dict:
@@ -338,13 +413,17 @@ class DQNTrainer:
         """Everything a bit-exact resume needs.  ``learner/pi/params`` is the online network, the
         layout ``launcher.evaluate_checkpoint_state`` reads."""
         sd = {"cfg": self.cfg.to_dict(),
-              "learner": {"pi": self.q.state_dict(), "target": {"params": self.target.cpu()}},
+              "learner": {"pi": self.q.state_dict(), "target": {"params": self.target[:self.q.P].cpu()}},
               "ring": {k: t.cpu() for k, t in self.ring._asdict().items()},
               "epoch": self.epoch, "env_steps": self.env_steps, "updates": self.updates, "cursor": self.cursor,
               "slots_written": self.slots_written, "eval_step0": self.eval_step0,
               "env_state": self.state.cpu(), "ep_len": self.ep_len.cpu(), "ep_ret": self.ep_ret.cpu()}
         if self.per is not None:  # the tree is a pure function of its leaves: load_state_dict rebuilds it
             sd["per"] = {"leaves": self.per.leaves.cpu(), "pmax": float(self.per.pmax.item())}
+        if self.theta is not None:  # learner/pi and learner/target hold the mu halves: the evaluators read them
+            P = self.q.P
+            sd["noisy"] = {"sigma": self.theta[P:].cpu(), "m": self.theta_m[P:].cpu(), "v": self.theta_v[P:].cpu(),
+                           "target_sigma": self.target[P:].cpu()}
         return sd
 
     def load_state_dict(self, sd: dict):
@@ -357,8 +436,17 @@ class DQNTrainer:
             raise ValueError(f"this trainer has dueling={mine} ({self.q.P} parameters); the checkpoint has "
                              f"dueling={bool(theirs)} ({got} parameters): build the trainer with the checkpoint's "
                              "dueling setting")
+        mine, theirs = bool(self.cfg.noisy), bool(sd.get("cfg", {}).get("noisy", False)) or "noisy" in sd
+        if mine != theirs:
+            raise ValueError(f"this trainer has noisy={mine}; the checkpoint has noisy={theirs}"
+                             f"{'' if theirs else ' (no sigma)'}: build the trainer with the checkpoint's noisy setting")
         self.q.load_state_dict(sd["learner"]["pi"])
-        self.target.copy_(sd["learner"]["target"]["params"].to(self.device))
+        self.target[:self.q.P].copy_(sd["learner"]["target"]["params"].to(self.device))
+        if self.theta is not None:
+            P, nz = self.q.P, sd["noisy"]
+            for dst, k in ((self.theta, "sigma"), (self.theta_m, "m"), (self.theta_v, "v"),
+                           (self.target, "target_sigma")):
+                dst[P:].copy_(nz[k].to(self.device))
         for k, t in self.ring._asdict().items():
             src = sd["ring"][k]
             if tuple(src.shape) != tuple(t.shape):

@@ -98,6 +98,16 @@ PRESETS: Dict[str, Preset] = {
                 "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
                 "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
                 "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "dueling": True}),
+    "cartpole-dqn-noisy": Preset(
+        "cartpole-dqn-noisy", "cartpole-dqn-dueling with NoisyNet exploration: W = mu + sigma * eps (factorised "
+        "Gaussian noise) in all three layers, composed by one small kernel per rollout and per update, and no "
+        "epsilon schedule (--set noisy=true on any DQN preset is the same mechanism)",
+        "vec", {"env": "CartPole-v1", "algo": "dqn", "num_envs": 1024, "rollout_len": 4, "buffer_slots": 256,
+                "batch_size": 1024, "updates_per_epoch": 4, "gamma": 0.99, "q_lr": 5e-4, "eps_start": 0.0,
+                "eps_end": 0.0, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
+                "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
+                "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "dueling": True,
+                "noisy": True}),
 }
 
 
