@@ -1,5 +1,5 @@
 // Bindings of the DQN kernels (csrc/kernels/dqn.hip): the epsilon-greedy actor that fills the replay
-// ring and the sample + gather + TD-target kernel, uniform and prioritised, of the priority sum
+// ring and the sample + gather + TD-target launch (one dqn_targets for every form), of the priority sum
 // tree (csrc/kernels/per.hip) and of the noisy layers (csrc/kernels/noisy.hip).  Every tensor is
 // validated before a launch.
 #include <algorithm>
@@ -69,71 +69,6 @@ int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int
   return 0;
 }
 
-// What every form of the targets launch checks; the ring's N, D, the batch size and the online pointer.
-struct TargetCall {
-  int64_t N, D, B, L;
-  const float* online;
-};
-
-TargetCall check_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
-                         const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled,
-                         bool double_q, const Tensor& Xb, const Tensor& act_b, const Tensor& y, bool dueling) {
-  TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
-  const int64_t D = obs.size(2);
-  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
-  TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  const int64_t AO = dueling_outputs(A, dueling);
-  auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
-  TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
-  const int64_t P = H * D + H + H * H + H + AO * H + AO;
-  check(target, "target", at::kFloat, P);
-  const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
-  TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
-  check(y, "y", at::kFloat);
-  const int64_t B = y.numel();
-  TORCH_CHECK(B >= 1 && B * D < (int64_t)INT32_MAX, "batch size out of range");
-  check(Xb, "Xb", at::kFloat, B * D);
-  check(act_b, "act_b", at::kInt, B);
-  return {N, D, B, C * N, on};
-}
-
-// The n-step forms: N is the ring's; n_step, filled % N and newest are the entry point's to refuse.
-void dqn_targets_nstep(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
-                       const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled,
-                       double gamma, bool double_q, int64_t sample_key, int64_t update, int64_t n_step, int64_t newest,
-                       const Tensor& Xb, const Tensor& act_b, const Tensor& y, const OptT& idx, const OptT& last,
-                       bool dueling) {
-  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y,
-                                     dueling);
-  TORCH_CHECK(std::abs(n_step) < (int64_t)INT32_MAX && std::abs(newest) < (int64_t)INT32_MAX,
-              "n_step / newest out of range");
-  int* ix = opt_ptr<int>(idx, "idx", at::kInt, c.B);
-  int* la = opt_ptr<int>(last, "last", at::kInt, c.B);
-  check_rc(rrl_dqn_targets_nstep(c.online, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
-                                 act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(),
-                                 (long long)filled, (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0,
-                                 (uint64_t)sample_key, (uint64_t)update, (int)n_step, (int)c.N, (int)newest,
-                                 Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(), ix, la,
-                                 dueling ? 1 : 0, grid_cus(), cur_stream()),
-           "dqn_targets_nstep");
-}
-
-void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
-                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
-                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
-                 const OptT& idx, bool dueling) {
-  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y,
-                                     dueling);
-  int* ix = opt_ptr<int>(idx, "idx", at::kInt, c.B);
-  check_rc(rrl_dqn_targets(c.online, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
-                           act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(), (long long)filled,
-                           (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0, (uint64_t)sample_key,
-                           (uint64_t)update, Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(), ix,
-                           dueling ? 1 : 0, grid_cus(), cur_stream()),
-           "dqn_targets");
-}
-
 // ------------------------------------------------------------------ prioritised replay (per.hip)
 int64_t per_tree_leaves(int64_t L) { return rrl_per_tree_leaves((long long)L); }
 
@@ -173,51 +108,72 @@ void per_update(const Tensor& tree, const Tensor& pmax, int64_t L, const Tensor&
            "per_update");
 }
 
-void dqn_targets_per_nstep(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
-                           const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done,
-                           const Tensor& tree, int64_t filled, double gamma, bool double_q, double beta,
-                           int64_t sample_key, int64_t update, int64_t n_step, int64_t newest, const Tensor& Xb,
-                           const Tensor& act_b, const Tensor& y, const Tensor& idx, const Tensor& w, const Tensor& wmax,
-                           const OptT& last, bool dueling) {
-  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y,
-                                     dueling);
-  TORCH_CHECK(beta > 0.0 && beta <= 1.0, "beta must be in (0, 1], got ", beta);
-  TORCH_CHECK(std::abs(n_step) < (int64_t)INT32_MAX && std::abs(newest) < (int64_t)INT32_MAX,
+// ------------------------------------------------------------------ TD targets (dqn.hip)
+// One launch for every form: a tree selects the prioritised one (it needs beta, idx, w and wmax, which are not
+// looked at without one), n_step > 1 the walk.  Without `newest` there is no walk to check and the slots are one
+// row each (N = 1, newest = 0); with it N is the ring's, and n_step, filled % N and newest are the entry point's
+// to refuse.
+void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
+                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
+                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
+                 const OptT& idx, const OptT& tree, std::optional<double> beta, const OptT& w, const OptT& wmax,
+                 int64_t n_step, std::optional<int64_t> newest, const OptT& last, bool dueling) {
+  TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
+  const int64_t D = obs.size(2);
+  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
+  TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
+  TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
+  const int64_t AO = dueling_outputs(A, dueling);
+  auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
+  TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
+  const int64_t P = H * D + H + H * H + H + AO * H + AO;
+  check(target, "target", at::kFloat, P);
+  const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
+  TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
+  check(y, "y", at::kFloat);
+  const int64_t B = y.numel();
+  TORCH_CHECK(B >= 1 && B * D < (int64_t)INT32_MAX, "batch size out of range");
+  check(Xb, "Xb", at::kFloat, B * D);
+  check(act_b, "act_b", at::kInt, B);
+  const int64_t nw = newest.value_or(0);
+  TORCH_CHECK(std::abs(n_step) < (int64_t)INT32_MAX && std::abs(nw) < (int64_t)INT32_MAX,
               "n_step / newest out of range");
-  check_tree(tree, wmax, "wmax", c.L);
-  check(idx, "idx", at::kInt, c.B);
-  check(w, "w", at::kFloat, c.B);
-  int* la = opt_ptr<int>(last, "last", at::kInt, c.B);
-  check_rc(rrl_dqn_targets_per_nstep(c.online, target.data_ptr<float>(), obs.data_ptr<float>(),
-                                     nobs.data_ptr<float>(), act.data_ptr<int>(), rew.data_ptr<float>(),
-                                     done.data_ptr<float>(), tree.data_ptr<float>(), (long long)c.L, (long long)filled,
-                                     (int)c.B, (int)c.D, (int)A, (int)H, (float)gamma, double_q ? 1 : 0, (float)beta,
-                                     (uint64_t)sample_key, (uint64_t)update, (int)n_step, (int)c.N, (int)newest,
-                                     Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(),
-                                     idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), la,
-                                     dueling ? 1 : 0, grid_cus(), cur_stream()),
-           "dqn_targets_per_nstep");
-}
-
-void dqn_targets_per(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
-                     const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& tree,
-                     int64_t filled, double gamma, bool double_q, double beta, int64_t sample_key, int64_t update,
-                     const Tensor& Xb, const Tensor& act_b, const Tensor& y, const Tensor& idx, const Tensor& w,
-                     const Tensor& wmax, bool dueling) {
-  const TargetCall c = check_targets(online, target, H, A, obs, nobs, act, rew, done, filled, double_q, Xb, act_b, y,
-                                     dueling);
-  TORCH_CHECK(beta > 0.0 && beta <= 1.0, "beta must be in (0, 1], got ", beta);
-  check_tree(tree, wmax, "wmax", c.L);
-  check(idx, "idx", at::kInt, c.B);
-  check(w, "w", at::kFloat, c.B);
-  check_rc(rrl_dqn_targets_per(c.online, target.data_ptr<float>(), obs.data_ptr<float>(), nobs.data_ptr<float>(),
-                               act.data_ptr<int>(), rew.data_ptr<float>(), done.data_ptr<float>(),
-                               tree.data_ptr<float>(), (long long)c.L, (long long)filled, (int)c.B, (int)c.D, (int)A,
-                               (int)H, (float)gamma, double_q ? 1 : 0, (float)beta, (uint64_t)sample_key,
-                               (uint64_t)update, Xb.data_ptr<float>(), act_b.data_ptr<int>(), y.data_ptr<float>(),
-                               idx.data_ptr<int>(), w.data_ptr<float>(), wmax.data_ptr<float>(), dueling ? 1 : 0,
-                               grid_cus(), cur_stream()),
-           "dqn_targets_per");
+  DqnTargetsCall c{};
+  if (tree.has_value()) {
+    TORCH_CHECK(beta.has_value() && idx.has_value() && w.has_value() && wmax.has_value(),
+                "the prioritised form needs beta, idx, w and wmax");
+    TORCH_CHECK(*beta > 0.0 && *beta <= 1.0, "beta must be in (0, 1], got ", *beta);
+    check_tree(*tree, *wmax, "wmax", C * N);
+    check(*w, "w", at::kFloat, B);
+    c.tree = tree->data_ptr<float>();
+    c.L = C * N;
+    c.beta = (float)*beta;
+    c.w = w->data_ptr<float>();
+    c.wmax = wmax->data_ptr<float>();
+  }
+  c.online = on;
+  c.target = target.data_ptr<float>();
+  c.obs = obs.data_ptr<float>();
+  c.nobs = nobs.data_ptr<float>();
+  c.act = act.data_ptr<int>();
+  c.rew = rew.data_ptr<float>();
+  c.done = done.data_ptr<float>();
+  c.filled = filled;
+  c.B = (int)B, c.D = (int)D, c.A = (int)A, c.H = (int)H;
+  c.gamma = (float)gamma;
+  c.double_q = double_q ? 1 : 0;
+  c.dueling = dueling ? 1 : 0;
+  c.sample_key = (uint64_t)sample_key;
+  c.update = (uint64_t)update;
+  c.Xb = Xb.data_ptr<float>();
+  c.act_b = act_b.data_ptr<int>();
+  c.y = y.data_ptr<float>();
+  c.idx = opt_ptr<int>(idx, "idx", at::kInt, B);
+  c.n_step = (int)n_step;
+  c.N = newest.has_value() ? (int)N : 1;
+  c.newest = (int)nw;
+  c.last = opt_ptr<int>(last, "last", at::kInt, B);
+  check_rc(rrl_dqn_targets(&c, grid_cus(), cur_stream()), "dqn_targets");
 }
 
 // ------------------------------------------------------------------ noisy layers (noisy.hip)
@@ -291,11 +247,6 @@ void register_dqn_ops(pybind11::module_& m) {
         py::arg("slot0"));
   m.def("per_update", &per_update, py::arg("tree"), py::arg("pmax"), py::arg("L"), py::arg("idx"), py::arg("td_abs"),
         py::arg("alpha"), py::arg("prio_eps"));
-  m.def("dqn_targets_per", &dqn_targets_per, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
-        py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("tree"),
-        py::arg("filled"), py::arg("gamma"), py::arg("double_q"), py::arg("beta"), py::arg("sample_key"),
-        py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("w"),
-        py::arg("wmax"), py::arg("dueling") = false);
   m.def("dqn_rollout_grid", &dqn_rollout_grid);
   m.def("dqn_rollout", &dqn_rollout, py::arg("env"), py::arg("params"), py::arg("H"), py::arg("T"), py::arg("slot0"),
         py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"), py::arg("act"),
@@ -304,16 +255,7 @@ void register_dqn_ops(pybind11::module_& m) {
   m.def("dqn_targets", &dqn_targets, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"), py::arg("obs"),
         py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"), py::arg("gamma"),
         py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"),
-        py::arg("idx"), py::arg("dueling") = false);
-  m.def("dqn_targets_nstep", &dqn_targets_nstep, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
-        py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"),
-        py::arg("gamma"), py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("n_step"),
-        py::arg("newest"), py::arg("Xb"), py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("last"),
-        py::arg("dueling") = false);
-  m.def("dqn_targets_per_nstep", &dqn_targets_per_nstep, py::arg("online"), py::arg("target"), py::arg("H"),
-        py::arg("A"), py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"),
-        py::arg("tree"), py::arg("filled"), py::arg("gamma"), py::arg("double_q"), py::arg("beta"),
-        py::arg("sample_key"), py::arg("update"), py::arg("n_step"), py::arg("newest"), py::arg("Xb"),
-        py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("w"), py::arg("wmax"), py::arg("last"),
-        py::arg("dueling") = false);
+        py::arg("idx"), py::arg("tree") = py::none(), py::arg("beta") = py::none(), py::arg("w") = py::none(),
+        py::arg("wmax") = py::none(), py::arg("n_step") = 1, py::arg("newest") = py::none(),
+        py::arg("last") = py::none(), py::arg("dueling") = false);
 }

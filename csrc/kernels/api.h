@@ -30,6 +30,27 @@ enum GradHead : int {
 
 enum EnvId : int { ENV_CARTPOLE = 0, ENV_MOUNTAINCAR = 1, ENV_ACROBOT = 2, ENV_LUNARLANDER = 3, ENV_HALFCHEETAH = 4 };
 
+// The arguments of rrl_dqn_targets, which has the contract.
+struct DqnTargetsCall {
+  const float *online, *target;  // nets: MLPSpec(D, H, A + dueling); online is read with double_q only
+  const float *obs, *nobs;       // ring: rows [slot][env] of D floats, the first `filled` of them are sampled
+  const int* act;
+  const float *rew, *done;       // done: 0 running, 1 terminal, 2 time-limit truncation
+  long long filled;
+  int B, D, A, H;                // shape: batch rows, obs dim, actions, hidden size
+  float gamma;                   // target
+  int double_q, dueling;
+  uint64_t sample_key, update;   // sampling
+  float *Xb, *y;                 // outputs: Xb [B][D], y [B]
+  int *act_b, *idx;              // [B] each; idx may be null without a tree
+  const float* tree;             // prioritised part, used iff tree != nullptr: [2 * P2] over the ring's L rows
+  long long L;
+  float beta;
+  float *w, *wmax;               // [B], [1]
+  int n_step, N, newest;         // walk: N envs per slot, newest the slot written last
+  int* last;                     // [B], may be null; n_step, N, newest, last = 1, 1, 0, nullptr is "no walk"
+};
+
 }  // namespace rrl
 
 extern "C" {
@@ -152,50 +173,25 @@ int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, in
                     float* ep_ret, float* obs, float* nobs, int* act, float* rew, float* done, float* ep_stats,
                     uint64_t seed, uint64_t step0, float epsilon, int reset_all, int max_steps, int dueling,
                     int num_cu, void* stream);
-// Batch row b of update `update` samples ring row r = (philox((b, update, 0), sample_key).x * filled) >> 32
-// of the first `filled` rows ([slot][env] order), gathers obs[r] -> Xb[b], act[r] -> act_b[b], r -> idx[b]
-// (idx may be null) and writes y[b] = rew[r] + gamma * (done[r] == 1 ? 0 : 1) * Q_target(nobs[r], a*), a* =
-// the lowest-index argmax of Q_target (double_q = 0) or Q_online (double_q = 1; online may be null
-// otherwise).  -1: a null pointer; -2: filled < 1 or >= 2^31, or B < 1; -3: H not 64 / 128, D outside
-// [1, 16] or A outside [1, 16].  dueling != 0 (all four forms): online and target are dueling nets of A + 1
-// outputs (HEAD_Q_DUEL has the combine), a* is the lowest-index argmax of the selecting net's A advantage
-// outputs and Q_target(., a*) the dueling Q of the target net; -3 then also for A > 15.  The sampled rows and
-// every output but y do not depend on it
-int rrl_dqn_targets(const float* online, const float* target, const float* obs, const float* nobs, const int* act,
-                    const float* rew, const float* done, long long filled, int B, int D, int A, int H, float gamma,
-                    int double_q, uint64_t sample_key, uint64_t update, float* Xb, int* act_b, float* y, int* idx,
-                    int dueling, int num_cu, void* stream);
-// The prioritised form: batch row b descends the sum tree of per.hip (L = the ring's C * N rows, leaf of
-// row r at tree[P2 + r]) with m = (b + u01(philox((b, update, 1), sample_key).x)) * (tree[1] / B), exactly
-// log2(P2) steps `if (m >= left && right > 0) { m -= left; go right } else go left`, and clamps the row to
-// [0, filled - 1].  On top of rrl_dqn_targets' outputs (idx is mandatory) it writes w[b] = (filled * leaf /
-// tree[1])^-beta and *wmax = max_b w[b] (reset by the launcher, a bit-pattern maximum: the same bits every
-// launch).  -1: a null pointer; -2: filled outside [1, L], L < 1 or >= 2^30, or B < 1; -3: as rrl_dqn_targets
-int rrl_dqn_targets_per(const float* online, const float* target, const float* obs, const float* nobs,
-                        const int* act, const float* rew, const float* done, const float* tree, long long L,
-                        long long filled, int B, int D, int A, int H, float gamma, int double_q, float beta,
-                        uint64_t sample_key, uint64_t update, float* Xb, int* act_b, float* y, int* idx, float* w,
-                        float* wmax, int dueling, int num_cu, void* stream);
-// The n-step forms of the two above.  The ring is time-major with N envs per slot, `filled` a multiple of N
-// and `newest` the slot written last.  The sampled row r0 walks forward before the bootstrap:
+// The TD targets of one update.  Batch row b samples ring row r0, gathers obs[r0] -> Xb[b], act[r0] -> act_b[b],
+// r0 -> idx[b], walks to the row `last` (last[b] <- last) and writes, a* being the lowest-index argmax of
+// Q_target(nobs[last], .) (double_q = 0) or of Q_online (double_q = 1),
+//   y[b] = G + disc * (done[last] == 1 ? 0 : 1) * Q_target(nobs[last], a*).
+// Sampling: r0 = (philox((b, update, 0), sample_key).x * filled) >> 32; with a tree (per.hip, leaf of row r at
+// tree[P2 + r]) b descends it with m = (b + u01(philox((b, update, 1), sample_key).x)) * (tree[1] / B), exactly
+// log2(P2) steps `if (m >= left && right > 0) { m -= left; go right } else go left`, r0 is clamped to [0, filled - 1],
+// w[b] = (filled * leaf / tree[1])^-beta and *wmax = max_b w[b] (reset on the stream before the launch, a
+// bit-pattern maximum: the same bits every launch).  The walk, in fp32 and in this order:
 //   last = r0; G = rew[r0]; disc = gamma; m = 1
 //   while (m < n_step && done[last] == 0 && last / N != newest) {
 //     last += N; if (last >= filled) last -= filled;  G = fma(disc, rew[last], G);  disc *= gamma;  ++m; }
-//   y[b] = G + disc * (done[last] == 1 ? 0 : 1) * Q_target(nobs[last], a*),   a* chosen at nobs[last]
-// in fp32, in this order.  Xb, act_b, idx (and w, wmax) refer to r0 as before; last[b] (may be null) <- last.
-// n_step == 1 launches the one-step kernel (last = idx then: it needs idx).  The codes of the one-step forms,
-// and (nothing written) -2: n_step < 1, N < 1 or filled % N != 0; -4: newest outside [0, filled / N)
-int rrl_dqn_targets_nstep(const float* online, const float* target, const float* obs, const float* nobs,
-                          const int* act, const float* rew, const float* done, long long filled, int B, int D, int A,
-                          int H, float gamma, int double_q, uint64_t sample_key, uint64_t update, int n_step, int N,
-                          int newest, float* Xb, int* act_b, float* y, int* idx, int* last, int dueling, int num_cu,
-                          void* stream);
-int rrl_dqn_targets_per_nstep(const float* online, const float* target, const float* obs, const float* nobs,
-                              const int* act, const float* rew, const float* done, const float* tree, long long L,
-                              long long filled, int B, int D, int A, int H, float gamma, int double_q, float beta,
-                              uint64_t sample_key, uint64_t update, int n_step, int N, int newest, float* Xb,
-                              int* act_b, float* y, int* idx, float* w, float* wmax, int* last, int dueling,
-                              int num_cu, void* stream);
+// n_step == 1 launches the one-step kernel, which has no walk, and then copies idx to last.  dueling != 0: the
+// nets have A + 1 outputs (HEAD_Q_DUEL has the combine), a* is the argmax of the selecting net's A advantages and
+// Q_target the target net's dueling Q; only y depends on it.  Refusals write nothing and are checked in this order.
+// -1: a null pointer (online with double_q; idx, w, wmax with a tree; idx with last at n_step == 1); -2: B < 1,
+// filled outside [1, 2^31) or, with a tree, outside [1, L], L outside [1, 2^30]; -3: H not 64 / 128, D outside
+// [1, 16], A < 1 or A + dueling > 16; -2: n_step < 1, N < 1 or filled % N != 0; -4: newest outside [0, filled / N)
+int rrl_dqn_targets(const rrl::DqnTargetsCall* c, int num_cu, void* stream);
 
 // ---- per.hip
 // The priority sum tree of prioritised replay over a ring of L = C * N rows: fp32 tree[2 * P2], P2 =

@@ -376,14 +376,29 @@ static int launch_dqn_targets(const std::conditional_t<NSTEP, DqnNStepArgs, DqnT
   return (int)hipGetLastError();
 }
 
-// The instance of (PER, NSTEP) for H in {64, 128} and a plain or a dueling pair of nets.
-template <bool PER, bool NSTEP>
-static int dispatch_dqn_targets(const std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>& a, int H, int dueling,
-                                int grid, hipStream_t s) {
-  if (dueling)
-    return H == 128 ? launch_dqn_targets<8, PER, NSTEP, true>(a, grid, s)
-                    : launch_dqn_targets<4, PER, NSTEP, true>(a, grid, s);
-  return H == 128 ? launch_dqn_targets<8, PER, NSTEP>(a, grid, s) : launch_dqn_targets<4, PER, NSTEP>(a, grid, s);
+// The instance of (H, PER, NSTEP, DUEL); the one-step instances take the base of the block.  The order of the
+// cases has no functional meaning: it only keeps the kernels in the order they always had in the code object.
+static int dispatch_dqn_targets(const DqnNStepArgs& a, int H, bool per, bool nstep, bool duel, int grid,
+                                hipStream_t s) {
+  const DqnTargetArgs& one = a;
+  switch ((per ? 8 : 0) | (nstep ? 4 : 0) | (duel ? 2 : 0) | (H == 128 ? 1 : 0)) {
+    case 3: return launch_dqn_targets<8, false, false, true>(one, grid, s);
+    case 2: return launch_dqn_targets<4, false, false, true>(one, grid, s);
+    case 1: return launch_dqn_targets<8, false, false, false>(one, grid, s);
+    case 0: return launch_dqn_targets<4, false, false, false>(one, grid, s);
+    case 7: return launch_dqn_targets<8, false, true, true>(a, grid, s);
+    case 6: return launch_dqn_targets<4, false, true, true>(a, grid, s);
+    case 5: return launch_dqn_targets<8, false, true, false>(a, grid, s);
+    case 4: return launch_dqn_targets<4, false, true, false>(a, grid, s);
+    case 11: return launch_dqn_targets<8, true, false, true>(one, grid, s);
+    case 10: return launch_dqn_targets<4, true, false, true>(one, grid, s);
+    case 9: return launch_dqn_targets<8, true, false, false>(one, grid, s);
+    case 8: return launch_dqn_targets<4, true, false, false>(one, grid, s);
+    case 15: return launch_dqn_targets<8, true, true, true>(a, grid, s);
+    case 14: return launch_dqn_targets<4, true, true, true>(a, grid, s);
+    case 13: return launch_dqn_targets<8, true, true, false>(a, grid, s);
+    default: return launch_dqn_targets<4, true, true, false>(a, grid, s);
+  }
 }
 
 static int dqn_targets_grid(int B, int num_cu) {
@@ -392,99 +407,41 @@ static int dqn_targets_grid(int B, int num_cu) {
   return grid > cap ? cap : grid;
 }
 
-// The checks the n-step entry points add, and the walk's launch arguments.  0, or the code to return.
-static int dqn_nstep_args(DqnNStepArgs& a, const DqnTargetArgs& one, long long filled, int n_step, int N,
-                          int newest, int* last) {
-  if (n_step < 1 || N < 1 || filled % N != 0) return -2;
-  if (newest < 0 || newest >= filled / N) return -4;
-  static_cast<DqnTargetArgs&>(a) = one;
-  a.n_step = n_step;
-  a.N = (uint32_t)N;
-  a.slots = (uint32_t)(filled / N);
-  a.newest_row = (uint32_t)newest * (uint32_t)N;
-  a.last = last;
-  return 0;
-}
-
-// n_step == 1 is the one-step kernel; its target bootstraps from the sampled row itself
-static int dqn_one_step_last(int* last, const int* idx, int B, hipStream_t s) {
-  if (last == nullptr) return 0;
-  return (int)hipMemcpyAsync(last, idx, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s);
-}
-
-// The one-step forms: n_step = 1 over slots of one row (N = 1 divides every filled, newest = 0 is in range).
-extern "C" int rrl_dqn_targets(const float* online, const float* target, const float* obs, const float* nobs,
-                               const int* act, const float* rew, const float* done, long long filled, int B, int D,
-                               int A, int H, float gamma, int double_q, uint64_t sample_key, uint64_t update,
-                               float* Xb, int* act_b, float* y, int* idx, int dueling, int num_cu, void* stream) {
-  return rrl_dqn_targets_nstep(online, target, obs, nobs, act, rew, done, filled, B, D, A, H, gamma, double_q,
-                               sample_key, update, 1, 1, 0, Xb, act_b, y, idx, nullptr, dueling, num_cu, stream);
-}
-
-extern "C" int rrl_dqn_targets_per(const float* online, const float* target, const float* obs, const float* nobs,
-                                   const int* act, const float* rew, const float* done, const float* tree,
-                                   long long L, long long filled, int B, int D, int A, int H, float gamma,
-                                   int double_q, float beta, uint64_t sample_key, uint64_t update, float* Xb,
-                                   int* act_b, float* y, int* idx, float* w, float* wmax, int dueling, int num_cu,
-                                   void* stream) {
-  return rrl_dqn_targets_per_nstep(online, target, obs, nobs, act, rew, done, tree, L, filled, B, D, A, H, gamma,
-                                   double_q, beta, sample_key, update, 1, 1, 0, Xb, act_b, y, idx, w, wmax, nullptr,
-                                   dueling, num_cu, stream);
-}
-
-extern "C" int rrl_dqn_targets_nstep(const float* online, const float* target, const float* obs, const float* nobs,
-                                     const int* act, const float* rew, const float* done, long long filled, int B,
-                                     int D, int A, int H, float gamma, int double_q, uint64_t sample_key,
-                                     uint64_t update, int n_step, int N, int newest, float* Xb, int* act_b, float* y,
-                                     int* idx, int* last, int dueling, int num_cu, void* stream) {
-  if (!target || (double_q && !online) || !obs || !nobs || !act || !rew || !done || !Xb || !act_b || !y) return -1;
-  if (n_step == 1 && last && !idx) return -1;
-  if (filled < 1 || filled > 0x7FFFFFFFll || B < 1) return -2;
-  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A + (dueling ? 1 : 0) > kMaxAct) return -3;
-  DqnTargetArgs a{online, target, obs, nobs, act, rew, done, B, D, A, (uint32_t)filled, gamma, double_q ? 1 : 0,
-                  (uint32_t)sample_key, (uint32_t)(sample_key >> 32), (uint32_t)update, (uint32_t)(update >> 32),
-                  Xb, act_b, y, idx};
-  DqnNStepArgs na;
-  if (const int rc = dqn_nstep_args(na, a, filled, n_step, N, newest, last)) return rc;
-  const int grid = dqn_targets_grid(B, num_cu);
+extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream) {
+  if (!c || !c->target || (c->double_q && !c->online) || !c->obs || !c->nobs || !c->act || !c->rew || !c->done ||
+      !c->Xb || !c->act_b || !c->y)
+    return -1;
+  const bool per = c->tree != nullptr, nstep = c->n_step != 1, duel = c->dueling != 0;
+  if (per ? (!c->idx || !c->w || !c->wmax) : (!nstep && c->last && !c->idx)) return -1;
+  const long long P2 = per ? rrl_per_tree_leaves(c->L) : 1, most = per ? c->L : 0x7FFFFFFFll;
+  if (P2 < 1 || c->filled < 1 || c->filled > most || c->B < 1) return -2;
+  if ((c->H != 64 && c->H != 128) || c->D < 1 || c->D > 16 || c->A < 1 || c->A + (duel ? 1 : 0) > kMaxAct) return -3;
+  if (c->n_step < 1 || c->N < 1 || c->filled % c->N != 0) return -2;
+  if (c->newest < 0 || c->newest >= c->filled / c->N) return -4;
+  DqnNStepArgs a;
+  static_cast<DqnTargetArgs&>(a) = {c->online, c->target, c->obs, c->nobs, c->act, c->rew, c->done, c->B, c->D, c->A,
+                                    (uint32_t)c->filled, c->gamma, c->double_q ? 1 : 0, (uint32_t)c->sample_key,
+                                    (uint32_t)(c->sample_key >> 32), (uint32_t)c->update, (uint32_t)(c->update >> 32),
+                                    c->Xb, c->act_b, c->y, c->idx};
+  a.n_step = c->n_step;
+  a.N = (uint32_t)c->N;
+  a.slots = (uint32_t)(c->filled / c->N);
+  a.newest_row = (uint32_t)c->newest * (uint32_t)c->N;
+  a.last = c->last;
   hipStream_t s = (hipStream_t)stream;
-  if (n_step == 1) {
-    const int rc = dispatch_dqn_targets<false, false>(a, H, dueling, grid, s);
-    return rc ? rc : dqn_one_step_last(last, idx, B, s);
+  if (per) {
+    a.tree = c->tree;
+    a.P2 = (uint32_t)P2;
+    for (a.levels = 0; (1ll << a.levels) < P2; ++a.levels) {
+    }
+    a.beta = c->beta;
+    a.w = c->w;
+    a.wmax = reinterpret_cast<int*>(c->wmax);
+    const hipError_t e = hipMemsetAsync(c->wmax, 0, sizeof(float), s);  // +0.0f: below every weight
+    if (e != hipSuccess) return (int)e;
   }
-  return dispatch_dqn_targets<false, true>(na, H, dueling, grid, s);
-}
-
-extern "C" int rrl_dqn_targets_per_nstep(const float* online, const float* target, const float* obs,
-                                         const float* nobs, const int* act, const float* rew, const float* done,
-                                         const float* tree, long long L, long long filled, int B, int D, int A, int H,
-                                         float gamma, int double_q, float beta, uint64_t sample_key, uint64_t update,
-                                         int n_step, int N, int newest, float* Xb, int* act_b, float* y, int* idx,
-                                         float* w, float* wmax, int* last, int dueling, int num_cu, void* stream) {
-  if (!target || (double_q && !online) || !obs || !nobs || !act || !rew || !done || !Xb || !act_b || !y) return -1;
-  if (!tree || !idx || !w || !wmax) return -1;
-  const long long P2 = rrl_per_tree_leaves(L);
-  if (P2 < 1 || filled < 1 || filled > L || B < 1) return -2;
-  if ((H != 64 && H != 128) || D < 1 || D > 16 || A < 1 || A + (dueling ? 1 : 0) > kMaxAct) return -3;
-  DqnTargetArgs a{online, target, obs, nobs, act, rew, done, B, D, A, (uint32_t)filled, gamma, double_q ? 1 : 0,
-                  (uint32_t)sample_key, (uint32_t)(sample_key >> 32), (uint32_t)update, (uint32_t)(update >> 32),
-                  Xb, act_b, y, idx};
-  a.tree = tree;
-  a.P2 = (uint32_t)P2;
-  for (a.levels = 0; (1ll << a.levels) < P2; ++a.levels) {
-  }
-  a.beta = beta;
-  a.w = w;
-  a.wmax = reinterpret_cast<int*>(wmax);
-  DqnNStepArgs na;
-  if (const int rc = dqn_nstep_args(na, a, filled, n_step, N, newest, last)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(wmax, 0, sizeof(float), s);  // +0.0f: below every weight
-  if (e != hipSuccess) return (int)e;
-  const int grid = dqn_targets_grid(B, num_cu);
-  if (n_step == 1) {
-    const int rc = dispatch_dqn_targets<true, false>(a, H, dueling, grid, s);
-    return rc ? rc : dqn_one_step_last(last, idx, B, s);
-  }
-  return dispatch_dqn_targets<true, true>(na, H, dueling, grid, s);
+  const int rc = dispatch_dqn_targets(a, c->H, per, nstep, duel, dqn_targets_grid(c->B, num_cu), s);
+  if (rc || nstep || !c->last) return rc;
+  // the one-step kernel has no walk: its target bootstraps from the sampled row itself
+  return (int)hipMemcpyAsync(c->last, c->idx, (size_t)c->B * sizeof(int), hipMemcpyDeviceToDevice, s);
 }

@@ -1,7 +1,7 @@
 // NoisyNet exploration (Fortunato et al. 2018, factorised Gaussian noise) for the DQN path.
 //
 // A noisy Q-network keeps theta = [mu (P); sigma (P)] in the flat MLPSpec layout and every kernel that reads
-// weights (dqn_rollout, dqn_targets*, mlp_grad) gets the effective parameters mu + sigma * eps of one
+// weights (dqn_rollout, dqn_targets, mlp_grad) gets the effective parameters mu + sigma * eps of one
 // (role, draw) instead.  So the feature is two small kernels around launches that stay as they are:
 //
 //   rrl_noisy_compose  out[k] = mu_k + sigma_k * eps(role_k, draw_k) for up to three jobs in one launch

@@ -72,12 +72,9 @@ def dqn_rollout(env_id: int, params: torch.Tensor, hidden: int, rollout_len: int
     if dueling:
         D, A, _, _ = h.env_dims(int(env_id))
         check_q_params(params, D, hidden, A, True)
-        return int(h.dqn_rollout(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len,
-                                 ep_ret, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed),
-                                 int(step0), float(epsilon), bool(reset_all), int(max_steps), True))
     return int(h.dqn_rollout(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len, ep_ret,
                              ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed), int(step0),
-                             float(epsilon), bool(reset_all), int(max_steps)))
+                             float(epsilon), bool(reset_all), int(max_steps), bool(dueling)))
 
 
 def dqn_sample_rows_ref(seed: int, update: int, B: int, filled: int) -> np.ndarray:
@@ -157,25 +154,32 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
     ``dueling``: both nets are dueling nets of ``A + 1`` outputs; ``a*`` is the lowest-index argmax of the
     selecting net's advantages and ``Q_target`` is ``reference.dueling_q`` of the target net."""
     D = ring.obs.shape[-1]
+    dev = ring.obs.device
     _check_q_nets(online if double_q else None, target, D, H, A, dueling)
-    if int(n_step) != 1:
-        return _dqn_targets_nstep_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree,
-                                      beta, n_step, newest, dueling)
+    n_step = int(n_step)
+    if n_step != 1:
+        check_nstep(n_step, newest, int(ring.act.shape[1]), int(filled))
     if tree is None:
         rows = dqn_sample_rows_ref(seed, update, B, filled)
     else:
         from .per import per_sample_rows_ref, per_weights_ref
 
         rows = per_sample_rows_ref(tree, seed, update, B, filled)
-        w = per_weights_ref(tree, rows, filled, beta, dtype).to(ring.obs.device)
-    idx = torch.from_numpy(rows).to(ring.obs.device)
-    obs = ring.obs.reshape(-1, D)[idx]
-    nobs = ring.nobs.reshape(-1, D)[idx].to(dtype)
+        w = per_weights_ref(tree, rows, filled, beta, dtype).to(dev)
+    idx = torch.from_numpy(rows).to(dev)
+    if n_step == 1:  # the walk of length one
+        last, G, disc = idx, ring.rew.reshape(-1)[idx].to(dtype), gamma
+    else:
+        last, G, disc = (torch.from_numpy(x).to(dev)
+                         for x in dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)[:3])
+    nobs = ring.nobs.reshape(-1, D)[last].to(dtype)
     q_t, astar = _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype)
-    boot = (ring.done.reshape(-1)[idx] != 1).to(dtype)
-    y = ring.rew.reshape(-1)[idx].to(dtype) + gamma * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
-    res = (obs, ring.act.reshape(-1)[idx].to(torch.int32), y, idx)
-    return res if tree is None else res + (w, w.max().reshape(1))
+    boot = (ring.done.reshape(-1)[last] != 1).to(dtype)
+    y = G + disc * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
+    res = (ring.obs.reshape(-1, D)[idx], ring.act.reshape(-1)[idx].to(torch.int32), y, idx)
+    if tree is not None:
+        res += (w, w.max().reshape(1))
+    return res if n_step == 1 else res + (last,)
 
 
 def _check_q_nets(online, target, D, H, A, dueling):
@@ -195,30 +199,6 @@ def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
     sel = ref.trunk(online.to(dtype), nobs, D, H, AO)[0] if double_q else out_t
     astar, _ = ref.greedy_from_logits(sel[..., :A])
     return (ref.dueling_q(out_t, A) if dueling else out_t), astar
-
-
-def _dqn_targets_nstep_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
-                           n_step, newest, dueling=False):
-    D = ring.obs.shape[-1]
-    dev = ring.obs.device
-    check_nstep(n_step, newest, int(ring.act.shape[1]), int(filled))
-    if tree is None:
-        rows = dqn_sample_rows_ref(seed, update, B, filled)
-    else:
-        from .per import per_sample_rows_ref, per_weights_ref
-
-        rows = per_sample_rows_ref(tree, seed, update, B, filled)
-        w = per_weights_ref(tree, rows, filled, beta, dtype).to(dev)
-    last_np, G, disc, _ = dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)
-    idx, last = torch.from_numpy(rows).to(dev), torch.from_numpy(last_np).to(dev)
-    nobs = ring.nobs.reshape(-1, D)[last].to(dtype)
-    q_t, astar = _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype)
-    boot = (ring.done.reshape(-1)[last] != 1).to(dtype)
-    y = torch.from_numpy(G).to(dev) + torch.from_numpy(disc).to(dev) * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
-    res = (ring.obs.reshape(-1, D)[idx], ring.act.reshape(-1)[idx].to(torch.int32), y, idx)
-    if tree is not None:
-        res += (w, w.max().reshape(1))
-    return res + (last,)
 
 
 def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
@@ -245,98 +225,47 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
 
     per = tree is not None
     dueling = bool(dueling)
-    duel = (True,) if dueling else ()  # a plain launch passes what it always passed
     _check_q_nets(online if double_q else None, target, ring.obs.shape[-1], H, A, dueling)
     if per and not (beta is not None and 0.0 < beta <= 1.0):
         raise ValueError(f"the prioritised form needs beta in (0, 1], got {beta}")
     n_step = int(n_step)
     base = 6 if per else 4
-    if n_step == 1 and out is not None and len(out) == base + 1:  # a one-step target bootstraps from its own row
-        dqn_targets(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, tuple(out[:base]), dtype,
-                    tree, beta, dueling=dueling)
-        if out[base] is not None:
-            if out[3] is None:
-                raise ValueError("at n_step = 1 last is idx: it cannot be written without idx")
-            out[base].copy_(out[3])
-        return out
     if n_step != 1:
-        return _dqn_targets_nstep(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, out, dtype,
-                                  tree, beta, n_step, newest, dueling)
-    if not use_hip(target):
-        res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
-                              dueling=dueling)
-        if out is not None:
-            for dst, src in zip(out, res):
-                if dst is not None:
-                    dst.copy_(src)
-            return out
-        return res
-    dev = target.device
-    D = ring.obs.shape[-1]
-    if out is None:
-        out = (torch.empty(B, D, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
-        if per:
-            out += (torch.empty(B, device=dev), torch.empty(1, device=dev))
-    if out[2].numel() != B:
-        raise ValueError(f"y must hold {B} targets, got {out[2].numel()}")
-    if per:
-        Xb, act_b, y, idx, w, wmax = out
-        if idx is None:
-            raise ValueError("the prioritised form writes idx: it cannot be skipped")
-        hip().dqn_targets_per(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act,
-                              ring.rew, ring.done, tree, int(filled), float(gamma), bool(double_q), float(beta),
-                              int(seed), int(update), Xb, act_b, y, idx, w, wmax, *duel)
-        return out
-    Xb, act_b, y, idx = out
-    hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
-                      ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), Xb, act_b, y, idx,
-                      *duel)
-    return out
-
-
-def _dqn_targets_nstep(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, out, dtype, tree, beta,
-                       n_step, newest, dueling=False):
-    from . import use_hip, hip
-
-    per = tree is not None
-    duel = (True,) if dueling else ()
-    base = 6 if per else 4
-    N = int(ring.act.shape[1])
-    n_step, newest = check_nstep(n_step, newest, N, int(filled))
+        n_step, newest = check_nstep(n_step, newest, int(ring.act.shape[1]), int(filled))
+    else:
+        newest = None  # the one-step launch has no walk to check
     if out is not None and len(out) not in (base, base + 1):
         raise ValueError(f"out must hold {base} tensors, or {base + 1} with a trailing last; got {len(out)}")
+    if n_step == 1 and out is not None and len(out) > base and out[base] is not None and out[3] is None:
+        raise ValueError("at n_step = 1 last is idx: it cannot be written without idx")
     if not use_hip(target):
         res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
                               n_step, newest, dueling)
-        if out is not None:
-            for dst, src in zip(out, res):
-                if dst is not None:
-                    dst.copy_(src)
-            return out
-        return res
+        if out is None:
+            return res
+        if n_step == 1:
+            res += (res[3],)  # a one-step target bootstraps from its own row
+        for dst, src in zip(out, res):
+            if dst is not None:
+                dst.copy_(src)
+        return out
     dev = target.device
-    D = ring.obs.shape[-1]
     if out is None:
-        out = (torch.empty(B, D, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+        out = (torch.empty(B, ring.obs.shape[-1], device=dev), torch.empty(B, dtype=torch.int32, device=dev),
                torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
         if per:
             out += (torch.empty(B, device=dev), torch.empty(1, device=dev))
-        out += (torch.empty(B, dtype=torch.int32, device=dev),)
+        if n_step != 1:
+            out += (torch.empty(B, dtype=torch.int32, device=dev),)
     if out[2].numel() != B:
         raise ValueError(f"y must hold {B} targets, got {out[2].numel()}")
-    last = out[base] if len(out) > base else None
-    if per:
-        Xb, act_b, y, idx, w, wmax = out[:6]
-        if idx is None:
-            raise ValueError("the prioritised form writes idx: it cannot be skipped")
-        hip().dqn_targets_per_nstep(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs,
-                                    ring.act, ring.rew, ring.done, tree, int(filled), float(gamma), bool(double_q),
-                                    float(beta), int(seed), int(update), n_step, newest, Xb, act_b, y, idx, w, wmax,
-                                    last, *duel)
-        return out
-    Xb, act_b, y, idx = out[:4]
-    hip().dqn_targets_nstep(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act,
-                            ring.rew, ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update),
-                            n_step, newest, Xb, act_b, y, idx, last, *duel)
+    if per and out[3] is None:
+        raise ValueError("the prioritised form writes idx: it cannot be skipped")
+    w, wmax = out[4:6] if per else (None, None)
+    # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling) in its order: a positional call
+    # parses faster than a keyword one, and this is the one place that makes it
+    hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
+                      ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), *out[:4], tree,
+                      float(beta) if per else None, w, wmax, n_step, newest,
+                      out[base] if len(out) > base else None, dueling)
     return out

@@ -229,15 +229,16 @@ def test_dueling_targets_refuse_bad_arguments(cuda):
     o = tuple(x.t for x in out)
     r = (ring.obs, ring.nobs, ring.act, ring.rew, ring.done)
     for net, A, online in ((big, 16, big), (duel, 2, None), (plain, 2, plain)):
+        args = (online, net, H, A, *r, L, 0.9, True, 1, 0, *o[:4])
+        per = dict(tree=tree, beta=0.5, w=w.t, wmax=wmax.t)
         with pytest.raises(RuntimeError):
-            h.dqn_targets(online, net, H, A, *r, L, 0.9, True, 1, 0, *o[:4], True)
+            h.dqn_targets(*args, dueling=True)
         with pytest.raises(RuntimeError):
-            h.dqn_targets_nstep(online, net, H, A, *r, L, 0.9, True, 1, 0, 3, 2, *o, True)
+            h.dqn_targets(*args, n_step=3, newest=2, last=o[4], dueling=True)
         with pytest.raises(RuntimeError):
-            h.dqn_targets_per(online, net, H, A, *r, tree, L, 0.9, True, 0.5, 1, 0, *o[:4], w.t, wmax.t, True)
+            h.dqn_targets(*args, **per, dueling=True)
         with pytest.raises(RuntimeError):
-            h.dqn_targets_per_nstep(online, net, H, A, *r, tree, L, 0.9, True, 0.5, 1, 0, 3, 2, *o[:4], w.t, wmax.t,
-                                    o[4], True)
+            h.dqn_targets(*args, **per, n_step=3, newest=2, last=o[4], dueling=True)
     with pytest.raises(ValueError, match="15"):
         dqn_targets(big, big, H, 16, ring, L, 0.9, True, 1, 0, B, out=o[:4], dueling=True)
     with pytest.raises(ValueError, match="floats"):

@@ -246,25 +246,25 @@ def test_nstep_entry_points_refuse_bad_arguments(cuda):
         out = (Guarded((B, D)), Guarded((B,), torch.int32), Guarded((B,)), Guarded((B,), torch.int32),
                Guarded((B,), torch.int32))
         with pytest.raises(RuntimeError, match="code -[24]"):
-            h.dqn_targets_nstep(p, p, H, A, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, filled, 0.9, True, 1, 0,
-                                n, newest, *(o.t for o in out))
+            h.dqn_targets(p, p, H, A, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, filled, 0.9, True, 1, 0,
+                          *(o.t for o in out[:4]), n_step=n, newest=newest, last=out[4].t)
         with pytest.raises(ValueError):  # the wrapper says why before it launches
             dqn_targets(p, p, H, A, ring, filled, 0.9, True, 1, 0, B, out=tuple(o.t for o in out), n_step=n,
                         newest=newest)
         w, wmax = Guarded((B,)), Guarded((1,))
         with pytest.raises(RuntimeError, match="code -[24]"):
-            h.dqn_targets_per_nstep(p, p, H, A, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, pt.tree, filled, 0.9,
-                                    True, 0.5, 1, 0, n, newest, out[0].t, out[1].t, out[2].t, out[3].t, w.t, wmax.t,
-                                    out[4].t)
+            h.dqn_targets(p, p, H, A, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, filled, 0.9, True, 1, 0,
+                          *(o.t for o in out[:4]), tree=pt.tree, beta=0.5, w=w.t, wmax=wmax.t, n_step=n, newest=newest,
+                          last=out[4].t)
         torch.cuda.synchronize()
         assert _sentinels_only(out + (w, wmax)), (n, newest, filled)
     with pytest.raises(ValueError, match="newest"):
         dqn_targets(p, p, H, A, ring, 6 * N, 0.9, True, 1, 0, B, n_step=3)
-    # the sound calls, for contrast; n_step = 1 through the n-step entry point is the one-step launch
+    # the sound calls, for contrast; n_step = 1 with the walk's arguments is the one-step launch
     out = tuple(Guarded(s, d) for s, d in (((B, D), torch.float32), ((B,), torch.int32), ((B,), torch.float32),
                                            ((B,), torch.int32), ((B,), torch.int32)))
-    h.dqn_targets_nstep(p, p, H, A, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, 6 * N, 0.9, True, 1, 0, 1, 5,
-                        *(o.t for o in out))
+    h.dqn_targets(p, p, H, A, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, 6 * N, 0.9, True, 1, 0,
+                  *(o.t for o in out[:4]), n_step=1, newest=5, last=out[4].t)
     one = dqn_targets(p, p, H, A, ring, 6 * N, 0.9, True, 1, 0, B)
     torch.cuda.synchronize()
     for a, b in zip(one, out):
