@@ -39,6 +39,14 @@ with one job (the actor's, per rollout) and with three (per update) and of ``noi
 (``epoch_noisy_us`` / ``epoch_dueling_us``).  The line goes to ``profiles/dqn_noisy_bench.jsonl`` unless ``--out``
 names another file.  ``--noisy-learning EPOCHS`` instead records, for seeds 1..3 of both presets, the greedy mean
 return over 256 episodes every 100 epochs: one line per run in ``profiles/dqn_noisy_learning.jsonl``.
+
+``--quantiles NQ`` adds, from the same process, the quantile-regression head (QR-DQN, ``quantiles = NQ``) against the
+scalar one at the shapes of ``cartpole-dqn`` (``uniform``) and ``cartpole-dqn-nstep`` (``per_n3``; with ``NQ = 8`` it
+is the ``cartpole-dqn-quantile`` preset): ``epoch_<shape>_<scalar|quantile>_us`` and the microseconds per launch of
+``dqn_rollout``, ``dqn_targets`` and ``mlp_grad`` (``<kernel>_<shape>_<scalar|quantile>_us``).  The line goes to
+``profiles/dqn_quantile_bench.jsonl`` unless ``--out`` names another file.  ``--quantile-learning EPOCHS`` instead
+records, for seeds 1..3 of ``cartpole-dqn-nstep`` and ``cartpole-dqn-quantile``, the greedy mean return over 256
+episodes every 100 epochs: one line per run in ``profiles/dqn_quantile_learning.jsonl``.
 """
 import argparse
 import json
@@ -211,6 +219,90 @@ def dueling_records(a, dev, event_us):
     return rec
 
 
+def quantile_records(a, dev, event_us):
+    """The quantile head (``quantiles = a.quantiles``) against the scalar one in one process, at the shapes of
+    ``cartpole-dqn`` (uniform, one-step) and ``cartpole-dqn-nstep`` (prioritised, 3-step: with 8 quantiles it is the
+    ``cartpole-dqn-quantile`` preset): the epoch, and the three launches that stage the Q-network."""
+    from relayrl_prototype_amd.ops import dqn_rollout, dqn_targets, mlp_grad
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    assert PRESETS["cartpole-dqn-quantile"].overrides == dict(PRESETS["cartpole-dqn-nstep"].overrides, quantiles=8)
+    rec = dict(quantiles=a.quantiles)
+    for preset, tag in (("cartpole-dqn", "uniform"), ("cartpole-dqn-nstep", "per_n3")):
+        for NQ in (0, a.quantiles):
+            cfg = DQNConfig(**dict(PRESETS[preset].overrides, quantiles=NQ))
+            tr = DQNTrainer(cfg, device=dev)
+            for _ in range(a.warmup):
+                tr.train_epoch()
+            assert tr.updates > 0, "the warm-up must reach learning_starts"
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.epochs):
+                tr.train_epoch()
+            torch.cuda.synchronize()
+            key = f"{tag}_{'quantile' if NQ else 'scalar'}"
+            rec[f"epoch_{key}_us"] = round(1e6 * (time.perf_counter() - t0) / a.epochs, 2)
+            N, T, B, C = cfg.num_envs, cfg.rollout_len, cfg.batch_size, cfg.buffer_slots
+            filled = min(tr.slots_written, C) * N
+            qr = dict(quantiles=NQ) if NQ else {}
+            tkw = dict(qr)
+            gkw = dict(qr)
+            out = (tr.Xb, tr.act_b, tr.y, None)
+            if tr.per is not None:
+                tkw.update(tree=tr.per.tree, beta=0.7)
+                gkw.update(row_w=tr.w, w_norm=tr.wmax, td_abs=tr.td_abs)
+                out = (tr.Xb, tr.act_b, tr.y, tr.idx, tr.w, tr.wmax)
+            if cfg.n_step > 1:
+                tkw.update(n_step=cfg.n_step, newest=(tr.cursor - 1) % C)
+
+            def rollout():  # the same slot and step every time: timing only
+                dqn_rollout(tr.env_id, tr.q.params, cfg.hidden, T, 0, tr.ring, tr.state, tr.ep_len, tr.ep_ret,
+                            tr.ep_stats, seed=tr.env_seed, step0=0, epsilon=0.1, reset_all=False,
+                            max_steps=tr.max_steps, **qr)
+
+            def targets():
+                dqn_targets(tr.q.params, tr.target, cfg.hidden, tr.A, tr.ring, filled, cfg.gamma, cfg.double_q,
+                            tr.sample_seed, 7, B, out=out, **tkw)
+
+            def grad_q():
+                mlp_grad(tr.head, tr.q.params, tr.Xb, tr.A, cfg.hidden, act=tr.act_b, ret=tr.y,
+                         clip_eps=cfg.huber_delta, grad_slab=tr.slab, loss_slab=tr.loss, **gkw)
+
+            for name, fn in (("dqn_rollout", rollout), ("dqn_targets", targets), ("mlp_grad", grad_q)):
+                fn()
+                torch.cuda.synchronize()
+                med, lo, hi = event_us(fn, a.iters, a.reps)
+                rec[f"{name}_{key}_us"] = med
+                rec[f"{name}_{key}_us_range"] = [lo, hi]
+    return rec
+
+
+def quantile_learning(a, dev):
+    """Greedy mean return over 256 episodes every 100 epochs, seeds 1..3, ``cartpole-dqn-nstep`` and
+    ``cartpole-dqn-quantile``: one JSON line per run."""
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    lines = []
+    for preset in ("cartpole-dqn-nstep", "cartpole-dqn-quantile"):
+        for seed in (1, 2, 3):
+            cfg = DQNConfig(**dict(PRESETS[preset].overrides, seed=seed))
+            tr = DQNTrainer(cfg, device=dev)
+            curve = []
+            for epoch in range(1, a.quantile_learning + 1):
+                tr.train_epoch()
+                if epoch % 100 == 0:
+                    curve.append(round(tr.evaluate(episodes=1, num_envs=256).stats()["mean_return"], 1))
+            lines.append(json.dumps(dict(preset=preset, quantiles=cfg.quantiles, n_step=cfg.n_step, seed=seed,
+                                         eval_every=100, env_steps_per_epoch=cfg.num_envs * cfg.rollout_len,
+                                         greedy_mean_return_256=curve)))
+            print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def noisy_records(a, dev, event_us):
     """NoisyNet exploration in one process: the two new launches at the preset's net, and the epoch of
     ``cartpole-dqn-noisy`` against ``cartpole-dqn-dueling``."""
@@ -296,11 +388,20 @@ def main():
     ap.add_argument("--noisy", action="store_true", help="also measure NoisyNet exploration against cartpole-dqn-dueling")
     ap.add_argument("--noisy-learning", type=int, default=0, metavar="EPOCHS",
                     help="record greedy-return curves of cartpole-dqn-noisy and cartpole-dqn-dueling instead")
+    ap.add_argument("--quantiles", type=int, default=0, metavar="NQ",
+                    help="also measure the quantile head (QR-DQN) with NQ quantiles against the scalar one")
+    ap.add_argument("--quantile-learning", type=int, default=0, metavar="EPOCHS",
+                    help="record greedy-return curves of cartpole-dqn-quantile and cartpole-dqn-nstep instead")
     a = ap.parse_args()
+    if a.quantiles < 0 or 2 * a.quantiles > 16:
+        raise SystemExit("--quantiles takes 1 .. 8 (CartPole has 2 actions and the kernels hold 16 outputs)")
     if any(k < 1 for k in a.n_step):
         raise SystemExit("--n-step takes values >= 1")
-    if (a.prioritized or a.n_step or a.dueling or a.noisy or a.noisy_learning) and not a.out:
+    if (a.prioritized or a.n_step or a.dueling or a.noisy or a.noisy_learning or a.quantiles
+            or a.quantile_learning) and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "dqn_quantile_learning.jsonl" if a.quantile_learning else
+                             "dqn_quantile_bench.jsonl" if a.quantiles else
                              "dqn_noisy_learning.jsonl" if a.noisy_learning else
                              "dqn_noisy_bench.jsonl" if a.noisy else
                              "dqn_dueling_bench.jsonl" if a.dueling else
@@ -315,6 +416,8 @@ def main():
     torch.cuda.set_device(dev)
     if a.noisy_learning:
         return noisy_learning(a, dev)
+    if a.quantile_learning:
+        return quantile_learning(a, dev)
     cfg = DQNConfig(**PRESETS["cartpole-dqn"].overrides)
     tr = DQNTrainer(cfg, device=dev)
     for _ in range(a.warmup):
@@ -371,6 +474,8 @@ def main():
         rec.update(dueling_records(a, dev, event_us))
     if a.noisy:
         rec.update(noisy_records(a, dev, event_us))
+    if a.quantiles:
+        rec.update(quantile_records(a, dev, event_us))
     rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
     line = json.dumps(rec)
     print(line, flush=True)

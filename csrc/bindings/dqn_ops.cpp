@@ -40,18 +40,29 @@ int64_t dueling_outputs(int64_t A, bool dueling) {
   return A + (dueling ? 1 : 0);
 }
 
+// Outputs of a quantile Q-network over A actions, NQ per action (0: the scalar net, dueling or not).
+int64_t q_outputs(int64_t A, bool dueling, int64_t quantiles) {
+  TORCH_CHECK(quantiles >= 0, "quantiles must be >= 0, got ", quantiles);
+  TORCH_CHECK(quantiles == 0 || !dueling, "quantiles with dueling is not built: set one of the two");
+  TORCH_CHECK(A * quantiles <= 16, "a quantile net has A * quantiles <= 16 outputs, got ", A, " * ", quantiles);
+  return quantiles > 0 ? A * quantiles : dueling_outputs(A, dueling);
+}
+
 // Returns the kernel's code for a launch that would wrap (-4, nothing written); raises for anything else.
-int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
+int64_t dqn_rollout_qr(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
                     const Tensor& ep_len, const Tensor& ep_ret, const Tensor& obs, const Tensor& nobs,
                     const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& ep_stats, int64_t seed,
-                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling) {
+                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling,
+                    int64_t quantiles) {
   int D = 0, A = 0, NS = 0, ms = 0;
   TORCH_CHECK(rrl_env_dims((int)env, &D, &A, &NS, &ms) == 0, "unknown device env id ", env);
   TORCH_CHECK(env != ENV_HALFCHEETAH, "dqn_rollout takes the discrete device envs");
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(T >= 1 && max_steps >= 1, "T and max_steps must be >= 1");
-  const int64_t AO = dueling_outputs(A, dueling);
+  const int64_t AO = q_outputs(A, dueling, quantiles);
   check(params, "params", at::kFloat, (int64_t)H * D + H + H * H + H + AO * H + AO);
+  TORCH_CHECK(quantiles == 0 || params.numel() == (int64_t)H * D + H + H * H + H + AO * H + AO,
+              "params is not the quantile net MLPSpec(D, H, A * quantiles)");
   auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
   check(state, "state", at::kFloat, N * NS);
   check(ep_len, "ep_len", at::kInt, N);
@@ -63,10 +74,19 @@ int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int
                                  obs.data_ptr<float>(), nobs.data_ptr<float>(), act.data_ptr<int>(),
                                  rew.data_ptr<float>(), done.data_ptr<float>(), ep_stats.data_ptr<float>(),
                                  (uint64_t)seed, (uint64_t)step0, (float)epsilon, reset_all ? 1 : 0, (int)max_steps,
-                                 dueling ? 1 : 0, grid_cus(), cur_stream());
+                                 dueling ? 1 : 0, (int)quantiles, grid_cus(), cur_stream());
   if (rc == -4) return rc;
   check_rc(rc, "dqn_rollout");
   return 0;
+}
+
+// The scalar nets (plain or dueling): the binding as it always parsed.
+int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
+                    const Tensor& ep_len, const Tensor& ep_ret, const Tensor& obs, const Tensor& nobs,
+                    const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& ep_stats, int64_t seed,
+                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling) {
+  return dqn_rollout_qr(env, params, H, T, slot0, state, ep_len, ep_ret, obs, nobs, act, rew, done, ep_stats, seed,
+                        step0, epsilon, reset_all, max_steps, dueling, 0);
 }
 
 // ------------------------------------------------------------------ prioritised replay (per.hip)
@@ -113,17 +133,19 @@ void per_update(const Tensor& tree, const Tensor& pmax, int64_t L, const Tensor&
 // looked at without one), n_step > 1 the walk.  Without `newest` there is no walk to check and the slots are one
 // row each (N = 1, newest = 0); with it N is the ring's, and n_step, filled % N and newest are the entry point's
 // to refuse.
-void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
-                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
-                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
-                 const OptT& idx, const OptT& tree, std::optional<double> beta, const OptT& w, const OptT& wmax,
-                 int64_t n_step, std::optional<int64_t> newest, const OptT& last, bool dueling) {
+void dqn_targets_qr(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
+                    const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled,
+                    double gamma, bool double_q, int64_t sample_key, int64_t update, const Tensor& Xb,
+                    const Tensor& act_b, const Tensor& y, const OptT& idx, const OptT& tree,
+                    std::optional<double> beta, const OptT& w, const OptT& wmax, int64_t n_step,
+                    std::optional<int64_t> newest, const OptT& last, bool dueling, int64_t quantiles) {
   TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
   const int64_t D = obs.size(2);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  const int64_t AO = dueling_outputs(A, dueling);
+  const int64_t AO = q_outputs(A, dueling, quantiles);
+  const int64_t NQ = std::max<int64_t>(quantiles, 1);  // targets per batch row
   auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
   TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
   const int64_t P = H * D + H + H * H + H + AO * H + AO;
@@ -131,7 +153,8 @@ void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A,
   const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
   TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
   check(y, "y", at::kFloat);
-  const int64_t B = y.numel();
+  TORCH_CHECK(y.numel() % NQ == 0, "y must hold quantiles = ", NQ, " targets per batch row, has ", y.numel());
+  const int64_t B = y.numel() / NQ;
   TORCH_CHECK(B >= 1 && B * D < (int64_t)INT32_MAX, "batch size out of range");
   check(Xb, "Xb", at::kFloat, B * D);
   check(act_b, "act_b", at::kInt, B);
@@ -163,6 +186,7 @@ void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A,
   c.gamma = (float)gamma;
   c.double_q = double_q ? 1 : 0;
   c.dueling = dueling ? 1 : 0;
+  c.quantiles = (int)quantiles;
   c.sample_key = (uint64_t)sample_key;
   c.update = (uint64_t)update;
   c.Xb = Xb.data_ptr<float>();
@@ -174,6 +198,16 @@ void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A,
   c.newest = (int)nw;
   c.last = opt_ptr<int>(last, "last", at::kInt, B);
   check_rc(rrl_dqn_targets(&c, grid_cus(), cur_stream()), "dqn_targets");
+}
+
+// The scalar nets (plain or dueling): the binding as it always parsed.
+void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
+                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
+                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
+                 const OptT& idx, const OptT& tree, std::optional<double> beta, const OptT& w, const OptT& wmax,
+                 int64_t n_step, std::optional<int64_t> newest, const OptT& last, bool dueling) {
+  dqn_targets_qr(online, target, H, A, obs, nobs, act, rew, done, filled, gamma, double_q, sample_key, update, Xb,
+                 act_b, y, idx, tree, beta, w, wmax, n_step, newest, last, dueling, 0);
 }
 
 // ------------------------------------------------------------------ noisy layers (noisy.hip)
@@ -252,10 +286,21 @@ void register_dqn_ops(pybind11::module_& m) {
         py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"), py::arg("act"),
         py::arg("rew"), py::arg("done"), py::arg("ep_stats"), py::arg("seed"), py::arg("step0"), py::arg("epsilon"),
         py::arg("reset_all"), py::arg("max_steps"), py::arg("dueling") = false);
+  m.def("dqn_rollout_qr", &dqn_rollout_qr, py::arg("env"), py::arg("params"), py::arg("H"), py::arg("T"),
+        py::arg("slot0"), py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"),
+        py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("ep_stats"), py::arg("seed"), py::arg("step0"),
+        py::arg("epsilon"), py::arg("reset_all"), py::arg("max_steps"), py::arg("dueling") = false,
+        py::arg("quantiles") = 0);
   m.def("dqn_targets", &dqn_targets, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"), py::arg("obs"),
         py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"), py::arg("gamma"),
         py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"),
         py::arg("idx"), py::arg("tree") = py::none(), py::arg("beta") = py::none(), py::arg("w") = py::none(),
         py::arg("wmax") = py::none(), py::arg("n_step") = 1, py::arg("newest") = py::none(),
         py::arg("last") = py::none(), py::arg("dueling") = false);
+  m.def("dqn_targets_qr", &dqn_targets_qr, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
+        py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"),
+        py::arg("gamma"), py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"),
+        py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("tree") = py::none(), py::arg("beta") = py::none(),
+        py::arg("w") = py::none(), py::arg("wmax") = py::none(), py::arg("n_step") = 1, py::arg("newest") = py::none(),
+        py::arg("last") = py::none(), py::arg("dueling") = false, py::arg("quantiles") = 0);
 }

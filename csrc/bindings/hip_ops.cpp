@@ -150,6 +150,42 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   check_rc(rc, "mlp_grad");
 }
 
+// HEAD_Q_QR, the quantile-regression head (rrl_mlp_grad_qr): the net has A * quantiles outputs and ret is
+// [B][quantiles].  A binding of its own, so that mlp_grad above stays what it was.
+void mlp_grad_qr(const Tensor& params, const Tensor& X, int64_t A, int64_t quantiles, int64_t H, const Tensor& act,
+                 const Tensor& ret, double inv_B, double kappa, const Tensor& grad_slab, const Tensor& loss_slab,
+                 const OptT& nvalid, const OptT& inv_B_dev, const OptT& row_w, const OptT& w_norm, const OptT& td_abs) {
+  check(params, "params", at::kFloat);
+  check(X, "X", at::kFloat);
+  TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
+  const int64_t B = X.size(0), D = X.size(1), NQ = quantiles;
+  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
+  TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
+  TORCH_CHECK(A >= 1 && NQ >= 1 && A * NQ <= 16, "a quantile net has 1 <= A * quantiles <= 16 outputs, got ", A, " * ",
+              NQ);
+  TORCH_CHECK(kappa > 0.0, "the quantile head needs a Huber threshold > 0, got ", kappa);
+  TORCH_CHECK(B >= 1 && B * std::max<int64_t>(D, A * NQ) < (int64_t)INT32_MAX,
+              "batch out of range for 32-bit row indexing");
+  const int64_t P = flat_size(D, H, A * NQ, false);
+  TORCH_CHECK(params.numel() == P, "params has ", params.numel(), " floats; MLPSpec(D, H, A * quantiles) has ", P);
+  const int64_t nslab = mlp_grad_slabs(B);
+  check(grad_slab, "grad_slab", at::kFloat, nslab * P);
+  check(loss_slab, "loss_slab", at::kFloat, nslab * 8);
+  check(act, "act", at::kInt, B);
+  check(ret, "ret", at::kFloat, B * NQ);
+  const int* nv = opt_ptr<const int>(nvalid, "nvalid", at::kInt, 1);
+  const float* ibd = opt_ptr<const float>(inv_B_dev, "inv_B_dev", at::kFloat, 1);
+  const float* rw = opt_ptr<const float>(row_w, "row_w", at::kFloat, B);
+  const float* wn = opt_ptr<const float>(w_norm, "w_norm", at::kFloat, 1);
+  float* ta = opt_ptr<float>(td_abs, "td_abs", at::kFloat, B);
+  TORCH_CHECK((rw == nullptr) == (wn == nullptr), "row_w and w_norm come together");
+  check_rc(rrl_mlp_grad_qr(params.data_ptr<float>(), X.data_ptr<float>(), (int)B, (int)D, (int)A, (int)NQ, (int)H,
+                           act.data_ptr<int>(), ret.data_ptr<float>(), (float)inv_B, (float)kappa,
+                           grad_slab.data_ptr<float>(), loss_slab.data_ptr<float>(), (int)P, nv, ibd, rw, wn, ta,
+                           num_cus(), cur_stream()),
+           "mlp_grad_qr");
+}
+
 int64_t scan_tm_parts(int64_t N) { return rrl_scan_tm_parts((int)N); }
 
 void gae_scan_tm(const Tensor& rew, const Tensor& done, const OptT& val, const OptT& tval, const Tensor& adv,
@@ -442,9 +478,9 @@ EvalShape check_eval_bufs(int64_t D, const Tensor& ep_ret, const Tensor& ep_len,
 }
 
 // Fused policy evaluation (evaluate.hip): every env runs E complete episodes under fixed weights.
-void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
+void evaluate_qr(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
               const Tensor& ep_code, const OptT& tr_obs, const OptT& tr_act, const OptT& tr_rew, const OptT& tr_done,
-              int64_t seed, int64_t step0, bool greedy, int64_t max_steps, bool dueling) {
+              int64_t seed, int64_t step0, bool greedy, int64_t max_steps, bool dueling, int64_t quantiles) {
   auto [D, A, NS, ms] = env_dims(env);
   (void)NS;
   (void)ms;
@@ -452,7 +488,12 @@ void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(!dueling || greedy, "a dueling Q-network is evaluated greedily: softmax-of-Q is not its policy");
   TORCH_CHECK(!dueling || A <= 15, "a dueling net has A + 1 outputs: act dim must be in [1, 15], got ", A);
-  check_exact(params, "params", at::kFloat, flat_size(D, H, A + (dueling ? 1 : 0), false));
+  TORCH_CHECK(quantiles >= 0, "quantiles must be >= 0, got ", quantiles);
+  TORCH_CHECK(quantiles == 0 || greedy, "a quantile Q-network is evaluated greedily: softmax-of-Q is not its policy");
+  TORCH_CHECK(quantiles == 0 || !dueling, "quantiles with dueling is not built: set one of the two");
+  TORCH_CHECK(A * quantiles <= 16, "a quantile net has A * quantiles <= 16 outputs, got ", A, " * ", quantiles);
+  check_exact(params, "params", at::kFloat,
+              flat_size(D, H, quantiles > 0 ? A * quantiles : A + (dueling ? 1 : 0), false));
   const EvalShape sh = check_eval_bufs(D, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done, at::kInt, 0,
                                        max_steps);
   const bool tr = sh.Tc > 0;
@@ -460,9 +501,17 @@ void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret
                         ep_ret.data_ptr<float>(), ep_len.data_ptr<int>(), ep_code.data_ptr<int>(),
                         tr ? tr_obs->data_ptr<float>() : nullptr, tr ? tr_act->data_ptr<int>() : nullptr,
                         tr ? tr_rew->data_ptr<float>() : nullptr, tr ? tr_done->data_ptr<float>() : nullptr,
-                        (uint64_t)seed, (uint64_t)step0, greedy ? 1 : 0, (int)max_steps, dueling ? 1 : 0, num_cus(),
-                        cur_stream()),
+                        (uint64_t)seed, (uint64_t)step0, greedy ? 1 : 0, (int)max_steps, dueling ? 1 : 0,
+                        (int)quantiles, num_cus(), cur_stream()),
            "evaluate");
+}
+
+// The scalar nets (plain or dueling): the binding as it always parsed.
+void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
+              const Tensor& ep_code, const OptT& tr_obs, const OptT& tr_act, const OptT& tr_rew, const OptT& tr_done,
+              int64_t seed, int64_t step0, bool greedy, int64_t max_steps, bool dueling) {
+  evaluate_qr(env, params, H, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done, seed, step0, greedy, max_steps,
+              dueling, 0);
 }
 
 void evaluate_cont(int64_t env, const Tensor& params, const Tensor& env_consts, int64_t H, const Tensor& ep_ret,
@@ -514,6 +563,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_forward", &mlp_forward);
   m.def("mlp_grad_slabs", &mlp_grad_slabs);
   m.def("mlp_grad", &mlp_grad);
+  m.def("mlp_grad_qr", &mlp_grad_qr, pybind11::arg("params"), pybind11::arg("X"), pybind11::arg("A"),
+        pybind11::arg("quantiles"), pybind11::arg("H"), pybind11::arg("act"), pybind11::arg("ret"),
+        pybind11::arg("inv_B"), pybind11::arg("kappa"), pybind11::arg("grad_slab"), pybind11::arg("loss_slab"),
+        pybind11::arg("nvalid") = pybind11::none(), pybind11::arg("inv_B_dev") = pybind11::none(),
+        pybind11::arg("row_w") = pybind11::none(), pybind11::arg("w_norm") = pybind11::none(),
+        pybind11::arg("td_abs") = pybind11::none());
   m.def("set_value_grad_stamps", [](const Tensor& t) { rrl_set_value_grad_stamps(t.numel() ? t.data_ptr() : nullptr); });
   m.def("set_value_grad_tune", [](int64_t t) { return (int64_t)rrl_set_value_grad_tune((int)t); });
   m.def("set_value_grad_mode", [](int64_t mode) { return (int64_t)rrl_set_value_grad_mode((int)mode); },
@@ -554,6 +609,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"), pybind11::arg("seed"),
         pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"),
         pybind11::arg("dueling") = false);
+  m.def("evaluate_qr", &evaluate_qr, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("H"),
+        pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"), pybind11::arg("tr_obs"),
+        pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"), pybind11::arg("seed"),
+        pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"),
+        pybind11::arg("dueling") = false, pybind11::arg("quantiles") = 0);
   m.def("evaluate_cont", &evaluate_cont, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("env_consts"),
         pybind11::arg("H"), pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"),
         pybind11::arg("tr_obs"), pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"),
@@ -564,7 +624,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                        RRL_ENUM(MODE_LOGITS), RRL_ENUM(MODE_GAUSS_SAMPLE), RRL_ENUM(MODE_GAUSS_EVAL));
   m.attr("GRAD_HEADS") = pybind11::dict(RRL_ENUM(HEAD_PG_CAT), RRL_ENUM(HEAD_VALUE_MSE), RRL_ENUM(HEAD_PPO_CAT),
                                         RRL_ENUM(HEAD_PPO_GAUSS), RRL_ENUM(HEAD_PG_GAUSS), RRL_ENUM(HEAD_Q_TD),
-                                        RRL_ENUM(HEAD_Q_DUEL));
+                                        RRL_ENUM(HEAD_Q_DUEL), RRL_ENUM(HEAD_Q_QR));
   m.attr("ENV_IDS") = pybind11::dict(RRL_ENUM(ENV_CARTPOLE), RRL_ENUM(ENV_MOUNTAINCAR), RRL_ENUM(ENV_ACROBOT),
                                      RRL_ENUM(ENV_LUNARLANDER), RRL_ENUM(ENV_HALFCHEETAH));
 #undef RRL_ENUM

@@ -26,6 +26,7 @@ enum GradHead : int {
   HEAD_PG_GAUSS = 4,   // REINFORCE / A2C with a Gaussian policy
   HEAD_Q_TD = 5,       // DQN: loss = mean(huber(Q(x)[act] - ret, delta)); delta travels in clip_eps
   HEAD_Q_DUEL = 6,     // HEAD_Q_TD on a dueling net of A + 1 outputs: Q = out[A] + out[act] - mean(out[0 .. A-1])
+  HEAD_Q_QR = 7,       // QR-DQN: quantile-Huber loss on a net of A * NQ outputs (rrl_mlp_grad_qr has the contract)
 };
 
 enum EnvId : int { ENV_CARTPOLE = 0, ENV_MOUNTAINCAR = 1, ENV_ACROBOT = 2, ENV_LUNARLANDER = 3, ENV_HALFCHEETAH = 4 };
@@ -49,6 +50,7 @@ struct DqnTargetsCall {
   float *w, *wmax;               // [B], [1]
   int n_step, N, newest;         // walk: N envs per slot, newest the slot written last
   int* last;                     // [B], may be null; n_step, N, newest, last = 1, 1, 0, nullptr is "no walk"
+  int quantiles;                 // 0: the scalar forms above; NQ >= 1: nets MLPSpec(D, H, A * NQ) and y [B][NQ]
 };
 
 }  // namespace rrl
@@ -71,7 +73,7 @@ int rrl_set_value_fwd_mode(int mode);
 // those of A + 1 outputs (rows 0 .. A-1 the advantages, row A the state value), and in fp32
 //   s = out[0]; s += out[k] (k = 1 .. A-1, ascending);  m = s / A;  Q(a) = (out[A] - m) + out[a].
 // -2: A outside [1, 16] or D outside [1, 32]; -3: H not 64 / 128, or HEAD_Q_DUEL with A > 15; -4: the net
-// and the staging do not fit the LDS
+// and the staging do not fit the LDS; -1: HEAD_Q_QR, which has its own entry point below
 int rrl_mlp_grad(int head, const float* params, const float* X, int B, int D, int A, int H, const float* mask,
                  const int* act, const float* actc, const float* adv, const float* ret, const float* logp_old,
                  const float* adv_stats, float inv_B, float clip_eps, float ent_coef, float* grad_slab,
@@ -85,6 +87,22 @@ int rrl_mlp_grad_weighted(int head, const float* params, const float* X, int B, 
                           const float* logp_old, const float* adv_stats, float inv_B, float clip_eps, float ent_coef,
                           float* grad_slab, float* loss_slab, int P, const int* nvalid, const float* inv_B_dev,
                           const float* row_w, const float* w_norm, float* td_abs, int num_cu, void* stream);
+// HEAD_Q_QR, the quantile-regression head of QR-DQN (Dabney et al. 2018).  params / P / the slabs are those of
+// MLPSpec(D, H, A * NQ); output a * NQ + i is quantile i of action a at level tau_i = (2 i + 1) / (2 NQ).  For a
+// row with action act: theta_i = out[act * NQ + i], T_j = qtarget[row][j] ([B][NQ]), u_ij = T_j - theta_i and
+//   rho = (1 / NQ) sum_i sum_j |tau_i - [u_ij < 0]| * huber_kappa(u_ij) / kappa,
+//   dout[act * NQ + i] = inv_B * w * -(1 / NQ) sum_j |tau_i - [u_ij < 0]| * clamp(u_ij, -kappa, kappa) / kappa,
+// every other output 0, w = row_w[row] / *w_norm or 1.  Loss slab: [0] += w * rho, [4] += s_act / NQ (s_act the
+// ascending fp32 sum of the action's quantiles), [5] += 1.  td_abs[row] (may be null) = rho, the unweighted row
+// loss.  act[row] is clamped into [0, A) (it indexes the output registers): an out-of-range action of a valid row
+// trains action 0 or A - 1, where HEAD_Q_TD would give the row no gradient.  nvalid / inv_B_dev as rrl_mlp_grad.
+// Nothing is written on a refusal: -1 a null pointer, or row_w without w_norm; -2 B < 1, A < 1, NQ < 1,
+// A * NQ > 16, D outside [1, 32], kappa <= 0, or P not the net's; -3 H not 64 / 128; -4 the net and the staging do
+// not fit the LDS
+int rrl_mlp_grad_qr(const float* params, const float* X, int B, int D, int A, int NQ, int H, const int* act,
+                    const float* qtarget, float inv_B, float kappa, float* grad_slab, float* loss_slab, int P,
+                    const int* nvalid, const float* inv_B_dev, const float* row_w, const float* w_norm,
+                    float* td_abs, int num_cu, void* stream);
 // number of partial-gradient slabs (== grid size) rrl_mlp_grad uses
 int rrl_mlp_grad_slabs(int B, int num_cu);
 // 1 = bf16x6 weight-stationary kernels, 0 = fp32 MFMA; returns the previous mode (-1 queries)
@@ -150,10 +168,13 @@ int rrl_rollout_cont(int env, const float* params, const float* env_consts, int 
 // steps, all four pointers or none (then Tc may be 0).  -2: N, E, Tc or max_steps below 1, or
 // E * max_steps >= 2^31; -3: unsupported H or env.  dueling != 0 (rrl_evaluate only): params is a dueling
 // Q-network of A + 1 outputs (HEAD_Q_DUEL) and the greedy action is the lowest-index argmax of its A
-// advantage outputs; -3 with greedy == 0, which is not a policy of that net
+// advantage outputs; -3 with greedy == 0, which is not a policy of that net.  quantiles = NQ >= 1 (rrl_evaluate
+// only): params is a quantile Q-network of A * NQ outputs (HEAD_Q_QR) and the greedy action is the lowest-index
+// argmax of the per-action sums s_a = out[a * NQ]; s_a += out[a * NQ + i] (i ascending); -3 with greedy == 0,
+// with quantiles < 0, with dueling != 0 as well, or with A * NQ > 16
 int rrl_evaluate(int env, const float* params, int N, int E, int Tc, int H, float* ep_ret, int* ep_len,
                  int* ep_code, float* tr_obs, int* tr_act, float* tr_rew, float* tr_done, uint64_t seed,
-                 uint64_t step0, int greedy, int max_steps, int dueling, int num_cu, void* stream);
+                 uint64_t step0, int greedy, int max_steps, int dueling, int quantiles, int num_cu, void* stream);
 // continuous-action envs (ENV_HALFCHEETAH); tr_act is [Tc][N][A]
 int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int N, int E, int Tc, int H,
                       float* ep_ret, int* ep_len, int* ep_code, float* tr_obs, float* tr_act, float* tr_rew,
@@ -167,12 +188,15 @@ int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int
 // rrl_rollout, with ep_stats [rrl_dqn_rollout_grid()][8].  -1: a null pointer; -2: N, T, C or max_steps
 // below 1; -3: unsupported H or env; -4 (nothing written): a launch that would wrap, i.e. unless
 // C % T == 0, slot0 % T == 0 and slot0 + T <= C.  dueling != 0: params is a dueling Q-network of A + 1
-// outputs (HEAD_Q_DUEL) and the greedy action is the lowest-index argmax of its A advantage outputs
+// outputs (HEAD_Q_DUEL) and the greedy action is the lowest-index argmax of its A advantage outputs.
+// quantiles = NQ >= 1: params is a quantile Q-network of A * NQ outputs (HEAD_Q_QR) and the greedy action is the
+// lowest-index argmax of the per-action quantile sums; the draws, the ring and the statistics do not depend on
+// it.  -3 (nothing written) with quantiles < 0, with dueling != 0 as well, or with A * NQ > 16
 int rrl_dqn_rollout_grid(int N, int num_cu);
 int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, int slot0, float* state, int* ep_len,
                     float* ep_ret, float* obs, float* nobs, int* act, float* rew, float* done, float* ep_stats,
                     uint64_t seed, uint64_t step0, float epsilon, int reset_all, int max_steps, int dueling,
-                    int num_cu, void* stream);
+                    int quantiles, int num_cu, void* stream);
 // The TD targets of one update.  Batch row b samples ring row r0, gathers obs[r0] -> Xb[b], act[r0] -> act_b[b],
 // r0 -> idx[b], walks to the row `last` (last[b] <- last) and writes, a* being the lowest-index argmax of
 // Q_target(nobs[last], .) (double_q = 0) or of Q_online (double_q = 1),
@@ -187,7 +211,11 @@ int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, in
 //     last += N; if (last >= filled) last -= filled;  G = fma(disc, rew[last], G);  disc *= gamma;  ++m; }
 // n_step == 1 launches the one-step kernel, which has no walk, and then copies idx to last.  dueling != 0: the
 // nets have A + 1 outputs (HEAD_Q_DUEL has the combine), a* is the argmax of the selecting net's A advantages and
-// Q_target the target net's dueling Q; only y depends on it.  Refusals write nothing and are checked in this order.
+// Q_target the target net's dueling Q; only y depends on it.  quantiles = NQ >= 1: the nets have A * NQ outputs
+// (HEAD_Q_QR), a* is the argmax of the selecting net's per-action quantile sums, y is [B][NQ] and
+//   y[b][j] = G + disc * (done[last] == 1 ? 0 : 1) * theta_target(nobs[last])[a* * NQ + j]
+// (at n_step == 1: rew[r0] + gamma * ...); again only y depends on it.  -3 also for quantiles < 0, quantiles with
+// dueling, or A * NQ > 16.  Refusals write nothing and are checked in this order.
 // -1: a null pointer (online with double_q; idx, w, wmax with a tree; idx with last at n_step == 1); -2: B < 1,
 // filled outside [1, 2^31) or, with a tree, outside [1, L], L outside [1, 2^30]; -3: H not 64 / 128, D outside
 // [1, 16], A < 1 or A + dueling > 16; -2: n_step < 1, N < 1 or filled % N != 0; -4: newest outside [0, filled / N)

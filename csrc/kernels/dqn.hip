@@ -19,6 +19,10 @@
 // Both kernels have a DUEL instance for the dueling Q-network (heads.h: A + 1 outputs, Q = V + adv - mean adv):
 // it stages and evaluates A + 1 outputs, acts on the argmax of the A advantages and bootstraps from the
 // dueling Q.  The DUEL = false instances are the kernels as they were.
+//
+// Both also have a QR instance for the quantile-regression Q-network (heads.h: A * NQ outputs, action-major):
+// it stages and evaluates A * NQ outputs, acts on the argmax of the per-action quantile sums and writes NQ
+// targets per batch row.  NQ travels in an argument block of its own, so the QR = false instances keep theirs.
 #include <type_traits>
 
 #include "actor_step.h"
@@ -44,14 +48,22 @@ struct DqnRolloutArgs {
   int max_steps;
 };
 
+struct DqnRolloutQrArgs : DqnRolloutArgs {
+  int NQ = 1;  // quantiles per action, Env::A * NQ <= kMaxAct
+};
+
 // DUEL = true: the dueling Q-network (heads.h), Env::A + 1 outputs staged and evaluated; the greedy action
 // is the argmax of the A advantage outputs.  The draws, the ring writes and the episode slots do not change.
-template <class Env, int HT, bool DUEL = false>
-__global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(DqnRolloutArgs p) {
+// QR = true: the quantile Q-network, Env::A * p.NQ outputs; the greedy action is the argmax of the quantile sums.
+template <class Env, int HT, bool DUEL = false, bool QR = false>
+__global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(
+    std::conditional_t<QR, DqnRolloutQrArgs, DqnRolloutArgs> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = 1;
   constexpr int D = Env::D, A = Env::A;
-  constexpr int AO = A + (DUEL ? 1 : 0);  // outputs of the net
+  static_assert(!(DUEL && QR), "quantiles with the dueling head are not built");
+  int AO = A + (DUEL ? 1 : 0);  // outputs of the net
+  if constexpr (QR) AO = A * p.NQ;
   static_assert(D <= 16, "device envs use one input tile");
   static_assert(Env::A + 1 <= kMaxAct, "the dueling net has one output more than actions");
   const TileCtx c = tile_ctx(p);
@@ -74,7 +86,9 @@ __global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(DqnRolloutArgs p) {
       const uint4 rnd = step_draw(e.envc, gstep, c.key);
       const bool explore = u01(rnd.z) < p.epsilon;
       const int a_rand = min(A - 1, (int)floorf(u01(rnd.w) * (float)A));
-      const int a = explore ? a_rand : argmax_first(A, q);
+      int a;
+      if constexpr (QR) a = explore ? a_rand : quantile_argmax(A, p.NQ, q);
+      else a = explore ? a_rand : argmax_first(A, q);
 
       bool term;
       const float r = Env::step(e.s, a, term, u01(rnd.y));
@@ -151,6 +165,17 @@ struct DqnNStepArgs : DqnTargetArgs {
   uint32_t newest_row = 0;  // newest * N: the rows [newest_row, newest_row + N) end a walk
   int* last = nullptr;      // [B] or null: the row the target bootstrapped from
 };
+
+// The quantile instances (QR = true) add NQ to either block: y is [B][NQ].
+template <class Base>
+struct DqnQrArgs : Base {
+  int NQ = 1;
+};
+
+template <bool NSTEP, bool QR>
+using DqnTargetArgsOf = std::conditional_t<
+    QR, DqnQrArgs<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>,
+    std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>;
 
 RRL_DEV uint32_t dqn_sample_row(int b, const DqnTargetArgs& p) {
   const uint4 r = philox4x32(make_uint4((uint32_t)b, p.upd_lo, p.upd_hi, 0u), make_uint2(p.key_lo, p.key_hi));
@@ -235,14 +260,22 @@ RRL_DEV uint32_t dqn_nstep_last(uint32_t r0, uint32_t m1, const DqnNStepArgs& p)
 // DUEL = true: both nets are dueling (heads.h) with p.A + 1 outputs; a* is the argmax of the selecting
 // net's ADVANTAGES and the bootstrap is the dueling Q of the target net at a*.  What is parked between
 // the two passes does not change.
-template <int HT, bool PER, bool NSTEP = false, bool DUEL = false>
-__global__ __launch_bounds__(256, 1) void dqn_targets_kernel(
-    std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs> p) {
+// QR = true: both nets are quantile nets (heads.h) with p.A * p.NQ outputs and y is [B][NQ]; a* is the argmax of
+// the selecting net's quantile sums, parked in y[b * NQ], and row b receives the NQ quantiles of the target
+// net at a*, each through the expression of the scalar kernel.  Everything but y is that of QR = false.
+template <int HT, bool PER, bool NSTEP = false, bool DUEL = false, bool QR = false>
+__global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgsOf<NSTEP, QR> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  static_assert(!(DUEL && QR), "quantiles with the dueling head are not built");
   const int l = lane_id();
   const int j = l & 15, g = l >> 4;
   const int wave = threadIdx.x >> 6;
-  const int AO = p.A + (DUEL ? 1 : 0);  // outputs of the nets
+  int AO = p.A + (DUEL ? 1 : 0);  // outputs of the nets
+  int NQ = 1;                     // targets per batch row
+  if constexpr (QR) {
+    NQ = p.NQ;
+    AO = p.A * NQ;
+  }
 
   if (p.double_q) {
     stage_net<1, HT>(lds, p.online, p.D, AO, false);
@@ -264,7 +297,8 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(
         dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, AO, q);
       }
       if (ok && g == 0) {
-        p.y[b] = __int_as_float(argmax_first(p.A, q));
+        if constexpr (QR) p.y[(size_t)b * NQ] = __int_as_float(quantile_argmax(p.A, NQ, q));
+        else p.y[b] = __int_as_float(argmax_first(p.A, q));
         if (PER) p.idx[b] = (int)r;
       }
     }
@@ -301,16 +335,33 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(
     if (ok) {
       for (int f = g; f < p.D; f += 4) p.Xb[(size_t)b * p.D + f] = p.obs[r * p.D + f];
       if (g == 0) {
-        const int astar = p.double_q ? __float_as_int(p.y[b]) : argmax_first(p.A, q);
-        const float boot = (p.done[last] == 1.f) ? 0.f : 1.f;
-        float qstar;
-        if constexpr (DUEL) qstar = dueling_q(p.A, q, astar);
-        else qstar = pick_logit(p.A, q, astar);
-        if constexpr (NSTEP) {
-          p.y[b] = G + disc * boot * qstar;
-          if (p.last != nullptr) p.last[b] = (int)last;
+        if constexpr (QR) {
+          const float boot = (p.done[last] == 1.f) ? 0.f : 1.f;
+          // the parked a* comes back from memory: the clamp keeps the quantile index inside the 16 outputs
+          const int astar = p.double_q ? min(max(__float_as_int(p.y[(size_t)b * NQ]), 0), p.A - 1)
+                                       : quantile_argmax(p.A, NQ, q);
+          float rew0 = 0.f;
+          if constexpr (!NSTEP) rew0 = p.rew[r];
+          for (int i = 0; i < NQ; ++i) {
+            const float theta = pick_logit(AO, q, astar * NQ + i);
+            if constexpr (NSTEP) p.y[(size_t)b * NQ + i] = G + disc * boot * theta;
+            else p.y[(size_t)b * NQ + i] = rew0 + p.gamma * boot * theta;
+          }
+          if constexpr (NSTEP) {
+            if (p.last != nullptr) p.last[b] = (int)last;
+          }
         } else {
-          p.y[b] = p.rew[r] + p.gamma * boot * qstar;
+          const int astar = p.double_q ? __float_as_int(p.y[b]) : argmax_first(p.A, q);
+          const float boot = (p.done[last] == 1.f) ? 0.f : 1.f;
+          float qstar;
+          if constexpr (DUEL) qstar = dueling_q(p.A, q, astar);
+          else qstar = pick_logit(p.A, q, astar);
+          if constexpr (NSTEP) {
+            p.y[b] = G + disc * boot * qstar;
+            if (p.last != nullptr) p.last[b] = (int)last;
+          } else {
+            p.y[b] = p.rew[r] + p.gamma * boot * qstar;
+          }
         }
         p.act_b[b] = p.act[r];
         if (p.idx != nullptr) p.idx[b] = (int)r;
@@ -333,27 +384,36 @@ using namespace rrl;
 // 4 tiles per workgroup, one per wave; at most two workgroups per CU, beyond that the waves stride.
 extern "C" int rrl_dqn_rollout_grid(int N, int num_cu) { return tile_stride_grid(N, num_cu); }
 
-template <class Env, int HT, bool DUEL = false>
-static int launch_dqn_rollout(DqnRolloutArgs a, int slot0, int grid, hipStream_t s) {
+// QR = true: the block with NQ behind it, and the LDS image of Env::A * NQ outputs (-3 past kMaxAct of them).
+template <class Env, int HT, bool DUEL = false, bool QR = false>
+static int launch_dqn_rollout(std::conditional_t<QR, DqnRolloutQrArgs, DqnRolloutArgs> a, int slot0, int grid,
+                              hipStream_t s) {
   using L = LdsNet<1, HT>;
-  raise_lds_limit<dqn_rollout_kernel<Env, HT, DUEL>>();
+  int outputs = Env::A + (DUEL ? 1 : 0);
+  if constexpr (QR) {
+    if (a.NQ < 1 || Env::A * a.NQ > kMaxAct) return -3;
+    outputs = Env::A * a.NQ;
+  }
+  raise_lds_limit<dqn_rollout_kernel<Env, HT, DUEL, QR>>();
   const size_t off = (size_t)slot0 * a.N;
   a.obs += off * Env::D;
   a.nobs += off * Env::D;
   a.act += off;
   a.rew += off;
   a.done += off;
-  const size_t bytes = (size_t)L::floats(Env::A + (DUEL ? 1 : 0)) * sizeof(float);
-  hipLaunchKernelGGL((dqn_rollout_kernel<Env, HT, DUEL>), dim3(grid), dim3(256), bytes, s, a);
+  const size_t bytes = (size_t)L::floats(outputs) * sizeof(float);
+  hipLaunchKernelGGL((dqn_rollout_kernel<Env, HT, DUEL, QR>), dim3(grid), dim3(256), bytes, s, a);
   return (int)hipGetLastError();
 }
 
 extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, int slot0, float* state,
                                int* ep_len, float* ep_ret, float* obs, float* nobs, int* act, float* rew,
                                float* done, float* ep_stats, uint64_t seed, uint64_t step0, float epsilon,
-                               int reset_all, int max_steps, int dueling, int num_cu, void* stream) {
+                               int reset_all, int max_steps, int dueling, int quantiles, int num_cu,
+                               void* stream) {
   if (!params || !state || !ep_len || !ep_ret || !obs || !nobs || !act || !rew || !done || !ep_stats) return -1;
   if (N <= 0 || T <= 0 || C <= 0 || max_steps < 1) return -2;
+  if (quantiles < 0 || (quantiles > 0 && dueling)) return -3;
   if (slot0 < 0 || C % T != 0 || slot0 % T != 0 || (long long)slot0 + T > C) return -4;
   DqnRolloutArgs a{params, N, T, state, ep_len, ep_ret, obs, nobs, act, rew, done, ep_stats,
                    (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step0, (uint32_t)(step0 >> 32), epsilon,
@@ -361,6 +421,12 @@ extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H
   const int grid = rrl_dqn_rollout_grid(N, num_cu);
   return dispatch_env_h(env, H, [&](auto k) {
     using K = decltype(k);
+    if (quantiles > 0) {
+      DqnRolloutQrArgs aq;
+      static_cast<DqnRolloutArgs&>(aq) = a;
+      aq.NQ = quantiles;
+      return launch_dqn_rollout<typename K::Env, K::HT, false, true>(aq, slot0, grid, (hipStream_t)stream);
+    }
     if (dueling) return launch_dqn_rollout<typename K::Env, K::HT, true>(a, slot0, grid, (hipStream_t)stream);
     return launch_dqn_rollout<typename K::Env, K::HT>(a, slot0, grid, (hipStream_t)stream);
   });
@@ -401,6 +467,33 @@ static int dispatch_dqn_targets(const DqnNStepArgs& a, int H, bool per, bool nst
   }
 }
 
+// The quantile instances of (H, PER, NSTEP): the same blocks with NQ behind them.
+template <int HT, bool PER, bool NSTEP>
+static int launch_dqn_targets_qr(const DqnNStepArgs& a, int NQ, int grid, hipStream_t s) {
+  using L = LdsNet<1, HT>;
+  DqnTargetArgsOf<NSTEP, true> q;
+  static_cast<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>&>(q) = a;
+  q.NQ = NQ;
+  raise_lds_limit<dqn_targets_kernel<HT, PER, NSTEP, false, true>>();
+  const size_t bytes = (size_t)L::floats(a.A * NQ) * sizeof(float);
+  hipLaunchKernelGGL((dqn_targets_kernel<HT, PER, NSTEP, false, true>), dim3(grid), dim3(256), bytes, s, q);
+  return (int)hipGetLastError();
+}
+
+static int dispatch_dqn_targets_qr(const DqnNStepArgs& a, int NQ, int H, bool per, bool nstep, int grid,
+                                   hipStream_t s) {
+  switch ((per ? 4 : 0) | (nstep ? 2 : 0) | (H == 128 ? 1 : 0)) {
+    case 0: return launch_dqn_targets_qr<4, false, false>(a, NQ, grid, s);
+    case 1: return launch_dqn_targets_qr<8, false, false>(a, NQ, grid, s);
+    case 2: return launch_dqn_targets_qr<4, false, true>(a, NQ, grid, s);
+    case 3: return launch_dqn_targets_qr<8, false, true>(a, NQ, grid, s);
+    case 4: return launch_dqn_targets_qr<4, true, false>(a, NQ, grid, s);
+    case 5: return launch_dqn_targets_qr<8, true, false>(a, NQ, grid, s);
+    case 6: return launch_dqn_targets_qr<4, true, true>(a, NQ, grid, s);
+    default: return launch_dqn_targets_qr<8, true, true>(a, NQ, grid, s);
+  }
+}
+
 static int dqn_targets_grid(int B, int num_cu) {
   int grid = (B + 63) / 64;
   const int cap = num_cu > 0 ? num_cu : 256;
@@ -416,6 +509,8 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
   const long long P2 = per ? rrl_per_tree_leaves(c->L) : 1, most = per ? c->L : 0x7FFFFFFFll;
   if (P2 < 1 || c->filled < 1 || c->filled > most || c->B < 1) return -2;
   if ((c->H != 64 && c->H != 128) || c->D < 1 || c->D > 16 || c->A < 1 || c->A + (duel ? 1 : 0) > kMaxAct) return -3;
+  const int NQ = c->quantiles;
+  if (NQ < 0 || (NQ > 0 && duel) || (long long)c->A * NQ > kMaxAct) return -3;
   if (c->n_step < 1 || c->N < 1 || c->filled % c->N != 0) return -2;
   if (c->newest < 0 || c->newest >= c->filled / c->N) return -4;
   DqnNStepArgs a;
@@ -440,7 +535,9 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
     const hipError_t e = hipMemsetAsync(c->wmax, 0, sizeof(float), s);  // +0.0f: below every weight
     if (e != hipSuccess) return (int)e;
   }
-  const int rc = dispatch_dqn_targets(a, c->H, per, nstep, duel, dqn_targets_grid(c->B, num_cu), s);
+  const int grid = dqn_targets_grid(c->B, num_cu);
+  const int rc = NQ > 0 ? dispatch_dqn_targets_qr(a, NQ, c->H, per, nstep, grid, s)
+                        : dispatch_dqn_targets(a, c->H, per, nstep, duel, grid, s);
   if (rc || nstep || !c->last) return rc;
   // the one-step kernel has no walk: its target bootstraps from the sampled row itself
   return (int)hipMemcpyAsync(c->last, c->idx, (size_t)c->B * sizeof(int), hipMemcpyDeviceToDevice, s);

@@ -17,6 +17,8 @@
 //   * outputs are ep_ret / ep_len / ep_code [E][N] (the fp32 running sum ret += r, the length,
 //     1 terminal / 2 time limit) and, optionally, a trace of the first Tc steps in the rollout
 //     buffers' layout.  No reductions: statistics are torch reductions over the [E][N] tensors.
+#include <type_traits>
+
 #include "actor_step.h"
 
 namespace rrl {
@@ -38,6 +40,11 @@ struct EvalArgs {
   int max_steps;
 };
 
+// The quantile instance of evaluate_kernel (QR = true) takes NQ behind the block; the others keep theirs.
+struct EvalQrArgs : EvalArgs {
+  int NQ = 1;  // quantiles per action, Env::A * NQ <= kMaxAct
+};
+
 // One lane of an env that finished episode `ep` records it.
 template <class Env>
 RRL_DEV void store_episode(const EvalArgs& p, const EnvSlot<Env>& e, int ep, int code) {
@@ -49,12 +56,15 @@ RRL_DEV void store_episode(const EvalArgs& p, const EnvSlot<Env>& e, int ep, int
 
 // DUEL = true: a dueling Q-network (heads.h) of Env::A + 1 outputs, scored greedily: the action is the
 // argmax of the A advantage outputs.  The host refuses greedy = 0 for it.
-template <class Env, int HT, bool DUEL = false>
-__global__ __launch_bounds__(256, 2) void evaluate_kernel(EvalArgs p) {
+// QR = true: a quantile Q-network (heads.h) of Env::A * p.NQ outputs, scored greedily on the quantile sums.
+template <class Env, int HT, bool DUEL = false, bool QR = false>
+__global__ __launch_bounds__(256, 2) void evaluate_kernel(std::conditional_t<QR, EvalQrArgs, EvalArgs> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = 1;
   constexpr int D = Env::D, A = Env::A;
-  constexpr int AO = A + (DUEL ? 1 : 0);  // outputs of the net
+  static_assert(!(DUEL && QR), "quantiles with the dueling head are not built");
+  int AO = A + (DUEL ? 1 : 0);  // outputs of the net
+  if constexpr (QR) AO = A * p.NQ;
   static_assert(D <= 16, "device envs use one input tile");
   static_assert(Env::A + 1 <= kMaxAct, "the dueling net has one output more than actions");
   const TileCtx c = tile_ctx(p);
@@ -83,7 +93,9 @@ __global__ __launch_bounds__(256, 2) void evaluate_kernel(EvalArgs p) {
       policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), AO, logits);
       const uint4 rnd = step_draw(e.envc, gstep, c.key);
       int a;
-      if (DUEL || p.greedy) {
+      if constexpr (QR) {
+        a = quantile_argmax(A, p.NQ, logits);
+      } else if (DUEL || p.greedy) {
         a = argmax_first(A, logits);
       } else {
         const CatStats cs = cat_stats(A, logits);
@@ -203,14 +215,20 @@ int eval_args_bad(int N, int E, int Tc, int max_steps, const void* tr_obs, const
   return 0;
 }
 
-template <class Env, int HT, bool DUEL = false>
-int launch_evaluate(const EvalArgs& a, int num_cu, hipStream_t s) {
+// QR = true: the block with NQ behind it, and the LDS image of Env::A * NQ outputs (-3 past kMaxAct of them).
+template <class Env, int HT, bool DUEL = false, bool QR = false>
+int launch_evaluate(const std::conditional_t<QR, EvalQrArgs, EvalArgs>& a, int num_cu, hipStream_t s) {
   using L = LdsNet<1, HT>;
-  raise_lds_limit<evaluate_kernel<Env, HT, DUEL>>();
+  int outputs = Env::A + (DUEL ? 1 : 0);
+  if constexpr (QR) {
+    if (a.NQ < 1 || Env::A * a.NQ > kMaxAct) return -3;
+    outputs = Env::A * a.NQ;
+  }
+  raise_lds_limit<evaluate_kernel<Env, HT, DUEL, QR>>();
   int grid, block;
   eval_geometry(a.N, num_cu, &grid, &block);
-  const size_t bytes = (size_t)L::floats(Env::A + (DUEL ? 1 : 0)) * sizeof(float);
-  hipLaunchKernelGGL((evaluate_kernel<Env, HT, DUEL>), dim3(grid), dim3(block), bytes, s, a);
+  const size_t bytes = (size_t)L::floats(outputs) * sizeof(float);
+  hipLaunchKernelGGL((evaluate_kernel<Env, HT, DUEL, QR>), dim3(grid), dim3(block), bytes, s, a);
   return (int)hipGetLastError();
 }
 
@@ -230,14 +248,22 @@ int launch_evaluate_cont(const EvalArgs& a, int num_cu, hipStream_t s) {
 
 extern "C" int rrl_evaluate(int env, const float* params, int N, int E, int Tc, int H, float* ep_ret, int* ep_len,
                             int* ep_code, float* tr_obs, int* tr_act, float* tr_rew, float* tr_done, uint64_t seed,
-                            uint64_t step0, int greedy, int max_steps, int dueling, int num_cu, void* stream) {
+                            uint64_t step0, int greedy, int max_steps, int dueling, int quantiles, int num_cu,
+                            void* stream) {
   if (const int bad = eval_args_bad(N, E, Tc, max_steps, tr_obs, tr_act, tr_rew, tr_done)) return bad;
-  if (dueling && !greedy) return -3;  // softmax-of-Q is not a DQN policy
+  if ((dueling || quantiles) && !greedy) return -3;  // softmax-of-Q is not a DQN policy
+  if (quantiles < 0 || (quantiles > 0 && dueling)) return -3;
   EvalArgs a{params, nullptr, N, E, Tc, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done,
              (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step0, (uint32_t)(step0 >> 32), greedy ? 1 : 0,
              max_steps};
   return dispatch_env_h(env, H, [&](auto k) {
     using K = decltype(k);
+    if (quantiles > 0) {
+      EvalQrArgs aq;
+      static_cast<EvalArgs&>(aq) = a;
+      aq.NQ = quantiles;
+      return launch_evaluate<typename K::Env, K::HT, false, true>(aq, num_cu, (hipStream_t)stream);
+    }
     if (dueling) return launch_evaluate<typename K::Env, K::HT, true>(a, num_cu, (hipStream_t)stream);
     return launch_evaluate<typename K::Env, K::HT>(a, num_cu, (hipStream_t)stream);
   });

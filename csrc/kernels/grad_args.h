@@ -38,6 +38,14 @@ struct GradArgs {
   float* td_abs = nullptr;        // [B]
 };
 
+// Quantile regression (HEAD_Q_QR of mlp_grad.hip only): the net has A * NQ outputs, qtarget holds the NQ target
+// quantiles of every row, and td_abs receives the row's unweighted quantile-Huber loss.  A block of its own behind
+// GradArgs, so that every other instance keeps its block (and with it its code).
+struct GradQrArgs : GradArgs {
+  const float* qtarget = nullptr;  // [B][NQ]
+  int NQ = 1;
+};
+
 // Weight-stationary bf16x6 gradient kernels (value_grad.hip): value head for H = 128,
 // D <= 24; categorical policy heads (PG / PPO) for H = 128, D <= 8, A = 2..4; Gaussian
 // policy heads for H = 128, D <= 20, A = 1 or 6.

@@ -109,6 +109,39 @@ RRL_DEV float dueling_q(int A, const float (&out)[kMaxAct], int act) {
   return dueling_base(A, out) + pick_logit(A, out, act);
 }
 
+// Quantile-regression head (Dabney et al. 2018) over A * NQ outputs: out[a * NQ + i] is quantile i of action a
+// (action-major).  The greedy value of an action is the SUM of its quantiles, s = out[a * NQ]; s += out[a * NQ + i]
+// for i = 1 .. NQ-1 ascending, one add each, never divided (reference.quantile_q repeats the order); the
+// greedy action is argmax_first over the A sums.  NQ is a run-time value: the walk over the 16 registers is
+// unrolled and carries (action, quantile) counters, so `out` is never indexed by a variable.
+RRL_DEV int quantile_argmax(int A, int NQ, const float (&out)[kMaxAct]) {
+  int pick = 0, a = 0, i = 0;
+  float best = 0.f, s = 0.f;
+#pragma unroll
+  for (int k = 0; k < kMaxAct; ++k)
+    if (k < A * NQ) {
+      s = (i == 0) ? out[k] : s + out[k];
+      if (++i == NQ) {
+        if (a == 0 || s > best) {
+          best = s;
+          pick = a;
+        }
+        ++a;
+        i = 0;
+      }
+    }
+  return pick;
+}
+// The quantile sum of action act, in the same order.
+RRL_DEV float quantile_sum(int NQ, const float (&out)[kMaxAct], int act) {
+  const int lo = act * NQ;
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < kMaxAct; ++k)
+    if (k >= lo && k < lo + NQ) s = (k == lo) ? out[k] : s + out[k];
+  return s;
+}
+
 // Gaussian head: log N(x; mu, sigma) summed over dims.
 constexpr float kHalfLog2Pi = 0.91893853320467274f;
 

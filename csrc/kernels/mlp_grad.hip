@@ -18,6 +18,8 @@
 //
 // Each workgroup writes one partial-gradient slab (flat parameter order); the
 // reduce+Adam kernel (adam.hip) sums the slabs, so the result is deterministic.
+#include <type_traits>
+
 #include "api.h"
 #include "common.h"
 #include "heads.h"
@@ -26,6 +28,19 @@
 namespace rrl {
 
 constexpr int kStageLd = 68;  // [feature][64 batch + 4 pad]
+
+// The argument block of a head: the quantile head's carries qtarget and NQ behind GradArgs, every other head's is
+// GradArgs itself.
+template <int HEAD>
+using GradArgsOf = std::conditional_t<HEAD == HEAD_Q_QR, GradQrArgs, GradArgs>;
+
+// The outputs of the net a head trains: the dueling Q head has one more than actions (p.A), the state value, and
+// the quantile head NQ per action.
+template <int HEAD>
+__host__ __device__ inline int grad_outputs(const GradArgsOf<HEAD>& p) {
+  if constexpr (HEAD == HEAD_Q_QR) return p.A * p.NQ;
+  else return (HEAD == HEAD_VALUE_MSE) ? 1 : (HEAD == HEAD_Q_DUEL) ? p.A + 1 : p.A;
+}
 
 // acc[to][ti] += sum_b At[16*(to0+to)+i][b] * Bt[16*(ti0+ti)+i][b], b over the 64-row slab.
 // Operands of batch block bb+1 are loaded while block bb's MFMAs issue.
@@ -105,7 +120,7 @@ RRL_DEV void stage_x_tiles(float* __restrict__ St, int wave, const floatx4 (&v)[
 // the loss and in dq (row_w may be null: weight 1), and td_abs[i] (may be null) receives |diff| of
 // every valid row.  The unweighted instance reads none of the three pointers.
 template <int DT, int HT, int HEAD, int A3, int EARLY, bool WEIGHTED = false>
-__global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
+__global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgsOf<HEAD> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using L = LdsNet<DT, HT>;
   constexpr int H = L::H;
@@ -114,7 +129,9 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
   constexpr int TO = HT / 4;  // dW2 / dW1 output tiles per wave
   constexpr int TI3 = HT / 4; // dW3 input tiles per wave
   // A: the outputs of the net.  The dueling Q head has one more than actions (p.A), the state value
-  const int A = (HEAD == HEAD_VALUE_MSE) ? 1 : (HEAD == HEAD_Q_DUEL) ? p.A + 1 : p.A;
+  int outputs = (HEAD == HEAD_VALUE_MSE) ? 1 : (HEAD == HEAD_Q_DUEL) ? p.A + 1 : p.A;
+  if constexpr (HEAD == HEAD_Q_QR) outputs = p.A * p.NQ;  // and the quantile head NQ per action
+  const int A = outputs;
   const int net_floats = (L::floats(A) + 3) & ~3;
   float* st0 = lds + net_floats;        // [H][68]
   float* st1 = st0 + H * kStageLd;      // [H][68]
@@ -269,6 +286,49 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
         s_val += q;
         s_cnt += 1.f;
         if (WEIGHTED && p.td_abs != nullptr) p.td_abs[row] = ad;
+      }
+    } else if constexpr (HEAD == HEAD_Q_QR) {
+      // Quantile regression: out[act * NQ + i] = theta_i at level tau_i = (2 i + 1) / (2 NQ), targets T_j =
+      // qtarget[row][j], u = T_j - theta_i, kappa = clip_eps, and
+      //   rho = (1 / NQ) sum_i sum_j |tau_i - [u < 0]| huber_kappa(u) / kappa.
+      // j is the outer loop, so one T_j is live at a time; the inner loop is unrolled over the 16 output
+      // registers, of which the NQ of this row's action take part, and dout[k] itself accumulates
+      // sum_j |tau_i - [u < 0]| clamp(u, -kappa, kappa) before it is scaled.
+      float th[kMaxAct];
+      policy_logits<HT>(lds + L::W3, lds + L::B3, A, H, h2, th);
+      const int NQ = p.NQ;
+      const int act = valid ? min(max(p.act[row], 0), p.A - 1) : 0;
+      const int lo = act * NQ;
+      const float kappa = p.clip_eps;
+      const float half_step = 0.5f / (float)NQ;  // tau_i = (2 i + 1) * half_step
+      const float* trow = p.qtarget + (size_t)(valid ? row : 0) * NQ;
+      float rho = 0.f;
+      for (int jq = 0; jq < NQ; ++jq) {
+        const float T = valid ? trow[jq] : 0.f;
+#pragma unroll
+        for (int k = 0; k < kMaxAct; ++k) {
+          if (k < A && k >= lo && k < lo + NQ) {
+            const float tau = (float)(2 * (k - lo) + 1) * half_step;
+            const float u = valid ? T - th[k] : 0.f;
+            const float au = fabsf(u);
+            const float wq = u < 0.f ? 1.f - tau : tau;
+            dout[k] += wq * fminf(fmaxf(u, -kappa), kappa);
+            rho += wq * (au <= kappa ? 0.5f * u * u : kappa * (au - 0.5f * kappa));
+          }
+        }
+      }
+      const float norm = 1.f / ((float)NQ * kappa);
+      rho *= norm;
+      float wi = 1.f;
+      if (WEIGHTED && p.row_w != nullptr) wi = valid ? p.row_w[row] / *p.w_norm : 0.f;
+      const float scale = -(valid ? invB : 0.f) * wi * norm;  // d rho / d theta_i = -(1 / (NQ kappa)) sum_j ...
+#pragma unroll
+      for (int k = 0; k < kMaxAct; ++k) dout[k] *= scale;
+      if (count) {
+        s_loss += wi * rho;
+        s_val += quantile_sum(NQ, th, act) / (float)NQ;
+        s_cnt += 1.f;
+        if (WEIGHTED && p.td_abs != nullptr) p.td_abs[row] = rho;
       }
     } else {  // Gaussian heads
       float adv = valid ? p.adv[row] : 0.f;
@@ -483,9 +543,9 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgs p) {
 using namespace rrl;
 
 template <int DT, int HT, int HEAD, int A3, int EARLY, bool WEIGHTED = false>
-static int launch_grad_v(const GradArgs& a, int grid, hipStream_t s) {
+static int launch_grad_v(const GradArgsOf<HEAD>& a, int grid, hipStream_t s) {
   using L = LdsNet<DT, HT>;
-  const int A = (HEAD == HEAD_VALUE_MSE) ? 1 : (HEAD == HEAD_Q_DUEL) ? a.A + 1 : a.A;  // outputs, as the kernel
+  const int A = grad_outputs<HEAD>(a);  // as the kernel
   const size_t floats = (size_t)((L::floats(A) + 3) & ~3) + 2 * (size_t)L::H * kStageLd;
   const size_t bytes = floats * sizeof(float);
   if (bytes > 163840) return -4;
@@ -500,8 +560,9 @@ static int launch_grad_v(const GradArgs& a, int grid, hipStream_t s) {
 }
 
 template <int DT, int HT, int HEAD, int A3>
-static int launch_grad(const GradArgs& a, int grid, hipStream_t s) {
-  if constexpr (HEAD == HEAD_Q_TD || HEAD == HEAD_Q_DUEL) {  // prioritised replay: the weighted instance
+static int launch_grad(const GradArgsOf<HEAD>& a, int grid, hipStream_t s) {
+  // prioritised replay: the weighted instance
+  if constexpr (HEAD == HEAD_Q_TD || HEAD == HEAD_Q_DUEL || HEAD == HEAD_Q_QR) {
     if (a.row_w != nullptr || a.td_abs != nullptr) return launch_grad_v<DT, HT, HEAD, A3, 1, true>(a, grid, s);
   }
   return launch_grad_v<DT, HT, HEAD, A3, 1>(a, grid, s);
@@ -510,9 +571,13 @@ static int launch_grad(const GradArgs& a, int grid, hipStream_t s) {
 // Keyed on the outputs of the last layer: 1 or 2 take the VALU dW3 path, more the MFMA tile.  The
 // dueling head has a.A + 1 of them, so only a one-action net (2 outputs) takes the VALU path.
 template <int DT, int HT, int HEAD>
-static int dispatch_a3(const GradArgs& a, int grid, hipStream_t s) {
+static int dispatch_a3(const GradArgsOf<HEAD>& a, int grid, hipStream_t s) {
   if constexpr (HEAD == HEAD_Q_DUEL) {
     if (a.A == 1) return launch_grad<DT, HT, HEAD, 2>(a, grid, s);
+    return launch_grad<DT, HT, HEAD, 0>(a, grid, s);
+  } else if constexpr (HEAD == HEAD_Q_QR) {  // A * NQ outputs
+    if (a.A * a.NQ == 1) return launch_grad<DT, HT, HEAD, 1>(a, grid, s);
+    if (a.A * a.NQ == 2) return launch_grad<DT, HT, HEAD, 2>(a, grid, s);
     return launch_grad<DT, HT, HEAD, 0>(a, grid, s);
   } else {
     if (HEAD == HEAD_VALUE_MSE || a.A == 1) return launch_grad<DT, HT, HEAD, 1>(a, grid, s);
@@ -572,6 +637,7 @@ extern "C" int rrl_mlp_grad_weighted(int head, const float* params, const float*
                                      const int* nvalid, const float* inv_B_dev, const float* row_w,
                                      const float* w_norm, float* td_abs, int num_cu, void* stream) {
   if (A < 1 || A > kMaxAct || D < 1 || D > 32) return -2;
+  if (head == HEAD_Q_QR) return -1;  // the quantile head has its own entry point, rrl_mlp_grad_qr
   if (head == HEAD_Q_DUEL && A + 1 > kMaxAct) return -3;  // the net has A + 1 outputs
   if ((row_w == nullptr) != (w_norm == nullptr)) return -1;
   if ((row_w != nullptr || td_abs != nullptr) && head != HEAD_Q_TD && head != HEAD_Q_DUEL) return -1;
@@ -592,4 +658,31 @@ extern "C" int rrl_mlp_grad_weighted(int head, const float* params, const float*
   if (H == 128) return DT == 1 ? dispatch_head<1, 8>(head, a, grid, s) : dispatch_head<2, 8>(head, a, grid, s);
   if (H == 64) return DT == 1 ? dispatch_head<1, 4>(head, a, grid, s) : dispatch_head<2, 4>(head, a, grid, s);
   return -3;
+}
+
+extern "C" int rrl_mlp_grad_qr(const float* params, const float* X, int B, int D, int A, int NQ, int H, const int* act,
+                               const float* qtarget, float inv_B, float kappa, float* grad_slab, float* loss_slab,
+                               int P, const int* nvalid, const float* inv_B_dev, const float* row_w,
+                               const float* w_norm, float* td_abs, int num_cu, void* stream) {
+  if (!params || !X || !act || !qtarget || !grad_slab || !loss_slab) return -1;
+  if ((row_w == nullptr) != (w_norm == nullptr)) return -1;
+  if (B < 1 || A < 1 || NQ < 1 || (long long)A * NQ > kMaxAct || D < 1 || D > 32 || !(kappa > 0.f)) return -2;
+  if (H != 64 && H != 128) return -3;
+  const int AO = A * NQ;
+  if (P != H * D + H + H * H + H + AO * H + AO) return -2;  // not MLPSpec(D, H, A * NQ)
+  GradQrArgs a;
+  static_cast<GradArgs&>(a) = {params, X, B, D, A, nullptr, act, nullptr, nullptr, nullptr, nullptr, nullptr, inv_B,
+                               kappa, 0.f, grad_slab, loss_slab, P};
+  a.nvalid = nvalid;
+  a.inv_B_dev = inv_B_dev;
+  a.row_w = row_w;
+  a.w_norm = w_norm;
+  a.td_abs = td_abs;
+  a.qtarget = qtarget;
+  a.NQ = NQ;
+  const int grid = rrl_mlp_grad_slabs(B, num_cu);
+  hipStream_t s = (hipStream_t)stream;
+  const int DT = (D <= 16) ? 1 : 2;
+  if (H == 128) return DT == 1 ? dispatch_a3<1, 8, HEAD_Q_QR>(a, grid, s) : dispatch_a3<2, 8, HEAD_Q_QR>(a, grid, s);
+  return DT == 1 ? dispatch_a3<1, 4, HEAD_Q_QR>(a, grid, s) : dispatch_a3<2, 4, HEAD_Q_QR>(a, grid, s);
 }

@@ -59,6 +59,7 @@ from .mlp import (  # noqa: E402
     GradHead,
     mlp_forward,
     mlp_grad,
+    mlp_grad_qr,
     set_value_grad_mode,
     grad_slabs,
     adam_step,
@@ -127,6 +128,7 @@ __all__ = [
     "GradHead",
     "mlp_forward",
     "mlp_grad",
+    "mlp_grad_qr",
     "set_value_grad_mode",
     "grad_slabs",
     "adam_step",

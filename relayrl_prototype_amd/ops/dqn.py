@@ -42,13 +42,35 @@ def dqn_rollout_grid(num_envs: int) -> int:
     return int(hip().dqn_rollout_grid(int(num_envs)))
 
 
-def check_q_params(params, D: int, H: int, A: int, dueling: bool, name: str = "params"):
+def check_quantiles(A: int, quantiles, dueling: bool = False) -> int:
+    """``quantiles`` as the kernels take it -> NQ: 0 is the scalar net; NQ >= 1 a quantile net of ``A * NQ <= 16``
+    outputs, which the dueling head is not built for."""
+    NQ = int(quantiles)
+    if NQ < 0:
+        raise ValueError(f"quantiles must be >= 0, got {quantiles}")
+    if NQ > 0 and dueling:
+        raise ValueError("quantiles > 0 with dueling=True is not built: the two heads share 16 outputs and the "
+                         "combination needs its own design; set quantiles=0 or dueling=False")
+    if NQ > 0 and int(A) * NQ > 16:
+        raise ValueError(f"a quantile net has A * quantiles <= 16 outputs, got A = {A} and quantiles = {NQ}")
+    return NQ
+
+
+def check_q_params(params, D: int, H: int, A: int, dueling: bool, name: str = "params", quantiles: int = 0):
     """A Q-network over ``A`` actions is ``MLPSpec(D, H, A)``, a dueling one ``MLPSpec(D, H, A + 1)`` (at most
-    16 outputs, so ``A <= 15``): ``params`` must have exactly that many floats."""
+    16 outputs, so ``A <= 15``), a quantile one ``MLPSpec(D, H, A * quantiles)`` (``A * quantiles <= 16``):
+    ``params`` must have exactly that many floats."""
     from .mlp import MLPSpec
 
+    NQ = check_quantiles(A, quantiles, dueling) if quantiles else 0
     if dueling and not 1 <= int(A) <= 15:
         raise ValueError(f"a dueling net has A + 1 <= 16 outputs: A must be in [1, 15], got {A}")
+    if NQ > 0:
+        want = MLPSpec(int(D), int(H), int(A) * NQ).P
+        if params is not None and params.numel() != want:
+            raise ValueError(f"{name} has {params.numel()} floats; a quantile Q-network of D = {D}, H = {H}, A = {A}, "
+                             f"quantiles = {NQ} has {want}")
+        return
     want = MLPSpec(int(D), int(H), int(A) + (1 if dueling else 0)).P
     if params is not None and params.numel() != want:
         raise ValueError(f"{name} has {params.numel()} floats; a {'dueling' if dueling else 'plain'} Q-network of "
@@ -57,21 +79,29 @@ def check_q_params(params, D: int, H: int, A: int, dueling: bool, name: str = "p
 
 def dqn_rollout(env_id: int, params: torch.Tensor, hidden: int, rollout_len: int, slot0: int, ring: ReplayRing,
                 state, ep_len, ep_ret, ep_stats, *, seed: int, step0: int, epsilon: float, reset_all: bool,
-                max_steps: int, dueling: bool = False) -> int:
+                max_steps: int, dueling: bool = False, quantiles: int = 0) -> int:
     """T = ``rollout_len`` epsilon-greedy steps of every env into ring slots ``slot0 .. slot0 + T - 1``.
     Returns 0, or the kernel's negative code (nothing written) for a launch that would wrap: unless
     ``C % T == 0``, ``slot0 % T == 0`` and ``slot0 + T <= C``.  Asynchronous on the current stream.
 
     ``dueling``: ``params`` is a dueling net of ``A + 1`` outputs (``reference.dueling_q``); a greedy step
-    takes the lowest-index argmax of its ``A`` advantage outputs.  The draws and the ring do not change."""
+    takes the lowest-index argmax of its ``A`` advantage outputs.  The draws and the ring do not change.
+
+    ``quantiles`` = NQ >= 1: ``params`` is a quantile net of ``A * NQ`` outputs (``reference.quantile_q``); a greedy
+    step takes the lowest-index argmax of the per-action quantile sums.  Again the draws and the ring do not change."""
     from . import hip
 
     h = hip()  # raises NativeExtensionMissing: there is no fallback
     if not params.is_cuda:
         raise ValueError("dqn_rollout runs the HIP kernel only: params must be a GPU tensor")
-    if dueling:
+    if dueling or quantiles:
         D, A, _, _ = h.env_dims(int(env_id))
-        check_q_params(params, D, hidden, A, True)
+        check_q_params(params, D, hidden, A, bool(dueling), quantiles=quantiles)
+    if quantiles:  # the quantile nets have a binding of their own: the scalar one parses what it always parsed
+        return int(h.dqn_rollout_qr(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len,
+                                    ep_ret, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed),
+                                    int(step0), float(epsilon), bool(reset_all), int(max_steps), bool(dueling),
+                                    int(quantiles)))
     return int(h.dqn_rollout(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len, ep_ret,
                              ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed), int(step0),
                              float(epsilon), bool(reset_all), int(max_steps), bool(dueling)))
@@ -139,7 +169,7 @@ def dqn_nstep_walk_ref(rows, ring: ReplayRing, filled: int, newest: int, n_step:
 @torch.no_grad()
 def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: int, gamma: float, double_q: bool,
                     seed: int, update: int, B: int, dtype=torch.float32, tree=None, beta: Optional[float] = None,
-                    n_step: int = 1, newest: Optional[int] = None, dueling: bool = False):
+                    n_step: int = 1, newest: Optional[int] = None, dueling: bool = False, quantiles: int = 0):
     """-> ``(Xb [B, D], act_b [B] int32, y [B], idx [B] int64)`` in ``dtype``;
     ``y = rew + gamma * (done == 1 ? 0 : 1) * Q_target(nobs, a*)`` with ``a*`` the lowest-index argmax of the
     target (``double_q`` false) or online net.  With ``tree`` (the priority sum tree of ops/per.py) the rows
@@ -152,10 +182,15 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
     the end: ``last [B]`` int64, the row the target bootstrapped from.
 
     ``dueling``: both nets are dueling nets of ``A + 1`` outputs; ``a*`` is the lowest-index argmax of the
-    selecting net's advantages and ``Q_target`` is ``reference.dueling_q`` of the target net."""
+    selecting net's advantages and ``Q_target`` is ``reference.dueling_q`` of the target net.
+
+    ``quantiles`` = NQ >= 1: both nets are quantile nets of ``A * NQ`` outputs, ``a*`` is the lowest-index argmax of
+    the selecting net's quantile sums (``reference.quantile_q``), ``y`` is [B, NQ] and
+    ``y[b, j] = G + disc * boot * theta_target[a* * NQ + j]``.  Everything but ``y`` is that of the scalar call."""
     D = ring.obs.shape[-1]
     dev = ring.obs.device
-    _check_q_nets(online if double_q else None, target, D, H, A, dueling)
+    NQ = check_quantiles(A, quantiles, dueling)
+    _check_q_nets(online if double_q else None, target, D, H, A, dueling, NQ)
     n_step = int(n_step)
     if n_step != 1:
         check_nstep(n_step, newest, int(ring.act.shape[1]), int(filled))
@@ -173,22 +208,30 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
         last, G, disc = (torch.from_numpy(x).to(dev)
                          for x in dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)[:3])
     nobs = ring.nobs.reshape(-1, D)[last].to(dtype)
-    q_t, astar = _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype)
     boot = (ring.done.reshape(-1)[last] != 1).to(dtype)
-    y = G + disc * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
+    if NQ > 0:
+        out_t = ref.trunk(target.to(dtype), nobs, D, H, A * NQ)[0]
+        sel = ref.trunk(online.to(dtype), nobs, D, H, A * NQ)[0] if double_q else out_t
+        astar, _ = ref.greedy_from_logits(ref.quantile_q(sel, A, NQ))
+        theta = out_t.reshape(-1, A, NQ).gather(1, astar.reshape(-1, 1, 1).expand(-1, 1, NQ)).squeeze(1)
+        col = (lambda t: t.unsqueeze(-1)) if torch.is_tensor(disc) else (lambda t: t)
+        y = G.unsqueeze(-1) + col(disc) * boot.unsqueeze(-1) * theta
+    else:
+        q_t, astar = _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype)
+        y = G + disc * boot * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1)
     res = (ring.obs.reshape(-1, D)[idx], ring.act.reshape(-1)[idx].to(torch.int32), y, idx)
     if tree is not None:
         res += (w, w.max().reshape(1))
     return res if n_step == 1 else res + (last,)
 
 
-def _check_q_nets(online, target, D, H, A, dueling):
+def _check_q_nets(online, target, D, H, A, dueling, quantiles=0):
     """The sizes of the nets a targets call reads.  A hidden size the kernels do not have is the launch's to
     refuse (a GPU call), so it is not judged here."""
     if target.is_cuda and int(H) not in (64, 128):
         return
-    check_q_params(target, D, H, A, dueling, "target")
-    check_q_params(online, D, H, A, dueling, "online")
+    check_q_params(target, D, H, A, dueling, "target", quantiles)
+    check_q_params(online, D, H, A, dueling, "online", quantiles)
 
 
 def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
@@ -204,7 +247,7 @@ def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
 def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
                 gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32,
                 tree=None, beta: Optional[float] = None, n_step: int = 1, newest: Optional[int] = None,
-                dueling: bool = False):
+                dueling: bool = False, quantiles: int = 0):
     """Sample, gather and TD target in one launch -> ``(Xb, act_b, y, idx)``; ``out`` = the four tensors to
     write into (``idx`` int32 on the GPU, or None to skip it).  CPU tensors take the torch reference in
     ``dtype``; a GPU tensor without the extension raises.
@@ -220,12 +263,17 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
 
     ``dueling`` selects the dueling instances: ``A`` stays the action count, ``online`` / ``target`` are
     ``MLPSpec(D, H, A + 1)`` nets (``dqn_targets_ref`` has the semantics).  The sampled rows and every result
-    but ``y`` are those of the plain launch on the same ring."""
+    but ``y`` are those of the plain launch on the same ring.
+
+    ``quantiles`` = NQ >= 1 selects the quantile instances: ``online`` / ``target`` are ``MLPSpec(D, H, A * NQ)``
+    nets and ``y`` is [B, NQ] (``dqn_targets_ref`` has the semantics); again only ``y`` differs from the scalar
+    launch.  It is refused together with ``dueling``."""
     from . import use_hip, hip
 
     per = tree is not None
     dueling = bool(dueling)
-    _check_q_nets(online if double_q else None, target, ring.obs.shape[-1], H, A, dueling)
+    NQ = check_quantiles(A, quantiles, dueling) if quantiles else 0
+    _check_q_nets(online if double_q else None, target, ring.obs.shape[-1], H, A, dueling, NQ)
     if per and not (beta is not None and 0.0 < beta <= 1.0):
         raise ValueError(f"the prioritised form needs beta in (0, 1], got {beta}")
     n_step = int(n_step)
@@ -240,7 +288,7 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
         raise ValueError("at n_step = 1 last is idx: it cannot be written without idx")
     if not use_hip(target):
         res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
-                              n_step, newest, dueling)
+                              n_step, newest, dueling, NQ)
         if out is None:
             return res
         if n_step == 1:
@@ -252,18 +300,24 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
     dev = target.device
     if out is None:
         out = (torch.empty(B, ring.obs.shape[-1], device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+               torch.empty((B, NQ) if NQ else (B,), device=dev), torch.empty(B, dtype=torch.int32, device=dev))
         if per:
             out += (torch.empty(B, device=dev), torch.empty(1, device=dev))
         if n_step != 1:
             out += (torch.empty(B, dtype=torch.int32, device=dev),)
-    if out[2].numel() != B:
-        raise ValueError(f"y must hold {B} targets, got {out[2].numel()}")
+    if out[2].numel() != (B * NQ if NQ else B):
+        raise ValueError(f"y must hold {B * NQ if NQ else B} targets, got {out[2].numel()}")
     if per and out[3] is None:
         raise ValueError("the prioritised form writes idx: it cannot be skipped")
     w, wmax = out[4:6] if per else (None, None)
     # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling) in its order: a positional call
     # parses faster than a keyword one, and this is the one place that makes it
+    if NQ:  # the quantile nets have a binding of their own: the scalar one parses what it always parsed
+        hip().dqn_targets_qr(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act,
+                             ring.rew, ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update),
+                             *out[:4], tree, float(beta) if per else None, w, wmax, n_step, newest,
+                             out[base] if len(out) > base else None, dueling, NQ)
+        return out
     hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
                       ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), *out[:4], tree,
                       float(beta) if per else None, w, wmax, n_step, newest,

@@ -24,7 +24,7 @@ class EvalTrace(NamedTuple):
 def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes: int, num_envs: int, *,
                        greedy: bool = True, seed: int = 0, step0: int = 0, max_steps: Optional[int] = None,
                        env_consts: Optional[torch.Tensor] = None, trace_steps: int = 0, out=None,
-                       trace: Optional[EvalTrace] = None, dueling: bool = False):
+                       trace: Optional[EvalTrace] = None, dueling: bool = False, quantiles: int = 0):
     """-> ``(ep_ret, ep_len, ep_code, trace-or-None)``: float32 / int32 / int32 ``[episodes, num_envs]``
     (code 1 terminal, 2 time limit).  ``out`` = the three tensors to write into; ``trace`` = an
     ``EvalTrace`` to write into, or ``trace_steps`` > 0 to have one allocated (zero-filled).
@@ -32,7 +32,10 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     Asynchronous on the current stream, like the other ops.
 
     ``dueling`` (discrete envs, ``greedy`` only): ``params`` is a dueling Q-network of ``A + 1`` outputs and
-    the action is the lowest-index argmax of its ``A`` advantage outputs."""
+    the action is the lowest-index argmax of its ``A`` advantage outputs.
+
+    ``quantiles`` = NQ >= 1 (discrete envs, ``greedy`` only): ``params`` is a quantile Q-network of ``A * NQ``
+    outputs and the action is the lowest-index argmax of the per-action quantile sums."""
     from . import hip
 
     h = hip()  # raises NativeExtensionMissing: there is no fallback
@@ -49,7 +52,15 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
             raise ValueError("a dueling Q-network needs a discrete action space")
         if not greedy:
             raise ValueError("a dueling Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
-        check_q_params(params, D, hidden, A, True)
+        check_q_params(params, D, hidden, A, True, quantiles=quantiles)
+    elif quantiles:
+        from .dqn import check_q_params
+
+        if continuous:
+            raise ValueError("a quantile Q-network needs a discrete action space")
+        if not greedy:
+            raise ValueError("a quantile Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
+        check_q_params(params, D, hidden, A, False, quantiles=quantiles)
     E, N = int(episodes), int(num_envs)
     if E < 1 or N < 1:
         raise ValueError(f"episodes and num_envs must be >= 1, got {E} and {N}")
@@ -70,6 +81,8 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     args = (int(hidden), ep_ret, ep_len, ep_code, *tr, int(seed), int(step0), bool(greedy), max_steps)
     if continuous:
         h.evaluate_cont(int(env_id), params, env_consts, *args)
+    elif quantiles:  # the quantile nets have a binding of their own
+        h.evaluate_qr(int(env_id), params, *args, bool(dueling), int(quantiles))
     elif dueling:
         h.evaluate(int(env_id), params, *args, True)
     else:

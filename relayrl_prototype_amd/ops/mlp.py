@@ -33,6 +33,7 @@ class GradHead(IntEnum):
     PG_GAUSS = 4
     Q_TD = 5  # DQN: Huber loss on Q(x)[act] - ret; the threshold delta travels in clip_eps
     Q_DUEL = 6  # Q_TD on a dueling net of A + 1 outputs: Q = V + adv[act] - mean(adv) (reference.dueling_q)
+    Q_QR = 7  # QR-DQN: quantile-Huber loss on a net of A * quantiles outputs; ret is [B, quantiles]
 
 
 from ..models.mlp_spec import MLPSpec  # noqa: E402,F401 -- torch-free (CPU agents import it)
@@ -132,7 +133,7 @@ def set_value_grad_mode(mode: int) -> int:
 def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=None, adv=None, ret=None,
              logp_old=None, adv_stats=None, inv_B: Optional[float] = None, clip_eps: float = 0.2,
              ent_coef: float = 0.0, grad_slab=None, loss_slab=None, nvalid=None, inv_B_dev=None, row_w=None,
-             w_norm=None, td_abs=None):
+             w_norm=None, td_abs=None, quantiles: int = 0):
     """Fused forward+backward.  GPU: fills grad_slab [nslab, P] and loss_slab [nslab, 8] and
     returns them; CPU: returns (grad [1, P], loss stats [1, 8]) computed with autograd.
 
@@ -145,7 +146,15 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
     every valid row (rows past ``nvalid`` are left alone).
 
     ``Q_DUEL``: ``A`` stays the number of actions (at most 15); ``params`` and the gradient slab are those
-    of ``MLPSpec(D, H, A + 1)``."""
+    of ``MLPSpec(D, H, A + 1)``.
+
+    ``Q_QR`` with ``quantiles`` = NQ >= 1 is ``mlp_grad_qr`` below, which has the contract; the two come together."""
+    if quantiles or head == GradHead.Q_QR:
+        if int(head) != GradHead.Q_QR:
+            raise ValueError(f"quantiles ({quantiles}) goes with the Q_QR head")
+        return mlp_grad_qr(params, X, A, quantiles, H, act=act, ret=ret, inv_B=inv_B, kappa=clip_eps,
+                           grad_slab=grad_slab, loss_slab=loss_slab, nvalid=nvalid, inv_B_dev=inv_B_dev, row_w=row_w,
+                           w_norm=w_norm, td_abs=td_abs)
     X = X.contiguous().float()
     B = X.shape[0]
     if inv_B is None:
@@ -205,6 +214,59 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
                    rows(logp_old), adv_stats, float(inv_B), float(clip_eps), float(ent_coef), grad_slab[off:off + n],
                    loss_slab[off:off + n], nvalid, inv_B_dev, rows(_f32(row_w)), w_norm, rows(td_abs))
         off += n
+    return grad_slab[:ns], loss_slab[:ns]
+
+
+def mlp_grad_qr(params, X, A: int, quantiles: int, H: int, act=None, ret=None, inv_B: Optional[float] = None,
+                kappa: float = 1.0, grad_slab=None, loss_slab=None, nvalid=None, inv_B_dev=None, row_w=None, w_norm=None,
+                td_abs=None):
+    """The quantile-regression head of QR-DQN (``GradHead.Q_QR``, ``quantiles`` = NQ >= 1, ``A * NQ <= 16``), with
+    ``mlp_grad``'s results.  ``params`` and the slab are those of ``MLPSpec(D, H, A * NQ)`` (output ``a * NQ + i`` is
+    quantile ``i`` of action ``a``), ``ret`` is [B, NQ], ``kappa`` > 0 is the Huber threshold, ``row_w`` / ``w_norm`` /
+    ``nvalid`` / ``inv_B_dev`` apply as in ``mlp_grad`` and ``td_abs[i]`` receives the row's UNWEIGHTED quantile-Huber
+    loss (``reference.mlp_grad_ref`` has the formula).  CPU tensors take the reference."""
+    X = X.contiguous().float()
+    B, D = X.shape
+    NQ = int(quantiles)
+    if inv_B is None:
+        inv_B = 1.0 / max(B, 1)
+    if (row_w is None) != (w_norm is None):
+        raise ValueError("row_w and w_norm come together")
+    if NQ < 1:
+        raise ValueError(f"the Q_QR head needs quantiles >= 1, got {quantiles}")
+    if not 1 <= int(A) * NQ <= 16:
+        raise ValueError(f"a quantile net has A * quantiles <= 16 outputs, got {A} * {NQ}")
+    if not kappa > 0:
+        raise ValueError(f"the quantile head needs a Huber threshold (clip_eps / huber_delta) > 0, got {kappa}")
+    P = MLPSpec(D, H, int(A) * NQ).P
+    if params.numel() != P:
+        raise ValueError(f"params has {params.numel()} floats; a quantile Q-network of D = {D}, H = {H}, A = {A}, "
+                         f"quantiles = {NQ} has {P}")
+    if act is None or ret is None or ret.numel() != B * NQ:
+        raise ValueError(f"act [B] and ret [B, quantiles] = [{B}, {NQ}] targets are required")
+    ret = ret.reshape(B, NQ)
+    h = _hip_for(X)
+    if h is None:
+        n = B if nvalid is None else int(nvalid.reshape(-1)[0])
+        ib = inv_B if inv_B_dev is None else float(inv_B_dev.reshape(-1)[0])
+        g, st = ref.mlp_grad_ref(ref.HEAD_Q_QR, params, X[:n], A, H, act=act[:n], ret=ret[:n], inv_B=ib, clip_eps=kappa,
+                                 row_w=None if row_w is None else row_w[:n], w_norm=w_norm, quantiles=NQ)
+        if td_abs is not None:
+            td_abs[:n].copy_(st["td_abs"])
+        ls = torch.zeros(1, 8)
+        ls[0, 0], ls[0, 4], ls[0, 5] = st["loss"], st["v"], st["count"]
+        return g.view(1, -1), ls
+    if B > GRAD_CHUNK_ROWS:
+        raise ValueError(f"the quantile head takes a single-launch batch (<= {GRAD_CHUNK_ROWS} rows)")
+    if td_abs is not None and not (td_abs.is_contiguous() and td_abs.dtype == torch.float32):
+        raise ValueError("td_abs is written in place: it must be a contiguous float32 tensor")
+    ns = grad_slabs(B, X.device)
+    if grad_slab is None:
+        grad_slab = torch.empty(ns, P, device=X.device)
+    if loss_slab is None:
+        loss_slab = torch.empty(ns, 8, device=X.device)
+    h.mlp_grad_qr(params, X, int(A), NQ, int(H), _i32(act), _f32(ret), float(inv_B), float(kappa), grad_slab[:ns],
+                  loss_slab[:ns], nvalid, inv_B_dev, _f32(row_w), w_norm, td_abs)
     return grad_slab[:ns], loss_slab[:ns]
 
 

@@ -14,7 +14,7 @@ import torch
 from . import philox
 
 MODE_VALUE, MODE_CAT_SAMPLE, MODE_CAT_EVAL, MODE_LOGITS, MODE_GAUSS_SAMPLE, MODE_GAUSS_EVAL = range(6)
-HEAD_PG_CAT, HEAD_VALUE_MSE, HEAD_PPO_CAT, HEAD_PPO_GAUSS, HEAD_PG_GAUSS, HEAD_Q_TD, HEAD_Q_DUEL = range(7)
+HEAD_PG_CAT, HEAD_VALUE_MSE, HEAD_PPO_CAT, HEAD_PPO_GAUSS, HEAD_PG_GAUSS, HEAD_Q_TD, HEAD_Q_DUEL, HEAD_Q_QR = range(8)
 HALF_LOG_2PI = 0.91893853320467274
 
 
@@ -144,6 +144,25 @@ def dueling_q(out: torch.Tensor, A: int) -> torch.Tensor:
     return (out[..., A] - m).unsqueeze(-1) + out[..., :A]
 
 
+def quantile_q(out: torch.Tensor, A: int, NQ: int) -> torch.Tensor:
+    """The per-action quantile sums of ``out`` [..., A * NQ] (column ``a * NQ + i`` is quantile ``i`` of action
+    ``a``) -> s [..., A], in the kernels' operation order (rrl::quantile_argmax), in ``out``'s dtype:
+
+        s_a = out[a * NQ]; s_a += out[a * NQ + i] for i = 1 .. NQ-1 (ascending, one add each)
+
+    There is no division: the greedy action of a quantile net is the argmax of these sums, and the Q-value the
+    metrics report is ``s_a / NQ``."""
+    A, NQ = int(A), int(NQ)
+    if NQ < 1 or out.shape[-1] != A * NQ:
+        raise ValueError(f"a quantile net over {A} actions with {NQ} quantiles has {A * NQ} outputs, "
+                         f"got {out.shape[-1]}")
+    th = out.reshape(*out.shape[:-1], A, NQ)
+    s = th[..., 0]
+    for i in range(1, NQ):
+        s = s + th[..., i]
+    return s
+
+
 @torch.no_grad()
 def greedy_actions_ref(params, obs, A, H, dtype=torch.float64):
     """The greedy action of the categorical policy at ``obs`` [..., D] and the gap between its two
@@ -166,16 +185,27 @@ def normalize_adv(adv, adv_stats):
 
 def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None, ret=None, logp_old=None,
                  adv_stats=None, inv_B=None, clip_eps=0.2, ent_coef=0.0, dtype=torch.float32, row_w=None,
-                 w_norm=None):
+                 w_norm=None, quantiles=0):
     """Returns (flat gradient, stats dict) of sum_i loss_i * inv_B (+ entropy bonus);
     ``dtype=torch.float64`` gives the float64 oracle (tools/grad_fuzz_probe.py).
     ``HEAD_Q_TD``: loss_i = huber(Q(x_i)[act_i] - ret_i, delta) with delta = ``clip_eps``, times
     ``row_w[i] / w_norm`` where the weights of prioritised replay are given; ``stats["td_abs"]`` is
     |Q - ret| per row.  ``HEAD_Q_DUEL`` is the same loss on a dueling net: ``A`` stays the number of
-    actions, ``params`` has ``A + 1`` outputs and Q is ``dueling_q`` of them."""
+    actions, ``params`` has ``A + 1`` outputs and Q is ``dueling_q`` of them.
+    ``HEAD_Q_QR`` (``quantiles`` = NQ >= 1): ``params`` has ``A * NQ`` outputs, ``ret`` is [B, NQ] and with
+    theta_i = out[act * NQ + i], tau_i = (2 i + 1) / (2 NQ), u_ij = ret_j - theta_i, kappa = ``clip_eps`` > 0
+    loss_i = rho = (1 / NQ) sum_i sum_j |tau_i - [u_ij < 0]| huber_kappa(u_ij) / kappa, times the weight;
+    ``stats["td_abs"]`` is the UNWEIGHTED rho per row and ``stats["v"]`` sums ``quantile_q(out)[act] / NQ``."""
     B, D = X.shape
     gaussian = head in (HEAD_PPO_GAUSS, HEAD_PG_GAUSS)
-    Aeff = 1 if head == HEAD_VALUE_MSE else A + 1 if head == HEAD_Q_DUEL else A
+    NQ = int(quantiles)
+    if (head == HEAD_Q_QR) != (NQ > 0) or NQ < 0:
+        raise ValueError(f"quantiles ({NQ}) goes with HEAD_Q_QR, where it is >= 1")
+    if head == HEAD_Q_QR and not 1 <= int(A) * NQ <= 16:
+        raise ValueError(f"a quantile net has A * quantiles <= 16 outputs, got {A} * {NQ}")
+    if head == HEAD_Q_QR and not clip_eps > 0:
+        raise ValueError(f"the quantile head needs a Huber threshold (clip_eps / huber_delta) > 0, got {clip_eps}")
+    Aeff = 1 if head == HEAD_VALUE_MSE else A + 1 if head == HEAD_Q_DUEL else A * NQ if head == HEAD_Q_QR else A
     if inv_B is None:
         inv_B = 1.0 / max(B, 1)
     p = params.detach().to(dtype).clone().requires_grad_(True)
@@ -186,6 +216,20 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
         li = (v - ret) ** 2
         loss = li.sum() * inv_B
         stats.update(loss=li.sum().item(), v=v.sum().item(), count=B)
+    elif head == HEAD_Q_QR:
+        idx = act.long().reshape(B, 1, 1).expand(B, 1, NQ)
+        theta = out.reshape(B, A, NQ).gather(1, idx).squeeze(1)            # [B, NQ]
+        u = ret.to(dtype).reshape(B, 1, NQ) - theta.unsqueeze(-1)          # [B, i, j]
+        tau = ((2 * torch.arange(NQ, dtype=dtype, device=out.device) + 1) / (2 * NQ)).reshape(1, NQ, 1)
+        au = u.abs()
+        hub = torch.where(au <= clip_eps, 0.5 * u * u, clip_eps * (au - 0.5 * clip_eps))
+        rho = ((tau - (u.detach() < 0).to(dtype)).abs() * hub / clip_eps).sum((1, 2)) / NQ
+        li = rho
+        if row_w is not None:
+            li = (row_w.to(dtype) / torch.as_tensor(w_norm).to(dtype).reshape(-1)[0]) * rho
+        loss = li.sum() * inv_B
+        s_act = quantile_q(out, A, NQ).gather(-1, act.long().unsqueeze(-1)).squeeze(-1)
+        stats.update(loss=li.sum().item(), v=(s_act / NQ).sum().item(), count=B, td_abs=rho.detach())
     elif head in (HEAD_Q_TD, HEAD_Q_DUEL):
         qs = dueling_q(out, A) if head == HEAD_Q_DUEL else out
         q = qs.gather(-1, act.long().unsqueeze(-1)).squeeze(-1)

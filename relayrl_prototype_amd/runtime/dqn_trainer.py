@@ -51,8 +51,20 @@ it to 0), ``evaluate()`` scores ``mu``, and a checkpoint keeps ``mu`` where the 
 (``learner/pi``, ``learner/target``) and sigma with its Adam moments under ``noisy``.  ``noisy=False`` calls none of
 this and launches the kernels it always launched.
 
-Left for later: per-env noise, several ranks, hipGraph capture, serving the policy to agents (the trainer exposes no
-``learner``, so a TrainingServer engine publishes no model).
+``quantiles = NQ >= 1`` is the distributional head of QR-DQN (Dabney et al. 2018): the online and target nets are
+``MLPSpec(D, H, A * NQ)``, output ``a * NQ + i`` the quantile of action ``a`` at level ``(2 i + 1) / (2 NQ)``, and
+at most 16 outputs (CartPole: 8 quantiles, LunarLanderSynth: 4).  The actor and the evaluator act on the argmax of
+the per-action quantile SUMS (``reference.quantile_q``: ascending adds, no division), ``dqn_targets`` writes
+``y [B, NQ]``, the n-step target applied to each quantile of the target net at ``a*``, and the update is
+``mlp_grad_qr``, the quantile-Huber loss with kappa = ``huber_delta`` (> 0).  With ``prioritized`` the priority is
+the row's unweighted loss, as in Rainbow.  ``QVals`` is the mean of ``sum / NQ``.  It composes with ``double_q``,
+``prioritized``, ``n_step`` and ``noisy`` (which only sees ``A * NQ`` outputs); ``quantiles`` with ``dueling`` is
+refused: 16 outputs would leave CartPole 5 quantiles and the combination needs its own design.  ``quantiles = 0``
+launches the kernels it always launched, with the arguments it always passed.
+
+Left for later: quantiles with the dueling head, more than 16 outputs, per-env noise, several ranks, hipGraph
+capture, serving the policy to agents (the trainer exposes no ``learner``, so a TrainingServer engine publishes no
+model).
 """
 from __future__ import annotations
 
@@ -63,6 +75,7 @@ import torch
 
 from ..algorithms.core import FlatNet
 from ..ops import GradHead, MLPSpec, ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_targets, grad_slabs, hip, mlp_grad
+from ..ops import mlp_grad_qr
 from ..ops import PriorityTree, per_insert, per_update
 from ..ops import adam_step, noisy_compose, noisy_grad, noisy_sigma_init
 from ..parallel.comm import Comm
@@ -81,6 +94,7 @@ def _as_bool(name: str, value) -> bool:
 
 
 MAX_DUELING_ACTIONS = 15  # the kernels hold 16 outputs, and the dueling net has one more than actions
+MAX_Q_OUTPUTS = 16        # and the quantile net A * quantiles of them
 
 
 @dataclass
@@ -114,6 +128,7 @@ class DQNConfig:
     dueling: bool = False           # dueling head: A + 1 outputs, Q = V + A - mean A (needs A <= 15)
     noisy: bool = False             # NoisyNet exploration: W = mu + sigma * eps in all three layers
     noisy_sigma0: float = 0.5       # sigma starts at noisy_sigma0 / sqrt(fan_in)
+    quantiles: int = 0              # QR-DQN: quantiles per action, A * quantiles <= 16 outputs (0: scalar DQN)
 
     def __post_init__(self):
         self.dueling = _as_bool("dueling", self.dueling)
@@ -131,6 +146,21 @@ class DQNConfig:
         if isinstance(self.n_step, float) and n != self.n_step:
             raise ValueError(f"n_step must be an integer, got {self.n_step!r}")
         self.n_step = n
+        try:
+            nq = int(self.quantiles)
+        except (TypeError, ValueError):
+            raise ValueError(f"quantiles must be an integer, got {self.quantiles!r}") from None
+        if isinstance(self.quantiles, float) and nq != self.quantiles:
+            raise ValueError(f"quantiles must be an integer, got {self.quantiles!r}")
+        self.quantiles = nq
+        if not 0 <= self.quantiles <= MAX_Q_OUTPUTS:
+            raise ValueError(f"quantiles must be in [0, {MAX_Q_OUTPUTS}], got {self.quantiles}")
+        if self.quantiles > 0 and self.dueling:
+            raise ValueError("quantiles > 0 with dueling=True is not built: 16 outputs would leave CartPole 5 "
+                             "quantiles and the combination needs its own design; set quantiles=0 or dueling=False")
+        if self.quantiles > 0 and not float(self.huber_delta) > 0.0:
+            raise ValueError(f"quantiles needs huber_delta > 0 (the kappa of the quantile-Huber loss), got "
+                             f"{self.huber_delta}")
         if not 1 <= self.n_step <= int(self.buffer_slots):
             raise ValueError(f"n_step must be in [1, buffer_slots = {self.buffer_slots}], got {self.n_step}")
         self.prioritized = _as_bool("prioritized", self.prioritized)
@@ -200,12 +230,18 @@ class DQNTrainer:
         if cfg.dueling and A > MAX_DUELING_ACTIONS:
             raise ValueError(f"dueling needs A + 1 <= 16 outputs: {cfg.env!r} has {A} actions, at most "
                              f"{MAX_DUELING_ACTIONS} are supported")
+        NQ = self.NQ = int(cfg.quantiles)
+        if A * NQ > MAX_Q_OUTPUTS:
+            raise ValueError(f"quantiles needs A * quantiles <= {MAX_Q_OUTPUTS} outputs: {cfg.env!r} has {A} actions, "
+                             f"so at most {MAX_Q_OUTPUTS // A} quantiles; got {NQ}")
         # the online net: the seeded init of PGLearner's policy, with its fused-Adam state; the dueling net
-        # has one output more, the state value (row A)
+        # has one output more, the state value (row A); the quantile net NQ outputs per action
         g = torch.Generator().manual_seed(int(cfg.seed))
-        self.q = FlatNet(MLPSpec(D, H, A + 1 if cfg.dueling else A), cfg.q_lr, dev, g)
-        self.head = GradHead.Q_DUEL if cfg.dueling else GradHead.Q_TD
-        self._duel = dict(dueling=True) if cfg.dueling else {}  # a plain trainer passes what it always passed
+        self.q = FlatNet(MLPSpec(D, H, A * NQ if NQ else A + 1 if cfg.dueling else A), cfg.q_lr, dev, g)
+        self.head = GradHead.Q_QR if NQ else GradHead.Q_DUEL if cfg.dueling else GradHead.Q_TD
+        # what the head adds to the actor's, the evaluator's and the targets' calls; a plain trainer passes what it
+        # always passed.  The quantile head's gradient is an op of its own (_grad_qr)
+        self._head_kw = dict(quantiles=NQ) if NQ else dict(dueling=True) if cfg.dueling else {}
         self.target = self.q.params.clone()
         self.theta = None
         if cfg.noisy:  # theta = [mu; sigma] with Adam state of 2P; the net's own tensors are its mu half
@@ -226,7 +262,7 @@ class DQNTrainer:
         B = cfg.batch_size
         self.Xb = torch.zeros(B, D, device=dev)
         self.act_b = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.y = torch.zeros(B, device=dev)
+        self.y = torch.zeros((B, NQ) if NQ else (B,), device=dev)
         ns = grad_slabs(B, dev)
         self.slab = torch.zeros(ns, self.q.P, device=dev)
         self.loss = torch.zeros(ns, 8, device=dev)
@@ -261,7 +297,7 @@ class DQNTrainer:
         self.last_beta = beta_at(cfg, self.epoch)  # the exponent of this epoch's updates
         rc = dqn_rollout(self.env_id, self._actor_params(), cfg.hidden, T, self.cursor, self.ring, self.state,
                          self.ep_len, self.ep_ret, self.ep_stats, seed=self.env_seed, step0=self.epoch * T,
-                         epsilon=self.last_epsilon, reset_all=self._first, max_steps=self.max_steps, **self._duel)
+                         epsilon=self.last_epsilon, reset_all=self._first, max_steps=self.max_steps, **self._head_kw)
         if rc != 0:
             raise RuntimeError(f"dqn_rollout refused slot {self.cursor} of {cfg.buffer_slots} (code {rc})")
         if self.per is not None:  # the new transitions enter at the running maximum priority
@@ -301,6 +337,13 @@ class DQNTrainer:
                   beta1=q.betas[0], beta2=q.betas[1], eps=q.eps, weight_decay=q.weight_decay)
         q.version += 1
 
+    def _grad_qr(self, params):
+        """The quantile head's gradient slabs of one batch (``mlp_grad_qr``), with the weights of prioritised replay
+        where there are any."""
+        per = {} if self.per is None else dict(row_w=self.w, w_norm=self.wmax, td_abs=self.td_abs)
+        mlp_grad_qr(params, self.Xb, self.A, self.NQ, self.cfg.hidden, act=self.act_b, ret=self.y,
+                    kappa=self.cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, **per)
+
     def update(self):
         """One gradient step on a freshly sampled batch; the target network follows on its schedule."""
         cfg = self.cfg
@@ -311,17 +354,23 @@ class DQNTrainer:
         if self.per is None:
             dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None),
-                        **nstep, **self._duel)
-            mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
-                     clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
+                        **nstep, **self._head_kw)
+            if self.NQ:
+                self._grad_qr(params)
+            else:
+                mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                         clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
             self._apply()
         else:
             dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, tree=self.per.tree, beta=self.last_beta,
-                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep, **self._duel)
-            mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
-                     clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
-                     w_norm=self.wmax, td_abs=self.td_abs)
+                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep, **self._head_kw)
+            if self.NQ:
+                self._grad_qr(params)
+            else:
+                mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                         clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
+                         w_norm=self.wmax, td_abs=self.td_abs)
             self._apply()
             per_update(self.per, self.idx, self.td_abs, cfg.per_alpha, cfg.per_eps)
         self.updates += 1
@@ -353,7 +402,7 @@ class DQNTrainer:
         step0 = self.eval_step0
         ep_ret, ep_len, ep_code, _ = evaluate_policy_op(self.env_id, self.q.params, self.cfg.hidden, E, N, greedy=True,
                                                         seed=self.eval_seed, step0=step0, max_steps=self.max_steps,
-                                                        **self._duel)
+                                                        **self._head_kw)
         self.eval_step0 += E * self.max_steps
         return EvalResult(ep_ret, ep_len, ep_code, True, self.eval_seed, step0)
 
@@ -373,7 +422,7 @@ class DQNTrainer:
                 loss_q, q_vals = ls[0] / ls[5], ls[4] / ls[5]
         out.update(LossQ=loss_q, QVals=q_vals, Epsilon=self.last_epsilon, Updates=self.updates,
                    EnvSteps=self.env_steps, WorldSize=1, NStep=self.cfg.n_step, Dueling=bool(self.cfg.dueling),
-                   Noisy=bool(self.cfg.noisy))
+                   Noisy=bool(self.cfg.noisy), Quantiles=int(self.cfg.quantiles))
         if self.theta is not None:
             out.update(SigmaMeanAbs=float(self.theta[self.q.P:].abs().mean().item()))
         if self.per is not None:
@@ -429,9 +478,14 @@ class DQNTrainer:
     def load_state_dict(self, sd: dict):
         """Resume from ``state_dict()``.  The Philox keys derive from ``cfg.seed``: build the trainer with the
         checkpoint's config (the launcher does, from the preset and its overrides) for a bit-exact resume."""
+        got = int(sd["learner"]["pi"]["params"].numel())
+        mine, theirs = int(self.cfg.quantiles), int(sd.get("cfg", {}).get("quantiles", 0) or 0)  # absent: scalar
+        if mine != theirs:
+            raise ValueError(f"this trainer has quantiles={mine} ({self.q.P} parameters); the checkpoint has "
+                             f"quantiles={theirs} ({got} parameters): build the trainer with the checkpoint's "
+                             "quantiles setting")
         mine = bool(self.cfg.dueling)
         theirs = sd.get("cfg", {}).get("dueling")  # absent in a checkpoint from before the dueling head: plain
-        got = int(sd["learner"]["pi"]["params"].numel())
         if got != self.q.P or (theirs is not None and bool(theirs) != mine):
             raise ValueError(f"this trainer has dueling={mine} ({self.q.P} parameters); the checkpoint has "
                              f"dueling={bool(theirs)} ({got} parameters): build the trainer with the checkpoint's "

@@ -57,13 +57,16 @@ class EvalResult:
 
 def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, num_envs: int, greedy: bool = True,
                     seed: int = 0, step0: int = 0, max_episode_steps: Optional[int] = None, device=None,
-                    dueling: bool = False) -> EvalResult:
+                    dueling: bool = False, quantiles: int = 0) -> EvalResult:
     """Score the flat policy weights ``params`` on the device env ``env``: ``num_envs`` envs x
     ``episodes`` complete episodes each, greedy (argmax / mean action) or sampled like training.
     Env resets and env noise come from the Philox stream ``(seed, step0 + t)``.
 
     ``dueling``: ``params`` is a dueling Q-network (``A + 1`` outputs) of a discrete env, scored greedily on
-    its advantage outputs; ``greedy=False`` raises."""
+    its advantage outputs; ``greedy=False`` raises.
+
+    ``quantiles`` = NQ >= 1: ``params`` is a quantile Q-network (``A * NQ`` outputs) of a discrete env, scored
+    greedily on the per-action quantile sums; ``greedy=False`` and ``dueling`` raise."""
     from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
 
     if env not in DEVICE_ENVS:
@@ -72,6 +75,15 @@ def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, 
         raise ValueError(f"a dueling Q-network needs a discrete action space; {env!r} is continuous")
     if dueling and not greedy:
         raise ValueError("a dueling Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
+    quantiles = int(quantiles)
+    if quantiles < 0:
+        raise ValueError(f"quantiles must be >= 0, got {quantiles}")
+    if quantiles and dueling:
+        raise ValueError("quantiles > 0 with dueling=True is not built")
+    if quantiles and env in CONTINUOUS_DEVICE_ENVS:
+        raise ValueError(f"a quantile Q-network needs a discrete action space; {env!r} is continuous")
+    if quantiles and not greedy:
+        raise ValueError("a quantile Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
     if device is None:
         device = params.device if params.is_cuda else torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -83,7 +95,8 @@ def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, 
         consts = torch.tensor(_native.env_constants(env), dtype=torch.float32, device=device)
     ep_ret, ep_len, ep_code, _ = evaluate_policy_op(DEVICE_ENVS[env], p, hidden, episodes, num_envs, greedy=greedy,
                                                     seed=seed, step0=step0, max_steps=max_episode_steps,
-                                                    env_consts=consts, dueling=bool(dueling))
+                                                    env_consts=consts, dueling=bool(dueling),
+                                                    **(dict(quantiles=quantiles) if quantiles else {}))
     return EvalResult(ep_ret, ep_len, ep_code, greedy, seed, step0)
 
 

@@ -98,6 +98,15 @@ PRESETS: Dict[str, Preset] = {
                 "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
                 "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
                 "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "dueling": True}),
+    "cartpole-dqn-quantile": Preset(
+        "cartpole-dqn-quantile", "cartpole-dqn-nstep with the quantile-regression head of QR-DQN: the Q-network has "
+        "A * 8 outputs, 8 quantiles per action, greedy on their sums in the actor, per-quantile n-step targets and the "
+        "quantile-Huber Q head (--set quantiles=8 on any non-dueling DQN preset is the same mechanism)",
+        "vec", {"env": "CartPole-v1", "algo": "dqn", "num_envs": 1024, "rollout_len": 4, "buffer_slots": 256,
+                "batch_size": 1024, "updates_per_epoch": 4, "gamma": 0.99, "q_lr": 5e-4, "eps_start": 1.0,
+                "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
+                "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
+                "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "quantiles": 8}),
     "cartpole-dqn-noisy": Preset(
         "cartpole-dqn-noisy", "cartpole-dqn-dueling with NoisyNet exploration: W = mu + sigma * eps (factorised "
         "Gaussian noise) in all three layers, composed by one small kernel per rollout and per update, and no "
@@ -579,9 +588,10 @@ def evaluate_checkpoint_state(st, checkpoint: str = "<state>", episodes: int = 1
     if pixel:
         return _evaluate_pixel_checkpoint(st, tr, per_env, n, stochastic, seed, max_episode_steps)
     limit = max_episode_steps or cfg.get("max_episode_steps")
-    # a checkpoint from before the dueling head has no such key: a plain net
+    # a checkpoint from before the dueling head (the quantile head) has no such key: a plain (scalar) net
     res = evaluate_policy(cfg["env"], params, int(cfg["hidden"]), per_env, n, greedy=not stochastic, seed=seed,
-                          max_episode_steps=int(limit) if limit else None, dueling=bool(cfg.get("dueling", False)))
+                          max_episode_steps=int(limit) if limit else None, dueling=bool(cfg.get("dueling", False)),
+                          quantiles=int(cfg.get("quantiles", 0) or 0))
     out = res.to_dict()
     out.update(env=cfg["env"], hidden=int(cfg["hidden"]), num_envs=n, episodes_per_env=per_env,
                checkpoint_epoch=int(tr.get("epoch", st.get("epoch", 0))))
