@@ -59,6 +59,12 @@ constexpr int kVgH = 128;
 #ifndef VG_MT2
 #define VG_MT2 1
 #endif
+// 1: the head partials (and the relu'(h2) bits) of the 4 batch tiles are reduced over the lane
+// groups together, as a reduce-scatter (group_sum_scatter4, group_or_pair); 0: one
+// group_sum_swap / group_or_swap per value
+#ifndef VG_HEAD_RS
+#define VG_HEAD_RS 1
+#endif
 constexpr int kVgLd = 144;          // bf16 row stride of the activation images
 constexpr int kVgImg = 64 * kVgLd;  // elements per image piece
 // LDS: h1 + dh2 images (3 pieces each), head partials [8 waves][NA][64], x slabs [2][64][DP],
@@ -249,6 +255,32 @@ RRL_DEV uint32_t group_or_swap(uint32_t v) {
   const auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
   const uint32_t s = a[0] | a[1];
   const auto b = __builtin_amdgcn_permlane32_swap(s, s, false, false);
+  return b[0] | b[1];
+}
+
+// Reduce-scatter of four values over the 4 lane groups: lane group g gets the sum of v[g] over
+// the groups, (r0 + r1) + (r2 + r3) like group_sum_swap, for 3 swaps and 3 adds instead of 8
+// and 8 (and no copies: the swap's two operands are different values).  v_permlane16_swap
+// exchanges the odd 16-lane rows of its first operand with the even rows of its second, so
+//   (v0, v1) -> rows [v0.r0 v1.r0 v0.r2 v1.r2], [v0.r1 v1.r1 v0.r3 v1.r3];  their sum s is
+//   [v0.r01 v1.r01 v0.r23 v1.r23], t the same of (v2, v3); v_permlane32_swap exchanges rows 2, 3
+//   of its first operand with rows 0, 1 of its second: [s.r0 s.r1 t.r0 t.r1], [s.r2 s.r3 t.r2 t.r3].
+// Wave-uniform call sites only.
+RRL_DEV float group_sum_scatter4(float v0, float v1, float v2, float v3) {
+  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
+  const float s = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+  const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(v2), __float_as_uint(v3), false, false);
+  const float t = __uint_as_float(b[0]) + __uint_as_float(b[1]);
+  const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(t), false, false);
+  return __uint_as_float(c[0]) + __uint_as_float(c[1]);
+}
+
+// Bitwise OR over the 4 lane groups of two values at once: lane groups 0, 1 get x01's, groups
+// 2, 3 get x23's (2 swaps and 2 ORs for both).
+RRL_DEV uint32_t group_or_pair(uint32_t x01, uint32_t x23) {
+  const auto a = __builtin_amdgcn_permlane32_swap(x01, x23, false, false);  // [x01.r0 x01.r1 x23.r0 x23.r1], [.r2 .r3 ..]
+  const uint32_t c = a[0] | a[1];
+  const auto b = __builtin_amdgcn_permlane16_swap(c, c, false, false);
   return b[0] | b[1];
 }
 
@@ -932,9 +964,14 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
         if (bt < 2) x01 |= nib << sh;
         else x23 |= nib << sh;
       }
+#if VG_HEAD_RS
+      const uint32_t xg = group_or_pair(x01, x23);
+#else
       x01 = group_or_swap(x01);
       x23 = group_or_swap(x23);
-      const uint32_t u = ((g < 2 ? x01 : x23) >> (16 * (g & 1))) & 0xffffu;
+      const uint32_t xg = g < 2 ? x01 : x23;
+#endif
+      const uint32_t u = (xg >> (16 * (g & 1))) & 0xffffu;
       uint8_t* mb = reinterpret_cast<uint8_t*>(mk) + (16 * g + j) * 16 + 8 * (w & 1) + (w >> 1);
       mb[0] = (uint8_t)(u & 0xffu);
       mb[4] = (uint8_t)(u >> 8);
@@ -971,14 +1008,24 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
       const floatx4 w3a = *reinterpret_cast<const floatx4*>(w3p + a * kVgH);
+      float pv[4];
 #pragma unroll
       for (int bt = 0; bt < 4; ++bt) {
-        float pv = w3a[0] * h2[bt][0];
-        pv = fmaf(w3a[1], h2[bt][1], pv);
-        pv = fmaf(w3a[2], h2[bt][2], pv);
-        pv = fmaf(w3a[3], h2[bt][3], pv);
-        pv = group_sum_swap(pv);
-        if (g == bt) red[(w * NA + a) * 64 + 16 * bt + j] = pv;
+        pv[bt] = w3a[0] * h2[bt][0];
+        pv[bt] = fmaf(w3a[1], h2[bt][1], pv[bt]);
+        pv[bt] = fmaf(w3a[2], h2[bt][2], pv[bt]);
+        pv[bt] = fmaf(w3a[3], h2[bt][3], pv[bt]);
+      }
+      // batch tile bt's sum over the lane groups is stored by lane group g == bt only (the
+      // forward-only instance keeps the one-value form)
+      if constexpr (VG_HEAD_RS && !FWD) {
+        red[(w * NA + a) * 64 + l] = group_sum_scatter4(pv[0], pv[1], pv[2], pv[3]);
+      } else {
+#pragma unroll
+        for (int bt = 0; bt < 4; ++bt) {
+          const float sv = group_sum_swap(pv[bt]);
+          if (g == bt) red[(w * NA + a) * 64 + 16 * bt + j] = sv;
+        }
       }
       if (NA > 2) __builtin_amdgcn_sched_barrier(0);
     }

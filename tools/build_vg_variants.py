@@ -1,7 +1,10 @@
 """Build _hip_ops variants that differ only in how value_grad.hip is compiled (LLVM scheduler
-options), each as a self-contained package copy under build_variants/<name>/ with its own
-tools/kbench.py, so `python build_variants/<name>/tools/kbench.py grad` times that build.
-Run after the normal build (reuses build/hip/*.o for every other object)."""
+options, or the kernel's compile-time macros), each as a self-contained package copy under
+build_variants/<name>/ with its own tools/kbench.py and bench.py, so
+`python build_variants/<name>/tools/kbench.py grad` times that build.
+Run after the normal build (reuses build/hip/*.o for every other object).
+
+  python tools/build_vg_variants.py [--root DIR] [name ...]      # default: every variant"""
 import glob
 import os
 import shutil
@@ -17,6 +20,8 @@ VARIANTS = {
     "maxilp": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
     "trackers": ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"],
     "bias0": ["-mllvm", "-amdgpu-schedule-metric-bias=0"],
+    # the head partials one value at a time (the arrangement before the lane-group reduce-scatter)
+    "swap8": ["-DVG_HEAD_RS=0"],
 }
 
 
@@ -26,8 +31,13 @@ def main():
     others = [o for o in glob.glob(os.path.join(B.BUILD, "hip", "*.o")) if not o.endswith("value_grad.hip.o")]
     tinc, tcf, tld = B._torch_flags()
     so_name = os.path.basename(B.HIP_OPS)
-    for name, extra in VARIANTS.items():
-        root = os.path.join(REPO, "build_variants", name)
+    argv = sys.argv[1:]
+    out = os.path.join(REPO, "build_variants")
+    if argv[:1] == ["--root"]:
+        out, argv = os.path.abspath(argv[1]), argv[2:]
+    for name in argv or list(VARIANTS):
+        extra = VARIANTS[name]
+        root = os.path.join(out, name)
         pkg = os.path.join(root, "relayrl_prototype_amd")
         if os.path.exists(root):
             shutil.rmtree(root)
@@ -35,6 +45,7 @@ def main():
                         ignore=shutil.ignore_patterns("__pycache__", "_hip_ops*.so"))
         os.makedirs(os.path.join(root, "tools"))
         shutil.copy(os.path.join(REPO, "tools", "kbench.py"), os.path.join(root, "tools", "kbench.py"))
+        shutil.copy(os.path.join(REPO, "bench.py"), os.path.join(root, "bench.py"))
         obj = os.path.join(root, "value_grad.hip.o")
         cmd = [B.HIPCC, f"--offload-arch={B.ARCH}", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
                *B.HIP_FLAGS, *extra, "-I", kdir, "-c", src, "-o", obj]
