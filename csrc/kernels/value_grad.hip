@@ -65,6 +65,21 @@ constexpr int kVgH = 128;
 #ifndef VG_HEAD_RS
 #define VG_HEAD_RS 1
 #endif
+// A/B switches of the head -> dh1 hand-off (tools/build_vg_variants.py builds each one off):
+// 1: dh1's relu'(h2) mask words and its first two table fragments are read right after the head
+// barrier, with the head partials; 0: after the dout table's fence
+#ifndef VG_EARLY_MASK
+#define VG_EARLY_MASK 1
+#endif
+// 1: unsigned row / column indices in the value head's x prefetch and x store
+#ifndef VG_UIDX
+#define VG_UIDX 1
+#endif
+// 1: dW2's A-fragment lane masks of a row pair from shift, and, 24-bit multiply; 0: two
+// bit-field extracts and two ANDs
+#ifndef VG_AFRAG_MUL
+#define VG_AFRAG_MUL 1
+#endif
 constexpr int kVgLd = 144;          // bf16 row stride of the activation images
 constexpr int kVgImg = 64 * kVgLd;  // elements per image piece
 // LDS: h1 + dh2 images (3 pieces each), head partials [8 waves][NA][64], x slabs [2][64][DP],
@@ -596,8 +611,14 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
     asm volatile("" : "+v"(tid));
 #pragma unroll
     for (int i = 0; i < (kDmaIn ? 1 : XQ); ++i) {
+#if VG_UIDX
+      // (unsigned: q / DP and q % DP are a shift and a mask, not signed-division sequences)
+      const unsigned q = min((unsigned)tid + 512u * i, 64u * DP - 1u);
+      const int rl = (int)(q / (unsigned)DP), d = (int)(q % (unsigned)DP), b = b0 + rl;
+#else
       const int q = min(tid + 512 * i, 64 * DP - 1);
       const int rl = q / DP, d = q % DP, b = b0 + rl;
+#endif
       xr[i] = p.X[(size_t)min(b, Bc - 1) * D + min(d, D - 1)];
     }
   };
@@ -606,9 +627,15 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
     asm volatile("" : "+v"(tid));
 #pragma unroll
     for (int i = 0; i < (kDmaIn ? 1 : XQ); ++i) {
+#if VG_UIDX
+      const unsigned q = (unsigned)tid + 512u * i;
+      const int rl = (int)(q / (unsigned)DP), d = (int)(q % (unsigned)DP);
+      if (q < 64u * DP) dst[q] = (b0 + rl < Bv && d < D) ? xr[i] : 0.f;
+#else
       const int q = tid + 512 * i;
       const int rl = q / DP, d = q % DP;
       if (q < 64 * DP) dst[q] = (b0 + rl < Bv && d < D) ? xr[i] : 0.f;
+#endif
     }
   };
   constexpr bool kHb2 = kDmaIn && vg_hbuf2(DP, HEAD, NA);
@@ -955,6 +982,8 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
       // + 0 / 1).  The 4 lane groups' nibbles of rows 16 bt + j are OR-ed together, then lane
       // group g writes the 16 bits of row 16 g + j.
       uint32_t x01 = 0, x23 = 0;
+      // (shifting each bit in as x = x + x + (h2 > 0) did not become an add-with-carry: the
+      // compiler rewrites it as selects, ORs and shifts, 48 instructions for these 44)
 #pragma unroll
       for (int bt = 0; bt < 4; ++bt) {
         uint32_t nib = 0;
@@ -1048,6 +1077,19 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
     // loss head: lane l handles batch row l (every wave computes the same 64 rows; wave 0's
     // lanes count each row once in the batch statistics and the head gradient sums)
     const bool lead = w == 0;
+    // kMaskB: dh1's relu'(h2) mask words (a row's 4 bytes are one dword) and its first two table
+    // fragments.  The head barrier published the mask and dh1's MFMAs need nothing of dout (it
+    // enters afterwards, as the row scale), so these reads go out here with the partials'
+    // instead of two LDS round trips behind the dout chain and the dout table's fence.
+    constexpr bool kEarlyMask = VG_EARLY_MASK && VG_MT2 && kMaskB;
+    uint32_t mrow[kMaskB ? 4 : 1];
+    vbf16x8 mq0, mq1;
+    if constexpr (kEarlyMask) {
+#pragma unroll
+      for (int bt = 0; bt < 4; ++bt) mrow[bt % (kMaskB ? 4 : 1)] = mk[(16 * bt + j) * 4 + g];
+      mq0 = mtab[mrow[0] & 0xffu];
+      mq1 = mtab[mrow[kMaskB ? 1 : 0] & 0xffu];
+    }
     float dout[NA];
     float dls_row[kGauss ? NA : 1];  // this row's dLoss/dlog_std terms (Gaussian heads)
     if constexpr (kSplitHead) {
@@ -1125,6 +1167,14 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
         const float* r = red + a * 64 + l;
         constexpr int S = NA * 64;  // wave stride
         outv[a] = (((r[0] + r[S]) + (r[2 * S] + r[3 * S])) + ((r[4 * S] + r[5 * S]) + (r[6 * S] + r[7 * S]))) + hsc[a];
+      }
+      if constexpr (kEarlyMask && kValue) {
+        // issue order behind the barrier: the mask words' two reads and the partials' four go out
+        // together; the two table addresses and their reads follow while the partials are in
+        // flight (left alone the scheduler waited for the mask words before reading the partials)
+        __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
       }
       if (kValue) {
         const float v = outv[0];
@@ -1324,15 +1374,23 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
         if (kMaskB) {
           // dh1^T = dout * (mask x A'^T), exact: the mask fragment of (k-chunk c, batch tile
           // bt) is the table entry of byte (row 16 bt + j, g, c); a row's 4 bytes are one dword
-          uint32_t mrow[4];
+          // (kEarlyMask: the words and the first two fragments were read right after the head barrier)
+          if constexpr (!kEarlyMask) {
 #pragma unroll
-          for (int bt = 0; bt < 4; ++bt) mrow[bt] = mk[(16 * bt + j) * 4 + g];
+            for (int bt = 0; bt < 4; ++bt) mrow[bt % (kMaskB ? 4 : 1)] = mk[(16 * bt + j) * 4 + g];
+          }
           // table fragments read two steps ahead (VG_MT2): one step of 3 MFMAs did not cover
           // the LDS latency (an lgkmcnt(0) wait before every step)
           constexpr int kAhead = VG_MT2 ? 2 : 1;
-          auto mfrag = [&](int it) { return mtab[(mrow[it & 3] >> (8 * (it >> 2))) & 0xffu]; };
-          vbf16x8 q0 = mfrag(0), q1;
-          if (kAhead == 2) q1 = mfrag(1);
+          auto mfrag = [&](int it) { return mtab[(mrow[(it & 3) % (kMaskB ? 4 : 1)] >> (8 * (it >> 2))) & 0xffu]; };
+          vbf16x8 q0, q1;
+          if constexpr (kEarlyMask) {
+            q0 = mq0;
+            q1 = mq1;
+          } else {
+            q0 = mfrag(0);
+            if (kAhead == 2) q1 = mfrag(1);
+          }
 #pragma unroll
           for (int it = 0; it < 16; ++it) {
             const int c = it >> 2, bt = it & 3;
@@ -1598,9 +1656,15 @@ __global__ __launch_bounds__(512, 1) void value_grad_split_kernel(GradArgs p) {
       vu32x4 m;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
+#if VG_AFRAG_MUL
+        // both rows of the dword at once: bit j of each 16-bit half to the half's bit 0, then
+        // x 0xffff spreads each over its half (shift, and, 24-bit multiply for a row pair)
+        m[k] = ((mb[k] >> j) & 0x00010001u) * 0xffffu;
+#else
         const uint32_t lo = (uint32_t)__builtin_amdgcn_sbfe((int)mb[k], (uint32_t)j, 1u);
         const uint32_t hi = (uint32_t)__builtin_amdgcn_sbfe((int)mb[k], (uint32_t)(j + 16), 1u);
         m[k] = (lo & 0x0000ffffu) | (hi & 0xffff0000u);
+#endif
       }
       Split8 a;
       a.h = __builtin_bit_cast(vbf16x8, m & *reinterpret_cast<const vu32x4*>(tp));

@@ -22,6 +22,11 @@ VARIANTS = {
     "bias0": ["-mllvm", "-amdgpu-schedule-metric-bias=0"],
     # the head partials one value at a time (the arrangement before the lane-group reduce-scatter)
     "swap8": ["-DVG_HEAD_RS=0"],
+    # the head -> dh1 hand-off, one item off at a time: mask words and first table fragments read after the dout table's fence; signed x indices;
+    # the longer A-fragment lane-mask sequence
+    "late_mask": ["-DVG_EARLY_MASK=0"],
+    "sidx": ["-DVG_UIDX=0"],
+    "afrag_bfe": ["-DVG_AFRAG_MUL=0"],
 }
 
 
