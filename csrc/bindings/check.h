@@ -46,4 +46,20 @@ inline void check_rc(int rc, const char* what, const char* negative = "bad argum
               ")");
 }
 
+// Outputs of a Q-network over A actions, and whether the combination is one the kernels have: A for the plain net,
+// A + 1 (the state value) for the dueling one, A * quantiles for the quantile one (quantiles = 0: a scalar net),
+// never both, and kMaxAct = 16 outputs are what the kernels hold.
+inline int64_t q_outputs(int64_t A, bool dueling, int64_t quantiles) {
+  TORCH_CHECK(quantiles >= 0, "quantiles must be >= 0, got ", quantiles);
+  TORCH_CHECK(quantiles == 0 || !dueling, "quantiles with dueling is not built: set one of the two");
+  TORCH_CHECK(A * quantiles <= 16, "a quantile net has A * quantiles <= 16 outputs, got ", A, " * ", quantiles);
+  TORCH_CHECK(!dueling || A <= 15, "a dueling net has A + 1 outputs: act dim must be in [1, 15], got ", A);
+  return quantiles > 0 ? A * quantiles : A + (dueling ? 1 : 0);
+}
+
+// Floats of MLPSpec(D, H, A) (+ log_std).
+inline int64_t flat_size(int64_t D, int64_t H, int64_t A, bool log_std = false) {
+  return H * D + H + H * H + H + A * H + A + (log_std ? A : 0);
+}
+
 }  // namespace rrl_bind

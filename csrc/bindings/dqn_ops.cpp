@@ -33,36 +33,19 @@ std::tuple<int64_t, int64_t> check_ring(int64_t D, const Tensor& obs, const Tens
   return {C, N};
 }
 
-// Outputs of a Q-network over A actions: the dueling net has one more, the state value, and kMaxAct = 16
-// outputs are what the kernels hold.
-int64_t dueling_outputs(int64_t A, bool dueling) {
-  TORCH_CHECK(!dueling || A <= 15, "a dueling net has A + 1 outputs: act dim must be in [1, 15], got ", A);
-  return A + (dueling ? 1 : 0);
-}
-
-// Outputs of a quantile Q-network over A actions, NQ per action (0: the scalar net, dueling or not).
-int64_t q_outputs(int64_t A, bool dueling, int64_t quantiles) {
-  TORCH_CHECK(quantiles >= 0, "quantiles must be >= 0, got ", quantiles);
-  TORCH_CHECK(quantiles == 0 || !dueling, "quantiles with dueling is not built: set one of the two");
-  TORCH_CHECK(A * quantiles <= 16, "a quantile net has A * quantiles <= 16 outputs, got ", A, " * ", quantiles);
-  return quantiles > 0 ? A * quantiles : dueling_outputs(A, dueling);
-}
-
 // Returns the kernel's code for a launch that would wrap (-4, nothing written); raises for anything else.
-int64_t dqn_rollout_qr(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
+int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
                     const Tensor& ep_len, const Tensor& ep_ret, const Tensor& obs, const Tensor& nobs,
                     const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& ep_stats, int64_t seed,
-                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling,
-                    int64_t quantiles) {
+                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling, int64_t quantiles) {
   int D = 0, A = 0, NS = 0, ms = 0;
   TORCH_CHECK(rrl_env_dims((int)env, &D, &A, &NS, &ms) == 0, "unknown device env id ", env);
   TORCH_CHECK(env != ENV_HALFCHEETAH, "dqn_rollout takes the discrete device envs");
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(T >= 1 && max_steps >= 1, "T and max_steps must be >= 1");
-  const int64_t AO = q_outputs(A, dueling, quantiles);
-  check(params, "params", at::kFloat, (int64_t)H * D + H + H * H + H + AO * H + AO);
-  TORCH_CHECK(quantiles == 0 || params.numel() == (int64_t)H * D + H + H * H + H + AO * H + AO,
-              "params is not the quantile net MLPSpec(D, H, A * quantiles)");
+  const int64_t P = flat_size(D, H, q_outputs(A, dueling, quantiles));
+  check(params, "params", at::kFloat, P);
+  TORCH_CHECK(quantiles == 0 || params.numel() == P, "params is not the quantile net MLPSpec(D, H, A * quantiles)");
   auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
   check(state, "state", at::kFloat, N * NS);
   check(ep_len, "ep_len", at::kInt, N);
@@ -78,15 +61,6 @@ int64_t dqn_rollout_qr(int64_t env, const Tensor& params, int64_t H, int64_t T, 
   if (rc == -4) return rc;
   check_rc(rc, "dqn_rollout");
   return 0;
-}
-
-// The scalar nets (plain or dueling): the binding as it always parsed.
-int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
-                    const Tensor& ep_len, const Tensor& ep_ret, const Tensor& obs, const Tensor& nobs,
-                    const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& ep_stats, int64_t seed,
-                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling) {
-  return dqn_rollout_qr(env, params, H, T, slot0, state, ep_len, ep_ret, obs, nobs, act, rew, done, ep_stats, seed,
-                        step0, epsilon, reset_all, max_steps, dueling, 0);
 }
 
 // ------------------------------------------------------------------ prioritised replay (per.hip)
@@ -133,22 +107,20 @@ void per_update(const Tensor& tree, const Tensor& pmax, int64_t L, const Tensor&
 // looked at without one), n_step > 1 the walk.  Without `newest` there is no walk to check and the slots are one
 // row each (N = 1, newest = 0); with it N is the ring's, and n_step, filled % N and newest are the entry point's
 // to refuse.
-void dqn_targets_qr(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs,
-                    const Tensor& nobs, const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled,
-                    double gamma, bool double_q, int64_t sample_key, int64_t update, const Tensor& Xb,
-                    const Tensor& act_b, const Tensor& y, const OptT& idx, const OptT& tree,
-                    std::optional<double> beta, const OptT& w, const OptT& wmax, int64_t n_step,
-                    std::optional<int64_t> newest, const OptT& last, bool dueling, int64_t quantiles) {
+void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
+                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
+                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
+                 const OptT& idx, const OptT& tree, std::optional<double> beta, const OptT& w, const OptT& wmax,
+                 int64_t n_step, std::optional<int64_t> newest, const OptT& last, bool dueling, int64_t quantiles) {
   TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
   const int64_t D = obs.size(2);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  const int64_t AO = q_outputs(A, dueling, quantiles);
+  const int64_t P = flat_size(D, H, q_outputs(A, dueling, quantiles));
   const int64_t NQ = std::max<int64_t>(quantiles, 1);  // targets per batch row
   auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
   TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
-  const int64_t P = H * D + H + H * H + H + AO * H + AO;
   check(target, "target", at::kFloat, P);
   const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
   TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
@@ -200,16 +172,6 @@ void dqn_targets_qr(const OptT& online, const Tensor& target, int64_t H, int64_t
   check_rc(rrl_dqn_targets(&c, grid_cus(), cur_stream()), "dqn_targets");
 }
 
-// The scalar nets (plain or dueling): the binding as it always parsed.
-void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
-                 const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
-                 int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
-                 const OptT& idx, const OptT& tree, std::optional<double> beta, const OptT& w, const OptT& wmax,
-                 int64_t n_step, std::optional<int64_t> newest, const OptT& last, bool dueling) {
-  dqn_targets_qr(online, target, H, A, obs, nobs, act, rew, done, filled, gamma, double_q, sample_key, update, Xb,
-                 act_b, y, idx, tree, beta, w, wmax, n_step, newest, last, dueling, 0);
-}
-
 // ------------------------------------------------------------------ noisy layers (noisy.hip)
 // A shape the entry points refuse is theirs to refuse (the code comes back, nothing is launched); for a shape
 // they take, every tensor is sized here first.  Returns 0 or the negative code; a HIP error raises.
@@ -226,7 +188,7 @@ int64_t noisy_compose(const std::vector<OptT>& thetas, const std::vector<int64_t
   TORCH_CHECK((int64_t)thetas.size() == njobs && (int64_t)draws.size() == njobs,
               "noisy_compose takes one theta, role and draw per job");
   const bool ok = noisy_shape_ok(D, H, A_out) && njobs >= 1 && njobs <= 3;
-  const int64_t P = H * D + H + H * H + H + A_out * H + A_out, U = D + 4 * H + A_out;
+  const int64_t P = flat_size(D, H, A_out), U = D + 4 * H + A_out;
   std::vector<const float*> tp;
   std::vector<int> rl;
   std::vector<uint64_t> dr;
@@ -256,7 +218,7 @@ int64_t noisy_compose(const std::vector<OptT>& thetas, const std::vector<int64_t
 int64_t noisy_grad(const OptT& slab, int64_t role, int64_t draw, int64_t D, int64_t H, int64_t A_out, int64_t key,
                    const OptT& grad_out, int64_t nslab) {
   const bool ok = noisy_shape_ok(D, H, A_out) && nslab >= 1;
-  const int64_t P = H * D + H + H * H + H + A_out * H + A_out;
+  const int64_t P = flat_size(D, H, A_out);
   TORCH_CHECK(nslab < (int64_t)INT32_MAX / std::max<int64_t>(P, 1), "too many slabs");
   static const float dummy = 0.f;
   const float* s = ok ? opt_ptr<const float>(slab, "slab", at::kFloat, nslab * P) : &dummy;
@@ -282,22 +244,12 @@ void register_dqn_ops(pybind11::module_& m) {
   m.def("per_update", &per_update, py::arg("tree"), py::arg("pmax"), py::arg("L"), py::arg("idx"), py::arg("td_abs"),
         py::arg("alpha"), py::arg("prio_eps"));
   m.def("dqn_rollout_grid", &dqn_rollout_grid);
-  m.def("dqn_rollout", &dqn_rollout, py::arg("env"), py::arg("params"), py::arg("H"), py::arg("T"), py::arg("slot0"),
-        py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"), py::arg("act"),
-        py::arg("rew"), py::arg("done"), py::arg("ep_stats"), py::arg("seed"), py::arg("step0"), py::arg("epsilon"),
-        py::arg("reset_all"), py::arg("max_steps"), py::arg("dueling") = false);
-  m.def("dqn_rollout_qr", &dqn_rollout_qr, py::arg("env"), py::arg("params"), py::arg("H"), py::arg("T"),
+  m.def("dqn_rollout", &dqn_rollout, py::arg("env"), py::arg("params"), py::arg("H"), py::arg("T"),
         py::arg("slot0"), py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"),
         py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("ep_stats"), py::arg("seed"), py::arg("step0"),
         py::arg("epsilon"), py::arg("reset_all"), py::arg("max_steps"), py::arg("dueling") = false,
         py::arg("quantiles") = 0);
-  m.def("dqn_targets", &dqn_targets, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"), py::arg("obs"),
-        py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"), py::arg("gamma"),
-        py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"), py::arg("act_b"), py::arg("y"),
-        py::arg("idx"), py::arg("tree") = py::none(), py::arg("beta") = py::none(), py::arg("w") = py::none(),
-        py::arg("wmax") = py::none(), py::arg("n_step") = 1, py::arg("newest") = py::none(),
-        py::arg("last") = py::none(), py::arg("dueling") = false);
-  m.def("dqn_targets_qr", &dqn_targets_qr, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
+  m.def("dqn_targets", &dqn_targets, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
         py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"),
         py::arg("gamma"), py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"),
         py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("tree") = py::none(), py::arg("beta") = py::none(),

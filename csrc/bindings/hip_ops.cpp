@@ -54,10 +54,6 @@ void destroy_stream(int64_t st) {
   if (st) (void)hipStreamDestroy((hipStream_t)(uintptr_t)st);
 }
 
-int64_t flat_size(int64_t D, int64_t H, int64_t A, bool log_std) {
-  return H * D + H + H * H + H + A * H + A + (log_std ? A : 0);
-}
-
 void mlp_forward(int64_t mode, const Tensor& params, const Tensor& X, int64_t A, int64_t H, const OptT& mask,
                  const OptT& act_in, const OptT& actc_in, const OptT& act_out, const OptT& actc_out,
                  const Tensor& out0, const OptT& out1, const OptT& logits_out, int64_t seed, int64_t step,
@@ -97,11 +93,13 @@ void mlp_forward(int64_t mode, const Tensor& params, const Tensor& X, int64_t A,
 
 int64_t mlp_grad_slabs(int64_t B) { return rrl_mlp_grad_slabs((int)B, num_cus()); }
 
+// Every head (rrl_mlp_grad has the contract).  quantiles = NQ >= 1 goes with HEAD_Q_QR and with no other head: the
+// net then has A * NQ outputs, params is exactly that net, ret is [B][NQ] and clip_eps the threshold kappa > 0.
 void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, int64_t H, const OptT& mask,
               const OptT& act, const OptT& actc, const OptT& adv, const OptT& ret, const OptT& logp_old,
               const OptT& adv_stats, double inv_B, double clip_eps, double ent_coef, const Tensor& grad_slab,
               const Tensor& loss_slab, const OptT& nvalid, const OptT& inv_B_dev, const OptT& row_w,
-              const OptT& w_norm, const OptT& td_abs) {
+              const OptT& w_norm, const OptT& td_abs, int64_t quantiles) {
   check(params, "params", at::kFloat);
   check(X, "X", at::kFloat);
   TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
@@ -109,81 +107,59 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_DUEL, "bad head");
-  TORCH_CHECK(B * std::max<int64_t>(D, A) < (int64_t)INT32_MAX, "batch too large for 32-bit row indexing");
+  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_QR, "bad head");
   const bool gauss = head == HEAD_PPO_GAUSS || head == HEAD_PG_GAUSS;
   const bool cat = head == HEAD_PG_CAT || head == HEAD_PPO_CAT;
   const bool value = head == HEAD_VALUE_MSE;
-  const bool duel = head == HEAD_Q_DUEL;       // the net has A + 1 outputs: A advantages and the state value
-  const bool qtd = head == HEAD_Q_TD || duel;  // reads act + ret; no advantages
-  TORCH_CHECK(!duel || A <= 15, "a dueling net has A + 1 outputs: act dim must be in [1, 15], got ", A);
-  const int64_t P = flat_size(D, H, value ? 1 : (duel ? A + 1 : A), gauss);
+  const bool qr = head == HEAD_Q_QR;
+  const bool qhead = head == HEAD_Q_TD || head == HEAD_Q_DUEL || qr;  // reads act + ret; no advantages
+  TORCH_CHECK(qr ? quantiles >= 1 : quantiles == 0, "quantiles >= 1 goes with the Q_QR head and no other: head ", head,
+              " got quantiles = ", quantiles);
+  const int64_t AO = value ? 1 : q_outputs(A, head == HEAD_Q_DUEL, quantiles);
+  TORCH_CHECK(B * std::max<int64_t>(D, qr ? AO : A) < (int64_t)INT32_MAX, "batch too large for 32-bit row indexing");
+  const int64_t P = flat_size(D, H, AO, gauss);
   check_numel(params, "params", P);
+  if (qr) {
+    TORCH_CHECK(B >= 1, "the quantile head needs a batch row");
+    TORCH_CHECK(clip_eps > 0.0, "the quantile head needs a Huber threshold > 0, got ", clip_eps);
+    TORCH_CHECK(params.numel() == P, "params has ", params.numel(), " floats; MLPSpec(D, H, A * quantiles) has ", P);
+  }
   const int64_t nslab = mlp_grad_slabs(B);
   check(grad_slab, "grad_slab", at::kFloat, nslab * P);
   check(loss_slab, "loss_slab", at::kFloat, nslab * 8);
-  const float* m = opt_ptr<const float>(mask, "mask", at::kFloat, B * A);
-  const int* a = opt_ptr<const int>(act, "act", at::kInt, cat || qtd ? B : 0);
-  if (cat || qtd) TORCH_CHECK(a != nullptr, "act required for categorical and Q heads");
-  const float* ac = opt_ptr<const float>(actc, "actc", at::kFloat, gauss ? B * A : 0);
-  if (gauss) TORCH_CHECK(ac != nullptr, "actc required for Gaussian heads");
-  const float* ad = opt_ptr<const float>(adv, "adv", at::kFloat, B);
-  if (!value && !qtd) TORCH_CHECK(ad != nullptr, "adv required for policy heads");
-  const float* rt = opt_ptr<const float>(ret, "ret", at::kFloat, B);
-  if (value || qtd) TORCH_CHECK(rt != nullptr, "ret required for the value and Q heads");
-  const float* lpo = opt_ptr<const float>(logp_old, "logp_old", at::kFloat, B);
-  if (head == HEAD_PPO_CAT || head == HEAD_PPO_GAUSS) TORCH_CHECK(lpo != nullptr, "logp_old required for PPO heads");
-  const float* st = opt_ptr<const float>(adv_stats, "adv_stats", at::kFloat, 3);
+  MlpGradCall c{};
+  c.head = (int)head;
+  c.B = (int)B, c.D = (int)D, c.A = (int)A, c.H = (int)H, c.P = (int)P;
+  c.quantiles = (int)quantiles;
+  c.params = params.data_ptr<float>();
+  c.X = X.data_ptr<float>();
+  c.mask = opt_ptr<const float>(mask, "mask", at::kFloat, B * A);
+  c.act = opt_ptr<const int>(act, "act", at::kInt, cat || qhead ? B : 0);
+  if (cat || qhead) TORCH_CHECK(c.act != nullptr, "act required for categorical and Q heads");
+  c.actc = opt_ptr<const float>(actc, "actc", at::kFloat, gauss ? B * A : 0);
+  if (gauss) TORCH_CHECK(c.actc != nullptr, "actc required for Gaussian heads");
+  c.adv = opt_ptr<const float>(adv, "adv", at::kFloat, B);
+  if (!value && !qhead) TORCH_CHECK(c.adv != nullptr, "adv required for policy heads");
+  c.ret = opt_ptr<const float>(ret, "ret", at::kFloat, B * std::max<int64_t>(quantiles, 1));
+  if (value || qhead) TORCH_CHECK(c.ret != nullptr, "ret required for the value and Q heads");
+  c.logp_old = opt_ptr<const float>(logp_old, "logp_old", at::kFloat, B);
+  if (head == HEAD_PPO_CAT || head == HEAD_PPO_GAUSS)
+    TORCH_CHECK(c.logp_old != nullptr, "logp_old required for PPO heads");
+  c.adv_stats = opt_ptr<const float>(adv_stats, "adv_stats", at::kFloat, 3);
+  c.inv_B = (float)inv_B, c.clip_eps = (float)clip_eps, c.ent_coef = (float)ent_coef;
+  c.grad_slab = grad_slab.data_ptr<float>();
+  c.loss_slab = loss_slab.data_ptr<float>();
   // device-side batch shape (graph replays with a changing batch): valid rows / 1 / global rows
-  const int* nv = opt_ptr<const int>(nvalid, "nvalid", at::kInt, 1);
-  const float* ibd = opt_ptr<const float>(inv_B_dev, "inv_B_dev", at::kFloat, 1);
-  // prioritised replay (the Q head only): importance weights, their normaliser, |TD error| out
-  const float* rw = opt_ptr<const float>(row_w, "row_w", at::kFloat, B);
-  const float* wn = opt_ptr<const float>(w_norm, "w_norm", at::kFloat, 1);
-  float* ta = opt_ptr<float>(td_abs, "td_abs", at::kFloat, B);
-  TORCH_CHECK((rw == nullptr) == (wn == nullptr), "row_w and w_norm come together");
-  TORCH_CHECK(qtd || (rw == nullptr && ta == nullptr), "row_w / w_norm / td_abs apply to the Q heads only");
-  const int rc = rrl_mlp_grad_weighted((int)head, params.data_ptr<float>(), X.data_ptr<float>(), (int)B, (int)D,
-                                       (int)A, (int)H, m, a, ac, ad, rt, lpo, st, (float)inv_B, (float)clip_eps,
-                                       (float)ent_coef, grad_slab.data_ptr<float>(), loss_slab.data_ptr<float>(),
-                                       (int)P, nv, ibd, rw, wn, ta, num_cus(), cur_stream());
-  check_rc(rc, "mlp_grad");
-}
-
-// HEAD_Q_QR, the quantile-regression head (rrl_mlp_grad_qr): the net has A * quantiles outputs and ret is
-// [B][quantiles].  A binding of its own, so that mlp_grad above stays what it was.
-void mlp_grad_qr(const Tensor& params, const Tensor& X, int64_t A, int64_t quantiles, int64_t H, const Tensor& act,
-                 const Tensor& ret, double inv_B, double kappa, const Tensor& grad_slab, const Tensor& loss_slab,
-                 const OptT& nvalid, const OptT& inv_B_dev, const OptT& row_w, const OptT& w_norm, const OptT& td_abs) {
-  check(params, "params", at::kFloat);
-  check(X, "X", at::kFloat);
-  TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
-  const int64_t B = X.size(0), D = X.size(1), NQ = quantiles;
-  TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
-  TORCH_CHECK(A >= 1 && NQ >= 1 && A * NQ <= 16, "a quantile net has 1 <= A * quantiles <= 16 outputs, got ", A, " * ",
-              NQ);
-  TORCH_CHECK(kappa > 0.0, "the quantile head needs a Huber threshold > 0, got ", kappa);
-  TORCH_CHECK(B >= 1 && B * std::max<int64_t>(D, A * NQ) < (int64_t)INT32_MAX,
-              "batch out of range for 32-bit row indexing");
-  const int64_t P = flat_size(D, H, A * NQ, false);
-  TORCH_CHECK(params.numel() == P, "params has ", params.numel(), " floats; MLPSpec(D, H, A * quantiles) has ", P);
-  const int64_t nslab = mlp_grad_slabs(B);
-  check(grad_slab, "grad_slab", at::kFloat, nslab * P);
-  check(loss_slab, "loss_slab", at::kFloat, nslab * 8);
-  check(act, "act", at::kInt, B);
-  check(ret, "ret", at::kFloat, B * NQ);
-  const int* nv = opt_ptr<const int>(nvalid, "nvalid", at::kInt, 1);
-  const float* ibd = opt_ptr<const float>(inv_B_dev, "inv_B_dev", at::kFloat, 1);
-  const float* rw = opt_ptr<const float>(row_w, "row_w", at::kFloat, B);
-  const float* wn = opt_ptr<const float>(w_norm, "w_norm", at::kFloat, 1);
-  float* ta = opt_ptr<float>(td_abs, "td_abs", at::kFloat, B);
-  TORCH_CHECK((rw == nullptr) == (wn == nullptr), "row_w and w_norm come together");
-  check_rc(rrl_mlp_grad_qr(params.data_ptr<float>(), X.data_ptr<float>(), (int)B, (int)D, (int)A, (int)NQ, (int)H,
-                           act.data_ptr<int>(), ret.data_ptr<float>(), (float)inv_B, (float)kappa,
-                           grad_slab.data_ptr<float>(), loss_slab.data_ptr<float>(), (int)P, nv, ibd, rw, wn, ta,
-                           num_cus(), cur_stream()),
-           "mlp_grad_qr");
+  c.nvalid = opt_ptr<const int>(nvalid, "nvalid", at::kInt, 1);
+  c.inv_B_dev = opt_ptr<const float>(inv_B_dev, "inv_B_dev", at::kFloat, 1);
+  // prioritised replay (the Q heads only): importance weights, their normaliser, |TD error| or row loss out
+  c.row_w = opt_ptr<const float>(row_w, "row_w", at::kFloat, B);
+  c.w_norm = opt_ptr<const float>(w_norm, "w_norm", at::kFloat, 1);
+  c.td_abs = opt_ptr<float>(td_abs, "td_abs", at::kFloat, B);
+  TORCH_CHECK((c.row_w == nullptr) == (c.w_norm == nullptr), "row_w and w_norm come together");
+  TORCH_CHECK(qhead || (c.row_w == nullptr && c.td_abs == nullptr),
+              "row_w / w_norm / td_abs apply to the Q heads only");
+  check_rc(rrl_mlp_grad(&c, num_cus(), cur_stream()), "mlp_grad");
 }
 
 int64_t scan_tm_parts(int64_t N) { return rrl_scan_tm_parts((int)N); }
@@ -401,7 +377,7 @@ void rollout(int64_t env, const Tensor& params, int64_t H, const Tensor& state, 
   auto [D, A, NS, ms] = env_dims(env);
   (void)ms;
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  check(params, "params", at::kFloat, flat_size(D, H, A, false));
+  check(params, "params", at::kFloat, flat_size(D, H, A));
   check(act_buf, "act_buf", at::kInt);
   TORCH_CHECK(act_buf.dim() == 2, "act_buf must be [T, N]");
   const int64_t T = act_buf.size(0), N = act_buf.size(1);
@@ -477,8 +453,9 @@ EvalShape check_eval_bufs(int64_t D, const Tensor& ep_ret, const Tensor& ep_len,
   return sh;
 }
 
-// Fused policy evaluation (evaluate.hip): every env runs E complete episodes under fixed weights.
-void evaluate_qr(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
+// Fused policy evaluation (evaluate.hip): every env runs E complete episodes under fixed weights.  dueling /
+// quantiles: params is that Q-network, exactly, and such a net is evaluated greedily.
+void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
               const Tensor& ep_code, const OptT& tr_obs, const OptT& tr_act, const OptT& tr_rew, const OptT& tr_done,
               int64_t seed, int64_t step0, bool greedy, int64_t max_steps, bool dueling, int64_t quantiles) {
   auto [D, A, NS, ms] = env_dims(env);
@@ -487,13 +464,8 @@ void evaluate_qr(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_
   TORCH_CHECK(env != ENV_HALFCHEETAH, "evaluate takes the discrete device envs; use evaluate_cont for env 4");
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(!dueling || greedy, "a dueling Q-network is evaluated greedily: softmax-of-Q is not its policy");
-  TORCH_CHECK(!dueling || A <= 15, "a dueling net has A + 1 outputs: act dim must be in [1, 15], got ", A);
-  TORCH_CHECK(quantiles >= 0, "quantiles must be >= 0, got ", quantiles);
-  TORCH_CHECK(quantiles == 0 || greedy, "a quantile Q-network is evaluated greedily: softmax-of-Q is not its policy");
-  TORCH_CHECK(quantiles == 0 || !dueling, "quantiles with dueling is not built: set one of the two");
-  TORCH_CHECK(A * quantiles <= 16, "a quantile net has A * quantiles <= 16 outputs, got ", A, " * ", quantiles);
-  check_exact(params, "params", at::kFloat,
-              flat_size(D, H, quantiles > 0 ? A * quantiles : A + (dueling ? 1 : 0), false));
+  TORCH_CHECK(quantiles <= 0 || greedy, "a quantile Q-network is evaluated greedily: softmax-of-Q is not its policy");
+  check_exact(params, "params", at::kFloat, flat_size(D, H, q_outputs(A, dueling, quantiles)));
   const EvalShape sh = check_eval_bufs(D, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done, at::kInt, 0,
                                        max_steps);
   const bool tr = sh.Tc > 0;
@@ -504,14 +476,6 @@ void evaluate_qr(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_
                         (uint64_t)seed, (uint64_t)step0, greedy ? 1 : 0, (int)max_steps, dueling ? 1 : 0,
                         (int)quantiles, num_cus(), cur_stream()),
            "evaluate");
-}
-
-// The scalar nets (plain or dueling): the binding as it always parsed.
-void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
-              const Tensor& ep_code, const OptT& tr_obs, const OptT& tr_act, const OptT& tr_rew, const OptT& tr_done,
-              int64_t seed, int64_t step0, bool greedy, int64_t max_steps, bool dueling) {
-  evaluate_qr(env, params, H, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done, seed, step0, greedy, max_steps,
-              dueling, 0);
 }
 
 void evaluate_cont(int64_t env, const Tensor& params, const Tensor& env_consts, int64_t H, const Tensor& ep_ret,
@@ -562,13 +526,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("destroy_stream", &destroy_stream);
   m.def("mlp_forward", &mlp_forward);
   m.def("mlp_grad_slabs", &mlp_grad_slabs);
-  m.def("mlp_grad", &mlp_grad);
-  m.def("mlp_grad_qr", &mlp_grad_qr, pybind11::arg("params"), pybind11::arg("X"), pybind11::arg("A"),
-        pybind11::arg("quantiles"), pybind11::arg("H"), pybind11::arg("act"), pybind11::arg("ret"),
-        pybind11::arg("inv_B"), pybind11::arg("kappa"), pybind11::arg("grad_slab"), pybind11::arg("loss_slab"),
+  // 22 positional parameters in the order they always had; the device-side shape, the prioritised trio and
+  // quantiles are optional
+  m.def("mlp_grad", &mlp_grad, pybind11::arg("head"), pybind11::arg("params"), pybind11::arg("X"), pybind11::arg("A"),
+        pybind11::arg("H"), pybind11::arg("mask"), pybind11::arg("act"), pybind11::arg("actc"), pybind11::arg("adv"),
+        pybind11::arg("ret"), pybind11::arg("logp_old"), pybind11::arg("adv_stats"), pybind11::arg("inv_B"),
+        pybind11::arg("clip_eps"), pybind11::arg("ent_coef"), pybind11::arg("grad_slab"), pybind11::arg("loss_slab"),
         pybind11::arg("nvalid") = pybind11::none(), pybind11::arg("inv_B_dev") = pybind11::none(),
         pybind11::arg("row_w") = pybind11::none(), pybind11::arg("w_norm") = pybind11::none(),
-        pybind11::arg("td_abs") = pybind11::none());
+        pybind11::arg("td_abs") = pybind11::none(), pybind11::arg("quantiles") = 0);
   m.def("set_value_grad_stamps", [](const Tensor& t) { rrl_set_value_grad_stamps(t.numel() ? t.data_ptr() : nullptr); });
   m.def("set_value_grad_tune", [](int64_t t) { return (int64_t)rrl_set_value_grad_tune((int)t); });
   m.def("set_value_grad_mode", [](int64_t mode) { return (int64_t)rrl_set_value_grad_mode((int)mode); },
@@ -605,11 +571,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rollout", &rollout);
   m.def("rollout_cont", &rollout_cont);
   m.def("evaluate", &evaluate, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("H"),
-        pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"), pybind11::arg("tr_obs"),
-        pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"), pybind11::arg("seed"),
-        pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"),
-        pybind11::arg("dueling") = false);
-  m.def("evaluate_qr", &evaluate_qr, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("H"),
         pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"), pybind11::arg("tr_obs"),
         pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"), pybind11::arg("seed"),
         pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"),

@@ -26,7 +26,7 @@ enum GradHead : int {
   HEAD_PG_GAUSS = 4,   // REINFORCE / A2C with a Gaussian policy
   HEAD_Q_TD = 5,       // DQN: loss = mean(huber(Q(x)[act] - ret, delta)); delta travels in clip_eps
   HEAD_Q_DUEL = 6,     // HEAD_Q_TD on a dueling net of A + 1 outputs: Q = out[A] + out[act] - mean(out[0 .. A-1])
-  HEAD_Q_QR = 7,       // QR-DQN: quantile-Huber loss on a net of A * NQ outputs (rrl_mlp_grad_qr has the contract)
+  HEAD_Q_QR = 7,       // QR-DQN: quantile-Huber loss on a net of A * NQ outputs (rrl_mlp_grad has the contract)
 };
 
 enum EnvId : int { ENV_CARTPOLE = 0, ENV_MOUNTAINCAR = 1, ENV_ACROBOT = 2, ENV_LUNARLANDER = 3, ENV_HALFCHEETAH = 4 };
@@ -53,6 +53,24 @@ struct DqnTargetsCall {
   int quantiles;                 // 0: the scalar forms above; NQ >= 1: nets MLPSpec(D, H, A * NQ) and y [B][NQ]
 };
 
+// The arguments of rrl_mlp_grad, which has the contract.
+struct MlpGradCall {
+  int head;                      // a GradHead
+  int B, D, A, H, P;             // shape: batch rows, obs dim, actions, hidden size, floats of the net
+  int quantiles;                 // NQ >= 1 with HEAD_Q_QR, 0 with every scalar head
+  const float *params, *X;       // net [P] and inputs [B][D]
+  const float* mask;             // [B][A] or null
+  const int* act;                // [B]
+  const float *actc, *adv, *ret, *logp_old;  // [B][A], [B], [B] ([B][NQ] with HEAD_Q_QR), [B]
+  const float* adv_stats;        // [3] = {sum, sumsq, count} or null
+  float inv_B, clip_eps, ent_coef;  // scalars; clip_eps: PPO clip, delta of HEAD_Q_TD / Q_DUEL, kappa of HEAD_Q_QR
+  float *grad_slab, *loss_slab;  // slabs: [rrl_mlp_grad_slabs()][P] and [..][8]
+  const int* nvalid;             // device-side batch shape, each may be null
+  const float* inv_B_dev;
+  const float *row_w, *w_norm;   // prioritised replay: [B], [1], both or neither
+  float* td_abs;                 // [B], may be null
+};
+
 }  // namespace rrl
 
 extern "C" {
@@ -67,42 +85,40 @@ int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D,
 int rrl_set_value_fwd_mode(int mode);
 
 // ---- mlp_grad.hip
-// head: a GradHead.  HEAD_Q_TD reads act and ret (the TD target) and takes its Huber threshold delta
-// from clip_eps, which it has no other use for; mask, adv, logp_old and ent_coef are ignored.
-// HEAD_Q_DUEL is HEAD_Q_TD on the dueling net: A stays the number of actions, params / P / the slabs are
-// those of A + 1 outputs (rows 0 .. A-1 the advantages, row A the state value), and in fp32
-//   s = out[0]; s += out[k] (k = 1 .. A-1, ascending);  m = s / A;  Q(a) = (out[A] - m) + out[a].
-// -2: A outside [1, 16] or D outside [1, 32]; -3: H not 64 / 128, or HEAD_Q_DUEL with A > 15; -4: the net
-// and the staging do not fit the LDS; -1: HEAD_Q_QR, which has its own entry point below
-int rrl_mlp_grad(int head, const float* params, const float* X, int B, int D, int A, int H, const float* mask,
-                 const int* act, const float* actc, const float* adv, const float* ret, const float* logp_old,
-                 const float* adv_stats, float inv_B, float clip_eps, float ent_coef, float* grad_slab,
-                 float* loss_slab, int P, const int* nvalid, const float* inv_B_dev, int num_cu, void* stream);
-// rrl_mlp_grad plus the per-row weights of prioritised replay, read by HEAD_Q_TD and HEAD_Q_DUEL alone: with w_i =
-// row_w[i] / *w_norm the row's loss is w_i * huber and its gradient is scaled by w_i; td_abs[i] (may be
-// null) receives |Q(x_i)[act_i] - ret_i| of every valid row.  row_w and w_norm come together or not at
-// all (-1); all three null is rrl_mlp_grad
-int rrl_mlp_grad_weighted(int head, const float* params, const float* X, int B, int D, int A, int H,
-                          const float* mask, const int* act, const float* actc, const float* adv, const float* ret,
-                          const float* logp_old, const float* adv_stats, float inv_B, float clip_eps, float ent_coef,
-                          float* grad_slab, float* loss_slab, int P, const int* nvalid, const float* inv_B_dev,
-                          const float* row_w, const float* w_norm, float* td_abs, int num_cu, void* stream);
-// HEAD_Q_QR, the quantile-regression head of QR-DQN (Dabney et al. 2018).  params / P / the slabs are those of
-// MLPSpec(D, H, A * NQ); output a * NQ + i is quantile i of action a at level tau_i = (2 i + 1) / (2 NQ).  For a
-// row with action act: theta_i = out[act * NQ + i], T_j = qtarget[row][j] ([B][NQ]), u_ij = T_j - theta_i and
-//   rho = (1 / NQ) sum_i sum_j |tau_i - [u_ij < 0]| * huber_kappa(u_ij) / kappa,
-//   dout[act * NQ + i] = inv_B * w * -(1 / NQ) sum_j |tau_i - [u_ij < 0]| * clamp(u_ij, -kappa, kappa) / kappa,
-// every other output 0, w = row_w[row] / *w_norm or 1.  Loss slab: [0] += w * rho, [4] += s_act / NQ (s_act the
-// ascending fp32 sum of the action's quantiles), [5] += 1.  td_abs[row] (may be null) = rho, the unweighted row
-// loss.  act[row] is clamped into [0, A) (it indexes the output registers): an out-of-range action of a valid row
-// trains action 0 or A - 1, where HEAD_Q_TD would give the row no gradient.  nvalid / inv_B_dev as rrl_mlp_grad.
-// Nothing is written on a refusal: -1 a null pointer, or row_w without w_norm; -2 B < 1, A < 1, NQ < 1,
-// A * NQ > 16, D outside [1, 32], kappa <= 0, or P not the net's; -3 H not 64 / 128; -4 the net and the staging do
-// not fit the LDS
-int rrl_mlp_grad_qr(const float* params, const float* X, int B, int D, int A, int NQ, int H, const int* act,
-                    const float* qtarget, float inv_B, float kappa, float* grad_slab, float* loss_slab, int P,
-                    const int* nvalid, const float* inv_B_dev, const float* row_w, const float* w_norm,
-                    float* td_abs, int num_cu, void* stream);
+// The fused forward + backward of every head.  Per head, what is read besides params, X, the slabs and the three
+// optional groups below (a field a head does not read is ignored, except where a refusal names it):
+//   HEAD_PG_CAT     act, adv; mask, adv_stats (may be null); ent_coef
+//   HEAD_VALUE_MSE  ret; the net has one output whatever A says
+//   HEAD_PPO_CAT    act, adv, logp_old; mask, adv_stats (may be null); clip_eps the PPO clip, ent_coef
+//   HEAD_PPO_GAUSS  actc, adv, logp_old; adv_stats (may be null); clip_eps the PPO clip, ent_coef
+//   HEAD_PG_GAUSS   actc, adv; adv_stats (may be null); ent_coef
+//   HEAD_Q_TD       act, ret (the TD target [B]); clip_eps is the Huber threshold delta
+//   HEAD_Q_DUEL     HEAD_Q_TD on the dueling net: A stays the number of actions, params / P / the slabs are those of
+//                   A + 1 outputs (rows 0 .. A-1 the advantages, row A the state value), and in fp32
+//                     s = out[0]; s += out[k] (k = 1 .. A-1, ascending);  m = s / A;  Q(a) = (out[A] - m) + out[a]
+//   HEAD_Q_QR       act, ret (the target quantiles [B][NQ], NQ = quantiles); clip_eps is the Huber threshold kappa.
+//                   The quantile-regression head of QR-DQN (Dabney et al. 2018): params / P / the slabs are those of
+//                   MLPSpec(D, H, A * NQ); output a * NQ + i is quantile i of action a at level tau_i = (2 i + 1) /
+//                   (2 NQ).  For a row with action act: theta_i = out[act * NQ + i], T_j = ret[row][j], u_ij = T_j -
+//                   theta_i and
+//                     rho = (1 / NQ) sum_i sum_j |tau_i - [u_ij < 0]| * huber_kappa(u_ij) / kappa,
+//                     dout[act * NQ + i] =
+//                       inv_B * w * -(1 / NQ) sum_j |tau_i - [u_ij < 0]| * clamp(u_ij, -kappa, kappa) / kappa,
+//                   every other output 0.  Loss slab: [0] += w * rho, [4] += s_act / NQ (s_act the ascending fp32 sum
+//                   of the action's quantiles), [5] += 1.  act[row] is clamped into [0, A) (it indexes the output
+//                   registers): an out-of-range action of a valid row trains action 0 or A - 1, where HEAD_Q_TD would
+//                   give the row no gradient.
+// nvalid / inv_B_dev (each may be null): the batch shape read from device memory; rows >= *nvalid are inert and
+// *inv_B_dev replaces inv_B.  row_w / w_norm / td_abs (the three Q heads, each may be null): the row's weight is
+// w = row_w[row] / *w_norm (else 1) in the loss and the gradient, and td_abs[row] of every valid row receives
+// |Q(x)[act] - ret| (HEAD_Q_TD, HEAD_Q_DUEL) or rho, the unweighted row loss (HEAD_Q_QR).
+// Nothing is written on a refusal; checked in this order.
+// -1: a head that is no GradHead; HEAD_Q_QR with quantiles < 1, or quantiles != 0 with another head; HEAD_Q_QR with a
+// null params, X, act, ret or slab; row_w without w_norm or the reverse; row_w or td_abs with a head that is not one
+// of the three Q heads.  -2: A outside [1, 16] or D outside [1, 32]; HEAD_Q_QR with B < 1, A * NQ > 16 or kappa <= 0.
+// -3: H not 64 / 128, or HEAD_Q_DUEL with A > 15.  -2: HEAD_Q_QR with P not that of MLPSpec(D, H, A * NQ).  -4: the
+// net and the staging do not fit the LDS
+int rrl_mlp_grad(const rrl::MlpGradCall* c, int num_cu, void* stream);
 // number of partial-gradient slabs (== grid size) rrl_mlp_grad uses
 int rrl_mlp_grad_slabs(int B, int num_cu);
 // 1 = bf16x6 weight-stationary kernels, 0 = fp32 MFMA; returns the previous mode (-1 queries)

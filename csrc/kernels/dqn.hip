@@ -469,7 +469,7 @@ static int dispatch_dqn_targets(const DqnNStepArgs& a, int H, bool per, bool nst
 
 // The quantile instances of (H, PER, NSTEP): the same blocks with NQ behind them.
 template <int HT, bool PER, bool NSTEP>
-static int launch_dqn_targets_qr(const DqnNStepArgs& a, int NQ, int grid, hipStream_t s) {
+static int launch_quantile_targets(const DqnNStepArgs& a, int NQ, int grid, hipStream_t s) {
   using L = LdsNet<1, HT>;
   DqnTargetArgsOf<NSTEP, true> q;
   static_cast<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>&>(q) = a;
@@ -480,17 +480,17 @@ static int launch_dqn_targets_qr(const DqnNStepArgs& a, int NQ, int grid, hipStr
   return (int)hipGetLastError();
 }
 
-static int dispatch_dqn_targets_qr(const DqnNStepArgs& a, int NQ, int H, bool per, bool nstep, int grid,
+static int dispatch_quantile_targets(const DqnNStepArgs& a, int NQ, int H, bool per, bool nstep, int grid,
                                    hipStream_t s) {
   switch ((per ? 4 : 0) | (nstep ? 2 : 0) | (H == 128 ? 1 : 0)) {
-    case 0: return launch_dqn_targets_qr<4, false, false>(a, NQ, grid, s);
-    case 1: return launch_dqn_targets_qr<8, false, false>(a, NQ, grid, s);
-    case 2: return launch_dqn_targets_qr<4, false, true>(a, NQ, grid, s);
-    case 3: return launch_dqn_targets_qr<8, false, true>(a, NQ, grid, s);
-    case 4: return launch_dqn_targets_qr<4, true, false>(a, NQ, grid, s);
-    case 5: return launch_dqn_targets_qr<8, true, false>(a, NQ, grid, s);
-    case 6: return launch_dqn_targets_qr<4, true, true>(a, NQ, grid, s);
-    default: return launch_dqn_targets_qr<8, true, true>(a, NQ, grid, s);
+    case 0: return launch_quantile_targets<4, false, false>(a, NQ, grid, s);
+    case 1: return launch_quantile_targets<8, false, false>(a, NQ, grid, s);
+    case 2: return launch_quantile_targets<4, false, true>(a, NQ, grid, s);
+    case 3: return launch_quantile_targets<8, false, true>(a, NQ, grid, s);
+    case 4: return launch_quantile_targets<4, true, false>(a, NQ, grid, s);
+    case 5: return launch_quantile_targets<8, true, false>(a, NQ, grid, s);
+    case 6: return launch_quantile_targets<4, true, true>(a, NQ, grid, s);
+    default: return launch_quantile_targets<8, true, true>(a, NQ, grid, s);
   }
 }
 
@@ -536,7 +536,7 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
     if (e != hipSuccess) return (int)e;
   }
   const int grid = dqn_targets_grid(c->B, num_cu);
-  const int rc = NQ > 0 ? dispatch_dqn_targets_qr(a, NQ, c->H, per, nstep, grid, s)
+  const int rc = NQ > 0 ? dispatch_quantile_targets(a, NQ, c->H, per, nstep, grid, s)
                         : dispatch_dqn_targets(a, c->H, per, nstep, duel, grid, s);
   if (rc || nstep || !c->last) return rc;
   // the one-step kernel has no walk: its target bootstraps from the sampled row itself

@@ -587,7 +587,7 @@ static int dispatch_a3(const GradArgsOf<HEAD>& a, int grid, hipStream_t s) {
 }
 
 template <int DT, int HT>
-static int dispatch_head(int head, const GradArgs& a, int grid, hipStream_t s) {
+static int dispatch_head(int head, const GradQrArgs& a, int grid, hipStream_t s) {
   switch (head) {
     case HEAD_PG_CAT: return dispatch_a3<DT, HT, HEAD_PG_CAT>(a, grid, s);
     case HEAD_VALUE_MSE: return launch_grad<DT, HT, HEAD_VALUE_MSE, 1>(a, grid, s);
@@ -596,6 +596,7 @@ static int dispatch_head(int head, const GradArgs& a, int grid, hipStream_t s) {
     case HEAD_PG_GAUSS: return dispatch_a3<DT, HT, HEAD_PG_GAUSS>(a, grid, s);
     case HEAD_Q_TD: return dispatch_a3<DT, HT, HEAD_Q_TD>(a, grid, s);
     case HEAD_Q_DUEL: return dispatch_a3<DT, HT, HEAD_Q_DUEL>(a, grid, s);
+    case HEAD_Q_QR: return dispatch_a3<DT, HT, HEAD_Q_QR>(a, grid, s);  // the one head that takes the whole block
   }
   return -1;
 }
@@ -619,36 +620,34 @@ extern "C" int rrl_mlp_grad_slabs(int B, int num_cu) {
   return grid;
 }
 
-extern "C" int rrl_mlp_grad(int head, const float* params, const float* X, int B, int D, int A, int H,
-                            const float* mask, const int* act, const float* actc, const float* adv,
-                            const float* ret, const float* logp_old, const float* adv_stats,
-                            float inv_B, float clip_eps, float ent_coef, float* grad_slab,
-                            float* loss_slab, int P, const int* nvalid, const float* inv_B_dev, int num_cu,
-                            void* stream) {
-  return rrl_mlp_grad_weighted(head, params, X, B, D, A, H, mask, act, actc, adv, ret, logp_old, adv_stats, inv_B,
-                               clip_eps, ent_coef, grad_slab, loss_slab, P, nvalid, inv_B_dev, nullptr, nullptr,
-                               nullptr, num_cu, stream);
-}
-
-extern "C" int rrl_mlp_grad_weighted(int head, const float* params, const float* X, int B, int D, int A, int H,
-                                     const float* mask, const int* act, const float* actc, const float* adv,
-                                     const float* ret, const float* logp_old, const float* adv_stats, float inv_B,
-                                     float clip_eps, float ent_coef, float* grad_slab, float* loss_slab, int P,
-                                     const int* nvalid, const float* inv_B_dev, const float* row_w,
-                                     const float* w_norm, float* td_abs, int num_cu, void* stream) {
+extern "C" int rrl_mlp_grad(const MlpGradCall* c, int num_cu, void* stream) {
+  const int head = c->head, D = c->D, A = c->A, H = c->H, NQ = c->quantiles;
+  const bool qr = head == HEAD_Q_QR, qhead = qr || head == HEAD_Q_TD || head == HEAD_Q_DUEL;
+  if (head < HEAD_PG_CAT || head > HEAD_Q_QR) return -1;
+  if (qr ? NQ < 1 : NQ != 0) return -1;
+  if (qr && (!c->params || !c->X || !c->act || !c->ret || !c->grad_slab || !c->loss_slab)) return -1;
+  if ((c->row_w == nullptr) != (c->w_norm == nullptr)) return -1;
+  if ((c->row_w != nullptr || c->td_abs != nullptr) && !qhead) return -1;
   if (A < 1 || A > kMaxAct || D < 1 || D > 32) return -2;
-  if (head == HEAD_Q_QR) return -1;  // the quantile head has its own entry point, rrl_mlp_grad_qr
+  if (qr && (c->B < 1 || (long long)A * NQ > kMaxAct || !(c->clip_eps > 0.f))) return -2;
+  if (H != 64 && H != 128) return -3;
   if (head == HEAD_Q_DUEL && A + 1 > kMaxAct) return -3;  // the net has A + 1 outputs
-  if ((row_w == nullptr) != (w_norm == nullptr)) return -1;
-  if ((row_w != nullptr || td_abs != nullptr) && head != HEAD_Q_TD && head != HEAD_Q_DUEL) return -1;
-  GradArgs a{params, X, B, D, A, mask, act, actc, adv, ret, logp_old, adv_stats, inv_B, clip_eps,
-             ent_coef, grad_slab, loss_slab, P};
-  a.nvalid = nvalid;
-  a.inv_B_dev = inv_B_dev;
-  a.row_w = row_w;
-  a.w_norm = w_norm;
-  a.td_abs = td_abs;
-  const int grid = rrl_mlp_grad_slabs(B, num_cu);
+  if (qr && c->P != H * D + H + H * H + H + A * NQ * H + A * NQ) return -2;  // not MLPSpec(D, H, A * NQ)
+  GradQrArgs a;  // the scalar heads launch with its GradArgs part
+  static_cast<GradArgs&>(a) = {c->params, c->X, c->B, D, A, c->mask, c->act, c->actc, c->adv, c->ret, c->logp_old,
+                               c->adv_stats, c->inv_B, c->clip_eps, c->ent_coef, c->grad_slab, c->loss_slab, c->P};
+  a.nvalid = c->nvalid;
+  a.inv_B_dev = c->inv_B_dev;
+  a.row_w = c->row_w;
+  a.w_norm = c->w_norm;
+  a.td_abs = c->td_abs;
+  if (qr) {  // its targets are [B][NQ] and it takes no other optional input
+    a.mask = a.actc = a.adv = a.ret = a.logp_old = a.adv_stats = nullptr;
+    a.ent_coef = 0.f;
+    a.qtarget = c->ret;
+    a.NQ = NQ;
+  }
+  const int grid = rrl_mlp_grad_slabs(c->B, num_cu);
   hipStream_t s = (hipStream_t)stream;
   if (head == HEAD_VALUE_MSE && g_value_grad_mode == 1 && value_grad_split_supported(D, H))
     return launch_value_grad_split(a, grid, s);
@@ -656,33 +655,5 @@ extern "C" int rrl_mlp_grad_weighted(int head, const float* params, const float*
     return launch_policy_grad_split(a, head, grid, s);
   const int DT = (D <= 16) ? 1 : 2;
   if (H == 128) return DT == 1 ? dispatch_head<1, 8>(head, a, grid, s) : dispatch_head<2, 8>(head, a, grid, s);
-  if (H == 64) return DT == 1 ? dispatch_head<1, 4>(head, a, grid, s) : dispatch_head<2, 4>(head, a, grid, s);
-  return -3;
-}
-
-extern "C" int rrl_mlp_grad_qr(const float* params, const float* X, int B, int D, int A, int NQ, int H, const int* act,
-                               const float* qtarget, float inv_B, float kappa, float* grad_slab, float* loss_slab,
-                               int P, const int* nvalid, const float* inv_B_dev, const float* row_w,
-                               const float* w_norm, float* td_abs, int num_cu, void* stream) {
-  if (!params || !X || !act || !qtarget || !grad_slab || !loss_slab) return -1;
-  if ((row_w == nullptr) != (w_norm == nullptr)) return -1;
-  if (B < 1 || A < 1 || NQ < 1 || (long long)A * NQ > kMaxAct || D < 1 || D > 32 || !(kappa > 0.f)) return -2;
-  if (H != 64 && H != 128) return -3;
-  const int AO = A * NQ;
-  if (P != H * D + H + H * H + H + AO * H + AO) return -2;  // not MLPSpec(D, H, A * NQ)
-  GradQrArgs a;
-  static_cast<GradArgs&>(a) = {params, X, B, D, A, nullptr, act, nullptr, nullptr, nullptr, nullptr, nullptr, inv_B,
-                               kappa, 0.f, grad_slab, loss_slab, P};
-  a.nvalid = nvalid;
-  a.inv_B_dev = inv_B_dev;
-  a.row_w = row_w;
-  a.w_norm = w_norm;
-  a.td_abs = td_abs;
-  a.qtarget = qtarget;
-  a.NQ = NQ;
-  const int grid = rrl_mlp_grad_slabs(B, num_cu);
-  hipStream_t s = (hipStream_t)stream;
-  const int DT = (D <= 16) ? 1 : 2;
-  if (H == 128) return DT == 1 ? dispatch_a3<1, 8, HEAD_Q_QR>(a, grid, s) : dispatch_a3<2, 8, HEAD_Q_QR>(a, grid, s);
-  return DT == 1 ? dispatch_a3<1, 4, HEAD_Q_QR>(a, grid, s) : dispatch_a3<2, 4, HEAD_Q_QR>(a, grid, s);
+  return DT == 1 ? dispatch_head<1, 4>(head, a, grid, s) : dispatch_head<2, 4>(head, a, grid, s);
 }

@@ -1,11 +1,29 @@
 """Flat-parameter MLP layout (``MLPSpec``), importable without torch: CPU agents (api/agent.py,
 models/cpu_policy.py) split the learner's flat weight vector with it; the device learner and
-the kernels use the same offsets (ops/mlp.py re-exports it)."""
+the kernels use the same offsets (ops/mlp.py re-exports it).  ``q_outputs`` is the one copy of the rule
+for how many outputs a Q-network has."""
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
 from typing import Optional
+
+
+def q_outputs(A: int, dueling: bool = False, quantiles: int = 0) -> int:
+    """Outputs of a Q-network over ``A`` actions, as the kernels hold them (16 at most): ``A`` for the plain net,
+    ``A + 1`` (the state value) for the dueling one, ``A * quantiles`` for the quantile one (``quantiles`` = 0 is a
+    scalar net), and never both.  Raises ``ValueError`` for a combination that is not built."""
+    A, NQ = int(A), int(quantiles)
+    if NQ < 0:
+        raise ValueError(f"quantiles must be >= 0, got {quantiles}")
+    if NQ > 0 and dueling:
+        raise ValueError("quantiles > 0 with dueling=True is not built: the two heads share 16 outputs and the "
+                         "combination needs its own design; set quantiles=0 or dueling=False")
+    if NQ > 0 and A * NQ > 16:
+        raise ValueError(f"a quantile net has A * quantiles <= 16 outputs, got A = {A} and quantiles = {NQ}")
+    if dueling and not 1 <= A <= 15:
+        raise ValueError(f"a dueling net has A + 1 <= 16 outputs: A must be in [1, 15], got {A}")
+    return A * NQ if NQ else A + 1 if dueling else A
 
 
 @dataclass(frozen=True)

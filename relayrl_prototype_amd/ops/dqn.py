@@ -18,6 +18,7 @@ import torch
 
 from . import philox
 from . import reference as ref
+from ..models.mlp_spec import MLPSpec, q_outputs
 
 
 class ReplayRing(NamedTuple):
@@ -44,37 +45,23 @@ def dqn_rollout_grid(num_envs: int) -> int:
 
 def check_quantiles(A: int, quantiles, dueling: bool = False) -> int:
     """``quantiles`` as the kernels take it -> NQ: 0 is the scalar net; NQ >= 1 a quantile net of ``A * NQ <= 16``
-    outputs, which the dueling head is not built for."""
-    NQ = int(quantiles)
-    if NQ < 0:
-        raise ValueError(f"quantiles must be >= 0, got {quantiles}")
-    if NQ > 0 and dueling:
-        raise ValueError("quantiles > 0 with dueling=True is not built: the two heads share 16 outputs and the "
-                         "combination needs its own design; set quantiles=0 or dueling=False")
-    if NQ > 0 and int(A) * NQ > 16:
-        raise ValueError(f"a quantile net has A * quantiles <= 16 outputs, got A = {A} and quantiles = {NQ}")
-    return NQ
+    outputs, which the dueling head is not built for (``q_outputs`` has the rule)."""
+    q_outputs(A, dueling, quantiles)
+    return int(quantiles)
 
 
 def check_q_params(params, D: int, H: int, A: int, dueling: bool, name: str = "params", quantiles: int = 0):
-    """A Q-network over ``A`` actions is ``MLPSpec(D, H, A)``, a dueling one ``MLPSpec(D, H, A + 1)`` (at most
-    16 outputs, so ``A <= 15``), a quantile one ``MLPSpec(D, H, A * quantiles)`` (``A * quantiles <= 16``):
-    ``params`` must have exactly that many floats."""
-    from .mlp import MLPSpec
-
-    NQ = check_quantiles(A, quantiles, dueling) if quantiles else 0
-    if dueling and not 1 <= int(A) <= 15:
-        raise ValueError(f"a dueling net has A + 1 <= 16 outputs: A must be in [1, 15], got {A}")
-    if NQ > 0:
-        want = MLPSpec(int(D), int(H), int(A) * NQ).P
-        if params is not None and params.numel() != want:
-            raise ValueError(f"{name} has {params.numel()} floats; a quantile Q-network of D = {D}, H = {H}, A = {A}, "
-                             f"quantiles = {NQ} has {want}")
+    """A Q-network over ``A`` actions is ``MLPSpec(D, H, q_outputs(A, dueling, quantiles))``: ``params`` must have
+    exactly that many floats."""
+    NQ = int(quantiles)
+    want = MLPSpec(int(D), int(H), q_outputs(A, dueling, NQ)).P
+    if params is None or params.numel() == want:
         return
-    want = MLPSpec(int(D), int(H), int(A) + (1 if dueling else 0)).P
-    if params is not None and params.numel() != want:
-        raise ValueError(f"{name} has {params.numel()} floats; a {'dueling' if dueling else 'plain'} Q-network of "
-                         f"D = {D}, H = {H}, A = {A} has {want} (dueling = {bool(dueling)})")
+    if NQ:
+        raise ValueError(f"{name} has {params.numel()} floats; a quantile Q-network of D = {D}, H = {H}, A = {A}, "
+                         f"quantiles = {NQ} has {want}")
+    raise ValueError(f"{name} has {params.numel()} floats; a {'dueling' if dueling else 'plain'} Q-network of "
+                     f"D = {D}, H = {H}, A = {A} has {want} (dueling = {bool(dueling)})")
 
 
 def dqn_rollout(env_id: int, params: torch.Tensor, hidden: int, rollout_len: int, slot0: int, ring: ReplayRing,
@@ -97,14 +84,9 @@ def dqn_rollout(env_id: int, params: torch.Tensor, hidden: int, rollout_len: int
     if dueling or quantiles:
         D, A, _, _ = h.env_dims(int(env_id))
         check_q_params(params, D, hidden, A, bool(dueling), quantiles=quantiles)
-    if quantiles:  # the quantile nets have a binding of their own: the scalar one parses what it always parsed
-        return int(h.dqn_rollout_qr(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len,
-                                    ep_ret, ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed),
-                                    int(step0), float(epsilon), bool(reset_all), int(max_steps), bool(dueling),
-                                    int(quantiles)))
     return int(h.dqn_rollout(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len, ep_ret,
                              ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed), int(step0),
-                             float(epsilon), bool(reset_all), int(max_steps), bool(dueling)))
+                             float(epsilon), bool(reset_all), int(max_steps), bool(dueling), int(quantiles)))
 
 
 def dqn_sample_rows_ref(seed: int, update: int, B: int, filled: int) -> np.ndarray:
@@ -237,7 +219,7 @@ def _check_q_nets(online, target, D, H, A, dueling, quantiles=0):
 def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
     """(Q_target [B, A], a* [B]) at ``nobs``: the selecting net is the online one with ``double_q``, else the
     target; a dueling net selects on its advantage outputs and evaluates ``reference.dueling_q``."""
-    AO = A + 1 if dueling else A
+    AO = q_outputs(A, dueling)
     out_t = ref.trunk(target.to(dtype), nobs, D, H, AO)[0]
     sel = ref.trunk(online.to(dtype), nobs, D, H, AO)[0] if double_q else out_t
     astar, _ = ref.greedy_from_logits(sel[..., :A])
@@ -310,16 +292,10 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
     if per and out[3] is None:
         raise ValueError("the prioritised form writes idx: it cannot be skipped")
     w, wmax = out[4:6] if per else (None, None)
-    # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling) in its order: a positional call
-    # parses faster than a keyword one, and this is the one place that makes it
-    if NQ:  # the quantile nets have a binding of their own: the scalar one parses what it always parsed
-        hip().dqn_targets_qr(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act,
-                             ring.rew, ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update),
-                             *out[:4], tree, float(beta) if per else None, w, wmax, n_step, newest,
-                             out[base] if len(out) > base else None, dueling, NQ)
-        return out
+    # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling, quantiles) in its order: a
+    # positional call parses faster than a keyword one, and this is the one place that makes it
     hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
                       ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), *out[:4], tree,
                       float(beta) if per else None, w, wmax, n_step, newest,
-                      out[base] if len(out) > base else None, dueling)
+                      out[base] if len(out) > base else None, dueling, NQ)
     return out

@@ -45,22 +45,15 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     continuous = int(env_id) == h.ENV_IDS["ENV_HALFCHEETAH"]
     if continuous and env_consts is None:
         raise ValueError("the continuous device env needs env_consts")
-    if dueling:
+    if dueling or quantiles:
         from .dqn import check_q_params
 
+        kind = "dueling" if dueling else "quantile"
         if continuous:
-            raise ValueError("a dueling Q-network needs a discrete action space")
+            raise ValueError(f"a {kind} Q-network needs a discrete action space")
         if not greedy:
-            raise ValueError("a dueling Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
-        check_q_params(params, D, hidden, A, True, quantiles=quantiles)
-    elif quantiles:
-        from .dqn import check_q_params
-
-        if continuous:
-            raise ValueError("a quantile Q-network needs a discrete action space")
-        if not greedy:
-            raise ValueError("a quantile Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
-        check_q_params(params, D, hidden, A, False, quantiles=quantiles)
+            raise ValueError(f"a {kind} Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
+        check_q_params(params, D, hidden, A, bool(dueling), quantiles=quantiles)
     E, N = int(episodes), int(num_envs)
     if E < 1 or N < 1:
         raise ValueError(f"episodes and num_envs must be >= 1, got {E} and {N}")
@@ -81,10 +74,6 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     args = (int(hidden), ep_ret, ep_len, ep_code, *tr, int(seed), int(step0), bool(greedy), max_steps)
     if continuous:
         h.evaluate_cont(int(env_id), params, env_consts, *args)
-    elif quantiles:  # the quantile nets have a binding of their own
-        h.evaluate_qr(int(env_id), params, *args, bool(dueling), int(quantiles))
-    elif dueling:
-        h.evaluate(int(env_id), params, *args, True)
     else:
-        h.evaluate(int(env_id), params, *args)
+        h.evaluate(int(env_id), params, *args, bool(dueling), int(quantiles))
     return ep_ret, ep_len, ep_code, trace

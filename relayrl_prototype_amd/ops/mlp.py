@@ -36,7 +36,7 @@ class GradHead(IntEnum):
     Q_QR = 7  # QR-DQN: quantile-Huber loss on a net of A * quantiles outputs; ret is [B, quantiles]
 
 
-from ..models.mlp_spec import MLPSpec  # noqa: E402,F401 -- torch-free (CPU agents import it)
+from ..models.mlp_spec import MLPSpec, q_outputs  # noqa: E402,F401 -- torch-free (CPU agents import it)
 
 
 def _hip_for(t):
@@ -130,6 +130,12 @@ def set_value_grad_mode(mode: int) -> int:
     return int(hip().set_value_grad_mode(int(mode)))
 
 
+# The heads as plain ints: mlp_grad runs once per update, and an enum member costs a metaclass lookup each time.
+_VALUE, _DUEL, _QR = int(GradHead.VALUE_MSE), int(GradHead.Q_DUEL), int(GradHead.Q_QR)
+_Q_HEADS = (int(GradHead.Q_TD), _DUEL, _QR)  # read act + ret, and may take row_w / w_norm / td_abs
+_GAUSS_HEADS = (int(GradHead.PPO_GAUSS), int(GradHead.PG_GAUSS))
+
+
 def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=None, adv=None, ret=None,
              logp_old=None, adv_stats=None, inv_B: Optional[float] = None, clip_eps: float = 0.2,
              ent_coef: float = 0.0, grad_slab=None, loss_slab=None, nvalid=None, inv_B_dev=None, row_w=None,
@@ -141,78 +147,89 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
     -- rows >= nvalid are inert and inv_B_dev replaces inv_B -- so a captured graph can replay
     a batch whose valid row count changes (agent rows folded into a fixed capacity).
 
-    ``row_w`` [B] / ``w_norm`` [1] / ``td_abs`` [B] (the Q_TD and Q_DUEL heads, prioritised replay): row i
+    ``row_w`` [B] / ``w_norm`` [1] / ``td_abs`` [B] (the Q_TD, Q_DUEL and Q_QR heads, prioritised replay): row i
     weighs ``row_w[i] / w_norm`` in the loss and the gradient, and ``td_abs[i]`` receives ``|Q - ret|`` of
     every valid row (rows past ``nvalid`` are left alone).
 
     ``Q_DUEL``: ``A`` stays the number of actions (at most 15); ``params`` and the gradient slab are those
     of ``MLPSpec(D, H, A + 1)``.
 
-    ``Q_QR`` with ``quantiles`` = NQ >= 1 is ``mlp_grad_qr`` below, which has the contract; the two come together."""
-    if quantiles or head == GradHead.Q_QR:
-        if int(head) != GradHead.Q_QR:
-            raise ValueError(f"quantiles ({quantiles}) goes with the Q_QR head")
-        return mlp_grad_qr(params, X, A, quantiles, H, act=act, ret=ret, inv_B=inv_B, kappa=clip_eps,
-                           grad_slab=grad_slab, loss_slab=loss_slab, nvalid=nvalid, inv_B_dev=inv_B_dev, row_w=row_w,
-                           w_norm=w_norm, td_abs=td_abs)
+    ``Q_QR``, the quantile-regression head of QR-DQN, comes with ``quantiles`` = NQ >= 1 (``A * NQ <= 16``) and no
+    other head does: ``params`` and the slab are those of ``MLPSpec(D, H, A * NQ)`` (output ``a * NQ + i`` is quantile
+    ``i`` of action ``a``), ``ret`` is [B, NQ], ``clip_eps`` > 0 is the Huber threshold kappa and ``td_abs[i]``
+    receives the row's UNWEIGHTED quantile-Huber loss (``reference.mlp_grad_ref`` has the formula)."""
+    head, NQ = int(head), int(quantiles)
+    qr = head == _QR
     X = X.contiguous().float()
-    B = X.shape[0]
+    B, D = X.shape
     if inv_B is None:
         inv_B = 1.0 / max(B, 1)
     if (row_w is None) != (w_norm is None):
         raise ValueError("row_w and w_norm come together")
-    if int(head) not in (GradHead.Q_TD, GradHead.Q_DUEL) and (row_w is not None or td_abs is not None):
-        raise ValueError("row_w / w_norm / td_abs apply to the Q_TD and Q_DUEL heads only")
-    if int(head) == GradHead.Q_DUEL and not 1 <= int(A) <= 15:
-        raise ValueError(f"a dueling net has A + 1 <= 16 outputs: A must be in [1, 15], got {A}")
+    if head not in _Q_HEADS and (row_w is not None or td_abs is not None):
+        raise ValueError("row_w / w_norm / td_abs apply to the Q_TD, Q_DUEL and Q_QR heads only")
+    if NQ and not qr:
+        raise ValueError(f"quantiles ({quantiles}) goes with the Q_QR head")
+    if qr and NQ < 1:
+        raise ValueError(f"the Q_QR head needs quantiles >= 1, got {quantiles}")
+    outputs = 1 if head == _VALUE else q_outputs(A, head == _DUEL, NQ)
+    P = MLPSpec(D, H, outputs, head in _GAUSS_HEADS).P
+    if qr:
+        if not clip_eps > 0:
+            raise ValueError(f"the quantile head needs a Huber threshold (clip_eps / huber_delta) > 0, got {clip_eps}")
+        if params.numel() != P:
+            raise ValueError(f"params has {params.numel()} floats; a quantile Q-network of D = {D}, H = {H}, A = {A}, "
+                             f"quantiles = {NQ} has {P}")
+        if act is None or ret is None or ret.numel() != B * NQ:
+            raise ValueError(f"act [B] and ret [B, quantiles] = [{B}, {NQ}] targets are required")
     h = _hip_for(X)
-    if h is None and (nvalid is not None or inv_B_dev is not None):
+    if h is None:
+        if qr:
+            ret = ret.reshape(B, NQ)
         n = B if nvalid is None else int(nvalid.reshape(-1)[0])
         ib = inv_B if inv_B_dev is None else float(inv_B_dev.reshape(-1)[0])
 
         def cut(t):
             return None if t is None else t[:n]
 
-        return mlp_grad(head, params, X[:n], A, H, cut(mask), cut(act), cut(actc), cut(adv), cut(ret), cut(logp_old),
-                        adv_stats, ib, clip_eps, ent_coef, row_w=cut(row_w), w_norm=w_norm, td_abs=cut(td_abs))
-    if h is None:
-        g, st = ref.mlp_grad_ref(int(head), params, X, A, H, mask, act, actc, adv, ret, logp_old, adv_stats,
-                                 inv_B, clip_eps, ent_coef, row_w=row_w, w_norm=w_norm)
+        g, st = ref.mlp_grad_ref(head, params, X[:n], A, H, cut(mask), cut(act), cut(actc), cut(adv), cut(ret),
+                                 cut(logp_old), adv_stats, ib, clip_eps, ent_coef, row_w=cut(row_w), w_norm=w_norm,
+                                 quantiles=NQ)
         if td_abs is not None:
-            td_abs.copy_(st["td_abs"])
+            td_abs[:n].copy_(st["td_abs"])
         ls = torch.zeros(1, 8)
         ls[0, 0] = st.get("loss", 0.0)
         ls[0, 1] = st.get("entropy", 0.0)
         ls[0, 2] = st.get("kl", 0.0)
         ls[0, 3] = st.get("clipfrac", 0.0)
         ls[0, 4] = st.get("v", 0.0)
-        ls[0, 5] = st.get("count", B)
+        ls[0, 5] = st.get("count", n)
         return g.view(1, -1), ls
-    gaussian = int(head) in (GradHead.PPO_GAUSS, GradHead.PG_GAUSS)
-    Aeff = 1 if int(head) == GradHead.VALUE_MSE else A + 1 if int(head) == GradHead.Q_DUEL else A
-    P = MLPSpec(X.shape[1], H, Aeff, gaussian).P
-    ns = grad_slabs(B, X.device)
+    chunks = grad_chunks(B)
+    if len(chunks) > 1 and qr:
+        raise ValueError(f"the quantile head takes a single-launch batch (<= {GRAD_CHUNK_ROWS} rows)")
+    if len(chunks) > 1 and nvalid is not None:
+        raise ValueError("a device-side row count needs a single-launch batch (< 2^25 rows)")
+    if td_abs is not None and not (td_abs.is_contiguous() and td_abs.dtype == torch.float32):
+        raise ValueError("td_abs is written in place: it must be a contiguous float32 tensor")
+    counts = [int(h.mlp_grad_slabs(hi - lo)) for lo, hi in chunks]  # slabs of each launch, back to back
+    ns = sum(counts)
     if grad_slab is None:
         grad_slab = torch.empty(ns, P, device=X.device)
     if loss_slab is None:
         loss_slab = torch.empty(ns, 8, device=X.device)
     mask, act, actc, adv, ret, logp_old = _f32(mask), _i32(act), _f32(actc), _f32(adv), _f32(ret), _f32(logp_old)
+    row_w = _f32(row_w)
     off = 0
-    chunks = grad_chunks(B)
-    if nvalid is not None and len(chunks) > 1:
-        raise ValueError("a device-side row count needs a single-launch batch (< 2^25 rows)")
-    if td_abs is not None and not (td_abs.is_contiguous() and td_abs.dtype == torch.float32):
-        raise ValueError("td_abs is written in place: it must be a contiguous float32 tensor")
-    for lo, hi in chunks:
+    for (lo, hi), n in zip(chunks, counts):
         whole = lo == 0 and hi == B
 
         def rows(t):
             return t if (t is None or whole) else t[lo:hi]
 
-        n = int(h.mlp_grad_slabs(hi - lo))
-        h.mlp_grad(int(head), params, rows(X), A, H, rows(mask), rows(act), rows(actc), rows(adv), rows(ret),
+        h.mlp_grad(head, params, rows(X), A, H, rows(mask), rows(act), rows(actc), rows(adv), rows(ret),
                    rows(logp_old), adv_stats, float(inv_B), float(clip_eps), float(ent_coef), grad_slab[off:off + n],
-                   loss_slab[off:off + n], nvalid, inv_B_dev, rows(_f32(row_w)), w_norm, rows(td_abs))
+                   loss_slab[off:off + n], nvalid, inv_B_dev, rows(row_w), w_norm, rows(td_abs), NQ)
         off += n
     return grad_slab[:ns], loss_slab[:ns]
 
@@ -220,54 +237,10 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
 def mlp_grad_qr(params, X, A: int, quantiles: int, H: int, act=None, ret=None, inv_B: Optional[float] = None,
                 kappa: float = 1.0, grad_slab=None, loss_slab=None, nvalid=None, inv_B_dev=None, row_w=None, w_norm=None,
                 td_abs=None):
-    """The quantile-regression head of QR-DQN (``GradHead.Q_QR``, ``quantiles`` = NQ >= 1, ``A * NQ <= 16``), with
-    ``mlp_grad``'s results.  ``params`` and the slab are those of ``MLPSpec(D, H, A * NQ)`` (output ``a * NQ + i`` is
-    quantile ``i`` of action ``a``), ``ret`` is [B, NQ], ``kappa`` > 0 is the Huber threshold, ``row_w`` / ``w_norm`` /
-    ``nvalid`` / ``inv_B_dev`` apply as in ``mlp_grad`` and ``td_abs[i]`` receives the row's UNWEIGHTED quantile-Huber
-    loss (``reference.mlp_grad_ref`` has the formula).  CPU tensors take the reference."""
-    X = X.contiguous().float()
-    B, D = X.shape
-    NQ = int(quantiles)
-    if inv_B is None:
-        inv_B = 1.0 / max(B, 1)
-    if (row_w is None) != (w_norm is None):
-        raise ValueError("row_w and w_norm come together")
-    if NQ < 1:
-        raise ValueError(f"the Q_QR head needs quantiles >= 1, got {quantiles}")
-    if not 1 <= int(A) * NQ <= 16:
-        raise ValueError(f"a quantile net has A * quantiles <= 16 outputs, got {A} * {NQ}")
-    if not kappa > 0:
-        raise ValueError(f"the quantile head needs a Huber threshold (clip_eps / huber_delta) > 0, got {kappa}")
-    P = MLPSpec(D, H, int(A) * NQ).P
-    if params.numel() != P:
-        raise ValueError(f"params has {params.numel()} floats; a quantile Q-network of D = {D}, H = {H}, A = {A}, "
-                         f"quantiles = {NQ} has {P}")
-    if act is None or ret is None or ret.numel() != B * NQ:
-        raise ValueError(f"act [B] and ret [B, quantiles] = [{B}, {NQ}] targets are required")
-    ret = ret.reshape(B, NQ)
-    h = _hip_for(X)
-    if h is None:
-        n = B if nvalid is None else int(nvalid.reshape(-1)[0])
-        ib = inv_B if inv_B_dev is None else float(inv_B_dev.reshape(-1)[0])
-        g, st = ref.mlp_grad_ref(ref.HEAD_Q_QR, params, X[:n], A, H, act=act[:n], ret=ret[:n], inv_B=ib, clip_eps=kappa,
-                                 row_w=None if row_w is None else row_w[:n], w_norm=w_norm, quantiles=NQ)
-        if td_abs is not None:
-            td_abs[:n].copy_(st["td_abs"])
-        ls = torch.zeros(1, 8)
-        ls[0, 0], ls[0, 4], ls[0, 5] = st["loss"], st["v"], st["count"]
-        return g.view(1, -1), ls
-    if B > GRAD_CHUNK_ROWS:
-        raise ValueError(f"the quantile head takes a single-launch batch (<= {GRAD_CHUNK_ROWS} rows)")
-    if td_abs is not None and not (td_abs.is_contiguous() and td_abs.dtype == torch.float32):
-        raise ValueError("td_abs is written in place: it must be a contiguous float32 tensor")
-    ns = grad_slabs(B, X.device)
-    if grad_slab is None:
-        grad_slab = torch.empty(ns, P, device=X.device)
-    if loss_slab is None:
-        loss_slab = torch.empty(ns, 8, device=X.device)
-    h.mlp_grad_qr(params, X, int(A), NQ, int(H), _i32(act), _f32(ret), float(inv_B), float(kappa), grad_slab[:ns],
-                  loss_slab[:ns], nvalid, inv_B_dev, _f32(row_w), w_norm, td_abs)
-    return grad_slab[:ns], loss_slab[:ns]
+    """``mlp_grad`` with ``GradHead.Q_QR``, which has the contract; ``kappa`` is its ``clip_eps``."""
+    return mlp_grad(GradHead.Q_QR, params, X, A, H, act=act, ret=ret, inv_B=inv_B, clip_eps=kappa, grad_slab=grad_slab,
+                    loss_slab=loss_slab, nvalid=nvalid, inv_B_dev=inv_B_dev, row_w=row_w, w_norm=w_norm, td_abs=td_abs,
+                    quantiles=quantiles)
 
 
 def reduce_slabs(slab: torch.Tensor, scale: float = 1.0, out=None):

@@ -56,7 +56,7 @@ this and launches the kernels it always launched.
 at most 16 outputs (CartPole: 8 quantiles, LunarLanderSynth: 4).  The actor and the evaluator act on the argmax of
 the per-action quantile SUMS (``reference.quantile_q``: ascending adds, no division), ``dqn_targets`` writes
 ``y [B, NQ]``, the n-step target applied to each quantile of the target net at ``a*``, and the update is
-``mlp_grad_qr``, the quantile-Huber loss with kappa = ``huber_delta`` (> 0).  With ``prioritized`` the priority is
+``mlp_grad(Q_QR)``, the quantile-Huber loss with kappa = ``huber_delta`` (> 0).  With ``prioritized`` the priority is
 the row's unweighted loss, as in Rainbow.  ``QVals`` is the mean of ``sum / NQ``.  It composes with ``double_q``,
 ``prioritized``, ``n_step`` and ``noisy`` (which only sees ``A * NQ`` outputs); ``quantiles`` with ``dueling`` is
 refused: 16 outputs would leave CartPole 5 quantiles and the combination needs its own design.  ``quantiles = 0``
@@ -75,7 +75,6 @@ import torch
 
 from ..algorithms.core import FlatNet
 from ..ops import GradHead, MLPSpec, ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_targets, grad_slabs, hip, mlp_grad
-from ..ops import mlp_grad_qr
 from ..ops import PriorityTree, per_insert, per_update
 from ..ops import adam_step, noisy_compose, noisy_grad, noisy_sigma_init
 from ..parallel.comm import Comm
@@ -240,7 +239,7 @@ class DQNTrainer:
         self.q = FlatNet(MLPSpec(D, H, A * NQ if NQ else A + 1 if cfg.dueling else A), cfg.q_lr, dev, g)
         self.head = GradHead.Q_QR if NQ else GradHead.Q_DUEL if cfg.dueling else GradHead.Q_TD
         # what the head adds to the actor's, the evaluator's and the targets' calls; a plain trainer passes what it
-        # always passed.  The quantile head's gradient is an op of its own (_grad_qr)
+        # always passed.  The gradient takes the head, and quantiles with it
         self._head_kw = dict(quantiles=NQ) if NQ else dict(dueling=True) if cfg.dueling else {}
         self.target = self.q.params.clone()
         self.theta = None
@@ -337,13 +336,6 @@ class DQNTrainer:
                   beta1=q.betas[0], beta2=q.betas[1], eps=q.eps, weight_decay=q.weight_decay)
         q.version += 1
 
-    def _grad_qr(self, params):
-        """The quantile head's gradient slabs of one batch (``mlp_grad_qr``), with the weights of prioritised replay
-        where there are any."""
-        per = {} if self.per is None else dict(row_w=self.w, w_norm=self.wmax, td_abs=self.td_abs)
-        mlp_grad_qr(params, self.Xb, self.A, self.NQ, self.cfg.hidden, act=self.act_b, ret=self.y,
-                    kappa=self.cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, **per)
-
     def update(self):
         """One gradient step on a freshly sampled batch; the target network follows on its schedule."""
         cfg = self.cfg
@@ -355,22 +347,16 @@ class DQNTrainer:
             dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None),
                         **nstep, **self._head_kw)
-            if self.NQ:
-                self._grad_qr(params)
-            else:
-                mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
-                         clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss)
+            mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                     clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, quantiles=self.NQ)
             self._apply()
         else:
             dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, tree=self.per.tree, beta=self.last_beta,
                         out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep, **self._head_kw)
-            if self.NQ:
-                self._grad_qr(params)
-            else:
-                mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
-                         clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
-                         w_norm=self.wmax, td_abs=self.td_abs)
+            mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
+                     clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
+                     w_norm=self.wmax, td_abs=self.td_abs, quantiles=self.NQ)
             self._apply()
             per_update(self.per, self.idx, self.td_abs, cfg.per_alpha, cfg.per_eps)
         self.updates += 1

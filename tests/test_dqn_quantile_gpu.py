@@ -122,7 +122,7 @@ def test_quantile_actor_refusals_write_nothing(cuda):
            True, 10)
     for net, dueling, NQ in ((plain, False, 8), (q16, False, 9), (q16, True, 8), (q16, False, -1)):
         with pytest.raises(RuntimeError):  # the binding's own checks
-            hip().dqn_rollout_qr(e.env_id, net, H, ACT_T, 0, *raw, dueling, NQ)
+            hip().dqn_rollout(e.env_id, net, H, ACT_T, 0, *raw, dueling, NQ)
     torch.cuda.synchronize()
     untouched(g["obs"], g["nobs"], g["act"], g["rew"], g["done"], *persist)
 
@@ -153,8 +153,8 @@ def test_quantile_evaluator_acts_on_the_sums(cuda, name, NQ, H):
     with pytest.raises(ValueError, match="greedily"):
         evaluate_policy_op(e.env_id, params.to(DEV), H, E, N, greedy=False, quantiles=NQ, **kw)
     with pytest.raises(RuntimeError):  # the binding refuses it too
-        hip().evaluate_qr(e.env_id, params.to(DEV), H, out[0].t, out[1].t, out[2].t, *(t.t for t in tr), 1, 0, False,
-                          e.max_steps, False, NQ)
+        hip().evaluate(e.env_id, params.to(DEV), H, out[0].t, out[1].t, out[2].t, *(t.t for t in tr), 1, 0, False,
+                       e.max_steps, False, quantiles=NQ)
     if NQ > 1:
         with pytest.raises(ValueError, match="floats"):  # a scalar net is not a quantile one
             evaluate_policy_op(e.env_id, ro.case_params(e, H, DEV), H, E, N, quantiles=NQ)
@@ -258,13 +258,13 @@ def test_quantile_targets_refuse_bad_arguments(cuda):
         args = (online, net, H, A, *r, L, 0.9, True, 1, 0, *o[:4])
         per = dict(tree=tree, beta=0.5, w=w.t, wmax=wmax.t)
         with pytest.raises(RuntimeError):
-            h.dqn_targets_qr(*args, **extra)
+            h.dqn_targets(*args, **extra)
         with pytest.raises(RuntimeError):
-            h.dqn_targets_qr(*args, n_step=3, newest=2, last=o[4], **extra)
+            h.dqn_targets(*args, n_step=3, newest=2, last=o[4], **extra)
         with pytest.raises(RuntimeError):
-            h.dqn_targets_qr(*args, **per, **extra)
+            h.dqn_targets(*args, **per, **extra)
         with pytest.raises(RuntimeError):
-            h.dqn_targets_qr(*args, **per, n_step=3, newest=2, last=o[4], **extra)
+            h.dqn_targets(*args, **per, n_step=3, newest=2, last=o[4], **extra)
     with pytest.raises(ValueError, match="16"):
         dqn_targets(q24, q24, H, 3, ring, L, 0.9, True, 1, 0, B, out=o[:4], quantiles=8)
     with pytest.raises(ValueError, match="floats"):
@@ -388,13 +388,14 @@ def test_q_qr_head_refusals_write_nothing(cuda):
     gs, gl, gtd = Guarded((1, p24.numel())), Guarded((1, 8)), Guarded((B,))
 
     def raw(p, A, kappa, NQ):
-        hip().mlp_grad_qr(p, X, A, NQ, H, act, T, 1.0 / B, kappa, gs.t, gl.t, td_abs=gtd.t)
+        hip().mlp_grad(int(GradHead.Q_QR), p, X, A, H, None, act, None, None, T, None, None, 1.0 / B, kappa, 0.0, gs.t,
+                       gl.t, td_abs=gtd.t, quantiles=NQ)
 
     for p, A, kappa, NQ in ((p24, 3, 1.0, 8), (p16, 2, 1.0, 0), (p16, 2, 1.0, -1), (p16, 2, 0.0, 8), (p16, 2, -1.0, 8),
                             (p2, 2, 1.0, 8), (p24, 2, 1.0, 8)):
         with pytest.raises(RuntimeError):
             raw(p, A, kappa, NQ)
-    with pytest.raises(RuntimeError):  # the scalar binding does not know the head
+    with pytest.raises(RuntimeError):  # no quantiles: Q_QR needs quantiles >= 1
         hip().mlp_grad(int(GradHead.Q_QR), p16, X, 2, H, None, act, None, None, T, None, None, 1.0 / B, 1.0, 0.0, gs.t,
                        gl.t, None, None, None, None, gtd.t)
     with pytest.raises(ValueError, match="quantiles"):  # quantiles with another head
