@@ -47,6 +47,14 @@ is the ``cartpole-dqn-quantile`` preset): ``epoch_<shape>_<scalar|quantile>_us``
 ``profiles/dqn_quantile_bench.jsonl`` unless ``--out`` names another file.  ``--quantile-learning EPOCHS`` instead
 records, for seeds 1..3 of ``cartpole-dqn-nstep`` and ``cartpole-dqn-quantile``, the greedy mean return over 256
 episodes every 100 epochs: one line per run in ``profiles/dqn_quantile_learning.jsonl``.
+
+``--atoms NA`` adds, from the same process, the categorical head (C51, ``atoms = NA`` on [0, 100], the wide output layer)
+against the scalar one at the shape of ``cartpole-dqn-nstep`` (with ``NA = 51`` it is the ``cartpole-dqn-c51`` preset):
+``epoch_<scalar|c51>_us`` and the microseconds per launch of ``dqn_rollout``, ``evaluate`` (one step budget of 64 envs),
+``dqn_targets`` and ``mlp_grad`` (``<kernel>_<scalar|c51>_us``).  The line goes to ``profiles/dqn_c51_bench.jsonl``
+unless ``--out`` names another file.  ``--c51-learning EPOCHS`` instead records, for seeds 1..3 of
+``cartpole-dqn-nstep``, ``cartpole-dqn-quantile`` and ``cartpole-dqn-c51``, the greedy mean return over 256 episodes
+every 100 epochs: one line per run in ``profiles/dqn_c51_learning.jsonl``.
 """
 import argparse
 import json
@@ -278,24 +286,84 @@ def quantile_records(a, dev, event_us):
     return rec
 
 
-def quantile_learning(a, dev):
-    """Greedy mean return over 256 episodes every 100 epochs, seeds 1..3, ``cartpole-dqn-nstep`` and
-    ``cartpole-dqn-quantile``: one JSON line per run."""
+def c51_records(a, dev, event_us):
+    """The categorical head (``atoms = a.atoms`` on [0, 100]) against the scalar one in one process, at the shape of
+    ``cartpole-dqn-nstep`` (prioritised, 3-step: with 51 atoms it is the ``cartpole-dqn-c51`` preset): the epoch, and
+    the four launches that stage the Q-network."""
+    from relayrl_prototype_amd.ops import dqn_rollout, dqn_targets, evaluate_policy_op, mlp_grad
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    base = PRESETS["cartpole-dqn-nstep"].overrides
+    assert PRESETS["cartpole-dqn-c51"].overrides == dict(base, atoms=51, v_min=0.0, v_max=100.0)
+    rec = dict(atoms=a.atoms)
+    for NA in (0, a.atoms):
+        sup = dict(atoms=NA, v_min=0.0, v_max=100.0) if NA else {}
+        cfg = DQNConfig(**dict(base, **sup))
+        tr = DQNTrainer(cfg, device=dev)
+        for _ in range(a.warmup):
+            tr.train_epoch()
+        assert tr.updates > 0, "the warm-up must reach learning_starts"
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.epochs):
+            tr.train_epoch()
+        torch.cuda.synchronize()
+        key = "c51" if NA else "scalar"
+        rec[f"epoch_{key}_us"] = round(1e6 * (time.perf_counter() - t0) / a.epochs, 2)
+        N, T, B, C = cfg.num_envs, cfg.rollout_len, cfg.batch_size, cfg.buffer_slots
+        filled = min(tr.slots_written, C) * N
+        out = (tr.Xb, tr.act_b, tr.y, tr.idx, tr.w, tr.wmax)
+        ev = (torch.zeros(1, 64, device=dev), torch.zeros(1, 64, dtype=torch.int32, device=dev),
+              torch.zeros(1, 64, dtype=torch.int32, device=dev))
+
+        def rollout():  # the same slot and step every time: timing only
+            dqn_rollout(tr.env_id, tr.q.params, cfg.hidden, T, 0, tr.ring, tr.state, tr.ep_len, tr.ep_ret,
+                        tr.ep_stats, seed=tr.env_seed, step0=0, epsilon=0.1, reset_all=False,
+                        max_steps=tr.max_steps, **sup)
+
+        def evaluate():  # 64 envs, one episode of at most 64 steps each
+            evaluate_policy_op(tr.env_id, tr.q.params, cfg.hidden, 1, 64, greedy=True, seed=tr.eval_seed, step0=0,
+                               max_steps=64, out=ev, **sup)
+
+        def targets():
+            dqn_targets(tr.q.params, tr.target, cfg.hidden, tr.A, tr.ring, filled, cfg.gamma, cfg.double_q,
+                        tr.sample_seed, 7, B, out=out, tree=tr.per.tree, beta=0.7, n_step=cfg.n_step,
+                        newest=(tr.cursor - 1) % C, **sup)
+
+        def grad_q():
+            mlp_grad(tr.head, tr.q.params, tr.Xb, tr.A, cfg.hidden, act=tr.act_b, ret=tr.y, clip_eps=cfg.huber_delta,
+                     grad_slab=tr.slab, loss_slab=tr.loss, row_w=tr.w, w_norm=tr.wmax, td_abs=tr.td_abs, **sup)
+
+        for name, fn in (("dqn_rollout", rollout), ("evaluate", evaluate), ("dqn_targets", targets),
+                         ("mlp_grad", grad_q)):
+            fn()
+            torch.cuda.synchronize()
+            med, lo, hi = event_us(fn, a.iters, a.reps)
+            rec[f"{name}_{key}_us"] = med
+            rec[f"{name}_{key}_us_range"] = [lo, hi]
+    return rec
+
+
+def quantile_learning(a, dev, presets=("cartpole-dqn-nstep", "cartpole-dqn-quantile"), epochs=None):
+    """Greedy mean return over 256 episodes every 100 epochs, seeds 1..3, of ``presets`` (``--quantile-learning``:
+    ``cartpole-dqn-nstep`` and ``cartpole-dqn-quantile``; ``--c51-learning`` adds ``cartpole-dqn-c51``): one JSON
+    line per run."""
     from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
     from relayrl_prototype_amd.runtime.launcher import PRESETS
 
     lines = []
-    for preset in ("cartpole-dqn-nstep", "cartpole-dqn-quantile"):
+    for preset in presets:
         for seed in (1, 2, 3):
             cfg = DQNConfig(**dict(PRESETS[preset].overrides, seed=seed))
             tr = DQNTrainer(cfg, device=dev)
             curve = []
-            for epoch in range(1, a.quantile_learning + 1):
+            for epoch in range(1, (epochs or a.quantile_learning) + 1):
                 tr.train_epoch()
                 if epoch % 100 == 0:
                     curve.append(round(tr.evaluate(episodes=1, num_envs=256).stats()["mean_return"], 1))
-            lines.append(json.dumps(dict(preset=preset, quantiles=cfg.quantiles, n_step=cfg.n_step, seed=seed,
-                                         eval_every=100, env_steps_per_epoch=cfg.num_envs * cfg.rollout_len,
+            lines.append(json.dumps(dict(preset=preset, quantiles=cfg.quantiles, atoms=cfg.atoms, n_step=cfg.n_step,
+                                         seed=seed, eval_every=100, env_steps_per_epoch=cfg.num_envs * cfg.rollout_len,
                                          greedy_mean_return_256=curve)))
             print(lines[-1], flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -392,14 +460,22 @@ def main():
                     help="also measure the quantile head (QR-DQN) with NQ quantiles against the scalar one")
     ap.add_argument("--quantile-learning", type=int, default=0, metavar="EPOCHS",
                     help="record greedy-return curves of cartpole-dqn-quantile and cartpole-dqn-nstep instead")
+    ap.add_argument("--atoms", type=int, default=0, metavar="NA",
+                    help="also measure the categorical head (C51) with NA atoms against the scalar one")
+    ap.add_argument("--c51-learning", type=int, default=0, metavar="EPOCHS",
+                    help="record greedy-return curves of cartpole-dqn-c51, -quantile and -nstep instead")
     a = ap.parse_args()
+    if a.atoms and not 2 <= a.atoms <= 64:
+        raise SystemExit("--atoms takes 2 .. 64 (CartPole has 2 actions and the wide layer 8 tiles of 16 outputs)")
     if a.quantiles < 0 or 2 * a.quantiles > 16:
         raise SystemExit("--quantiles takes 1 .. 8 (CartPole has 2 actions and the kernels hold 16 outputs)")
     if any(k < 1 for k in a.n_step):
         raise SystemExit("--n-step takes values >= 1")
     if (a.prioritized or a.n_step or a.dueling or a.noisy or a.noisy_learning or a.quantiles
-            or a.quantile_learning) and not a.out:
+            or a.quantile_learning or a.atoms or a.c51_learning) and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "dqn_c51_learning.jsonl" if a.c51_learning else
+                             "dqn_c51_bench.jsonl" if a.atoms else
                              "dqn_quantile_learning.jsonl" if a.quantile_learning else
                              "dqn_quantile_bench.jsonl" if a.quantiles else
                              "dqn_noisy_learning.jsonl" if a.noisy_learning else
@@ -418,6 +494,9 @@ def main():
         return noisy_learning(a, dev)
     if a.quantile_learning:
         return quantile_learning(a, dev)
+    if a.c51_learning:
+        return quantile_learning(a, dev, ("cartpole-dqn-nstep", "cartpole-dqn-quantile", "cartpole-dqn-c51"),
+                                 a.c51_learning)
     cfg = DQNConfig(**PRESETS["cartpole-dqn"].overrides)
     tr = DQNTrainer(cfg, device=dev)
     for _ in range(a.warmup):
@@ -476,6 +555,8 @@ def main():
         rec.update(noisy_records(a, dev, event_us))
     if a.quantiles:
         rec.update(quantile_records(a, dev, event_us))
+    if a.atoms:
+        rec.update(c51_records(a, dev, event_us))
     rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
     line = json.dumps(rec)
     print(line, flush=True)

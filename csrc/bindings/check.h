@@ -57,6 +57,19 @@ inline int64_t q_outputs(int64_t A, bool dueling, int64_t quantiles) {
   return quantiles > 0 ? A * quantiles : A + (dueling ? 1 : 0);
 }
 
+// Outputs of a categorical (C51) Q-network over A actions, A * atoms, and whether the kernels have it: it goes with
+// neither the dueling nor the quantile head, has 2 <= atoms, v_min < v_max, and fits the wide output layer's 8 tiles
+// of 16 outputs with every action's atoms rounded up to whole tiles.
+inline int64_t c51_outputs(int64_t A, int64_t atoms, double v_min, double v_max, bool dueling, int64_t quantiles) {
+  TORCH_CHECK(quantiles == 0, "atoms with quantiles is not built: set one of the two");
+  TORCH_CHECK(!dueling, "atoms with dueling is not built: set one of the two");
+  TORCH_CHECK(atoms >= 2, "atoms must be 0 or >= 2, got ", atoms);
+  TORCH_CHECK(v_max > v_min, "atoms needs v_min < v_max, got v_min = ", v_min, " and v_max = ", v_max);
+  TORCH_CHECK(A >= 1 && atoms <= 64 && A * ((atoms + 15) / 16) <= 8, "a categorical net has A * ceil(atoms / 16) <= 8 ",
+              "output tiles, got A = ", A, " and atoms = ", atoms);
+  return A * atoms;
+}
+
 // Floats of MLPSpec(D, H, A) (+ log_std).
 inline int64_t flat_size(int64_t D, int64_t H, int64_t A, bool log_std = false) {
   return H * D + H + H * H + H + A * H + A + (log_std ? A : 0);

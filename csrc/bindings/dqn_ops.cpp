@@ -37,15 +37,18 @@ std::tuple<int64_t, int64_t> check_ring(int64_t D, const Tensor& obs, const Tens
 int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int64_t slot0, const Tensor& state,
                     const Tensor& ep_len, const Tensor& ep_ret, const Tensor& obs, const Tensor& nobs,
                     const Tensor& act, const Tensor& rew, const Tensor& done, const Tensor& ep_stats, int64_t seed,
-                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling, int64_t quantiles) {
+                    int64_t step0, double epsilon, bool reset_all, int64_t max_steps, bool dueling, int64_t quantiles,
+                    int64_t atoms, double v_min, double v_max) {
   int D = 0, A = 0, NS = 0, ms = 0;
   TORCH_CHECK(rrl_env_dims((int)env, &D, &A, &NS, &ms) == 0, "unknown device env id ", env);
   TORCH_CHECK(env != ENV_HALFCHEETAH, "dqn_rollout takes the discrete device envs");
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(T >= 1 && max_steps >= 1, "T and max_steps must be >= 1");
-  const int64_t P = flat_size(D, H, q_outputs(A, dueling, quantiles));
+  const int64_t P = flat_size(D, H, atoms != 0 ? c51_outputs(A, atoms, v_min, v_max, dueling, quantiles)
+                                               : q_outputs(A, dueling, quantiles));
   check(params, "params", at::kFloat, P);
   TORCH_CHECK(quantiles == 0 || params.numel() == P, "params is not the quantile net MLPSpec(D, H, A * quantiles)");
+  TORCH_CHECK(atoms == 0 || params.numel() == P, "params is not the categorical net MLPSpec(D, H, A * atoms)");
   auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
   check(state, "state", at::kFloat, N * NS);
   check(ep_len, "ep_len", at::kInt, N);
@@ -57,7 +60,8 @@ int64_t dqn_rollout(int64_t env, const Tensor& params, int64_t H, int64_t T, int
                                  obs.data_ptr<float>(), nobs.data_ptr<float>(), act.data_ptr<int>(),
                                  rew.data_ptr<float>(), done.data_ptr<float>(), ep_stats.data_ptr<float>(),
                                  (uint64_t)seed, (uint64_t)step0, (float)epsilon, reset_all ? 1 : 0, (int)max_steps,
-                                 dueling ? 1 : 0, (int)quantiles, grid_cus(), cur_stream());
+                                 dueling ? 1 : 0, (int)quantiles, (int)atoms, (float)v_min, (float)v_max, grid_cus(),
+                                 cur_stream());
   if (rc == -4) return rc;
   check_rc(rc, "dqn_rollout");
   return 0;
@@ -111,21 +115,26 @@ void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A,
                  const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
                  int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
                  const OptT& idx, const OptT& tree, std::optional<double> beta, const OptT& w, const OptT& wmax,
-                 int64_t n_step, std::optional<int64_t> newest, const OptT& last, bool dueling, int64_t quantiles) {
+                 int64_t n_step, std::optional<int64_t> newest, const OptT& last, bool dueling, int64_t quantiles,
+                 int64_t atoms, double v_min, double v_max) {
   TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
   const int64_t D = obs.size(2);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  const int64_t P = flat_size(D, H, q_outputs(A, dueling, quantiles));
-  const int64_t NQ = std::max<int64_t>(quantiles, 1);  // targets per batch row
+  const int64_t P = flat_size(D, H, atoms != 0 ? c51_outputs(A, atoms, v_min, v_max, dueling, quantiles)
+                                               : q_outputs(A, dueling, quantiles));
+  const int64_t NQ = atoms != 0 ? atoms : std::max<int64_t>(quantiles, 1);  // targets per batch row
   auto [C, N] = check_ring(D, obs, nobs, act, rew, done);
   TORCH_CHECK(filled >= 1 && filled <= C * N, "filled must be in [1, C * N], got ", filled);
   check(target, "target", at::kFloat, P);
+  TORCH_CHECK(atoms == 0 || target.numel() == P, "target is not the categorical net MLPSpec(D, H, A * atoms)");
+  TORCH_CHECK(atoms == 0 || !online.has_value() || online->numel() == P,
+              "online is not the categorical net MLPSpec(D, H, A * atoms)");
   const float* on = opt_ptr<const float>(online, "online", at::kFloat, P);
   TORCH_CHECK(!double_q || on != nullptr, "double_q needs the online parameters");
   check(y, "y", at::kFloat);
-  TORCH_CHECK(y.numel() % NQ == 0, "y must hold quantiles = ", NQ, " targets per batch row, has ", y.numel());
+  TORCH_CHECK(y.numel() % NQ == 0, "y must hold quantiles / atoms = ", NQ, " targets per batch row, has ", y.numel());
   const int64_t B = y.numel() / NQ;
   TORCH_CHECK(B >= 1 && B * D < (int64_t)INT32_MAX, "batch size out of range");
   check(Xb, "Xb", at::kFloat, B * D);
@@ -159,6 +168,9 @@ void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A,
   c.double_q = double_q ? 1 : 0;
   c.dueling = dueling ? 1 : 0;
   c.quantiles = (int)quantiles;
+  c.atoms = (int)atoms;
+  c.v_min = (float)v_min;
+  c.v_max = (float)v_max;
   c.sample_key = (uint64_t)sample_key;
   c.update = (uint64_t)update;
   c.Xb = Xb.data_ptr<float>();
@@ -248,11 +260,12 @@ void register_dqn_ops(pybind11::module_& m) {
         py::arg("slot0"), py::arg("state"), py::arg("ep_len"), py::arg("ep_ret"), py::arg("obs"), py::arg("nobs"),
         py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("ep_stats"), py::arg("seed"), py::arg("step0"),
         py::arg("epsilon"), py::arg("reset_all"), py::arg("max_steps"), py::arg("dueling") = false,
-        py::arg("quantiles") = 0);
+        py::arg("quantiles") = 0, py::arg("atoms") = 0, py::arg("v_min") = 0.0, py::arg("v_max") = 0.0);
   m.def("dqn_targets", &dqn_targets, py::arg("online"), py::arg("target"), py::arg("H"), py::arg("A"),
         py::arg("obs"), py::arg("nobs"), py::arg("act"), py::arg("rew"), py::arg("done"), py::arg("filled"),
         py::arg("gamma"), py::arg("double_q"), py::arg("sample_key"), py::arg("update"), py::arg("Xb"),
         py::arg("act_b"), py::arg("y"), py::arg("idx"), py::arg("tree") = py::none(), py::arg("beta") = py::none(),
         py::arg("w") = py::none(), py::arg("wmax") = py::none(), py::arg("n_step") = 1, py::arg("newest") = py::none(),
-        py::arg("last") = py::none(), py::arg("dueling") = false, py::arg("quantiles") = 0);
+        py::arg("last") = py::none(), py::arg("dueling") = false, py::arg("quantiles") = 0, py::arg("atoms") = 0,
+        py::arg("v_min") = 0.0, py::arg("v_max") = 0.0);
 }

@@ -99,7 +99,7 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
               const OptT& act, const OptT& actc, const OptT& adv, const OptT& ret, const OptT& logp_old,
               const OptT& adv_stats, double inv_B, double clip_eps, double ent_coef, const Tensor& grad_slab,
               const Tensor& loss_slab, const OptT& nvalid, const OptT& inv_B_dev, const OptT& row_w,
-              const OptT& w_norm, const OptT& td_abs, int64_t quantiles) {
+              const OptT& w_norm, const OptT& td_abs, int64_t quantiles, int64_t atoms, double v_min, double v_max) {
   check(params, "params", at::kFloat);
   check(X, "X", at::kFloat);
   TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
@@ -107,22 +107,31 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
-  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_QR, "bad head");
+  TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_C51, "bad head");
   const bool gauss = head == HEAD_PPO_GAUSS || head == HEAD_PG_GAUSS;
   const bool cat = head == HEAD_PG_CAT || head == HEAD_PPO_CAT;
   const bool value = head == HEAD_VALUE_MSE;
-  const bool qr = head == HEAD_Q_QR;
-  const bool qhead = head == HEAD_Q_TD || head == HEAD_Q_DUEL || qr;  // reads act + ret; no advantages
+  const bool qr = head == HEAD_Q_QR, c51 = head == HEAD_Q_C51;
+  const bool qhead = head == HEAD_Q_TD || head == HEAD_Q_DUEL || qr || c51;  // reads act + ret; no advantages
+  TORCH_CHECK(c51 == (atoms != 0), "atoms >= 2 goes with the Q_C51 head and no other: head ", head, " got atoms = ",
+              atoms);
   TORCH_CHECK(qr ? quantiles >= 1 : quantiles == 0, "quantiles >= 1 goes with the Q_QR head and no other: head ", head,
               " got quantiles = ", quantiles);
-  const int64_t AO = value ? 1 : q_outputs(A, head == HEAD_Q_DUEL, quantiles);
-  TORCH_CHECK(B * std::max<int64_t>(D, qr ? AO : A) < (int64_t)INT32_MAX, "batch too large for 32-bit row indexing");
+  const int64_t AO = value ? 1
+                     : c51 ? c51_outputs(A, atoms, v_min, v_max, false, quantiles)
+                           : q_outputs(A, head == HEAD_Q_DUEL, quantiles);
+  TORCH_CHECK(B * std::max<int64_t>(D, qr || c51 ? AO : A) < (int64_t)INT32_MAX, "batch too large for 32-bit row indexing");
   const int64_t P = flat_size(D, H, AO, gauss);
   check_numel(params, "params", P);
   if (qr) {
     TORCH_CHECK(B >= 1, "the quantile head needs a batch row");
     TORCH_CHECK(clip_eps > 0.0, "the quantile head needs a Huber threshold > 0, got ", clip_eps);
     TORCH_CHECK(params.numel() == P, "params has ", params.numel(), " floats; MLPSpec(D, H, A * quantiles) has ", P);
+  }
+  if (c51) {
+    TORCH_CHECK(B >= 1, "the categorical head needs a batch row");
+    TORCH_CHECK(D <= 16, "the categorical head takes obs dim <= 16, got ", D);
+    TORCH_CHECK(params.numel() == P, "params has ", params.numel(), " floats; MLPSpec(D, H, A * atoms) has ", P);
   }
   const int64_t nslab = mlp_grad_slabs(B);
   check(grad_slab, "grad_slab", at::kFloat, nslab * P);
@@ -131,6 +140,7 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   c.head = (int)head;
   c.B = (int)B, c.D = (int)D, c.A = (int)A, c.H = (int)H, c.P = (int)P;
   c.quantiles = (int)quantiles;
+  c.atoms = (int)atoms, c.v_min = (float)v_min, c.v_max = (float)v_max;
   c.params = params.data_ptr<float>();
   c.X = X.data_ptr<float>();
   c.mask = opt_ptr<const float>(mask, "mask", at::kFloat, B * A);
@@ -140,7 +150,7 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   if (gauss) TORCH_CHECK(c.actc != nullptr, "actc required for Gaussian heads");
   c.adv = opt_ptr<const float>(adv, "adv", at::kFloat, B);
   if (!value && !qhead) TORCH_CHECK(c.adv != nullptr, "adv required for policy heads");
-  c.ret = opt_ptr<const float>(ret, "ret", at::kFloat, B * std::max<int64_t>(quantiles, 1));
+  c.ret = opt_ptr<const float>(ret, "ret", at::kFloat, B * std::max<int64_t>(c51 ? atoms : quantiles, 1));
   if (value || qhead) TORCH_CHECK(c.ret != nullptr, "ret required for the value and Q heads");
   c.logp_old = opt_ptr<const float>(logp_old, "logp_old", at::kFloat, B);
   if (head == HEAD_PPO_CAT || head == HEAD_PPO_GAUSS)
@@ -457,7 +467,8 @@ EvalShape check_eval_bufs(int64_t D, const Tensor& ep_ret, const Tensor& ep_len,
 // quantiles: params is that Q-network, exactly, and such a net is evaluated greedily.
 void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret, const Tensor& ep_len,
               const Tensor& ep_code, const OptT& tr_obs, const OptT& tr_act, const OptT& tr_rew, const OptT& tr_done,
-              int64_t seed, int64_t step0, bool greedy, int64_t max_steps, bool dueling, int64_t quantiles) {
+              int64_t seed, int64_t step0, bool greedy, int64_t max_steps, bool dueling, int64_t quantiles,
+              int64_t atoms, double v_min, double v_max) {
   auto [D, A, NS, ms] = env_dims(env);
   (void)NS;
   (void)ms;
@@ -465,7 +476,10 @@ void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(!dueling || greedy, "a dueling Q-network is evaluated greedily: softmax-of-Q is not its policy");
   TORCH_CHECK(quantiles <= 0 || greedy, "a quantile Q-network is evaluated greedily: softmax-of-Q is not its policy");
-  check_exact(params, "params", at::kFloat, flat_size(D, H, q_outputs(A, dueling, quantiles)));
+  TORCH_CHECK(atoms == 0 || greedy, "a categorical Q-network is evaluated greedily: softmax-of-Q is not its policy");
+  check_exact(params, "params", at::kFloat,
+              flat_size(D, H, atoms != 0 ? c51_outputs(A, atoms, v_min, v_max, dueling, quantiles)
+                                         : q_outputs(A, dueling, quantiles)));
   const EvalShape sh = check_eval_bufs(D, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done, at::kInt, 0,
                                        max_steps);
   const bool tr = sh.Tc > 0;
@@ -474,7 +488,7 @@ void evaluate(int64_t env, const Tensor& params, int64_t H, const Tensor& ep_ret
                         tr ? tr_obs->data_ptr<float>() : nullptr, tr ? tr_act->data_ptr<int>() : nullptr,
                         tr ? tr_rew->data_ptr<float>() : nullptr, tr ? tr_done->data_ptr<float>() : nullptr,
                         (uint64_t)seed, (uint64_t)step0, greedy ? 1 : 0, (int)max_steps, dueling ? 1 : 0,
-                        (int)quantiles, num_cus(), cur_stream()),
+                        (int)quantiles, (int)atoms, (float)v_min, (float)v_max, num_cus(), cur_stream()),
            "evaluate");
 }
 
@@ -534,7 +548,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("clip_eps"), pybind11::arg("ent_coef"), pybind11::arg("grad_slab"), pybind11::arg("loss_slab"),
         pybind11::arg("nvalid") = pybind11::none(), pybind11::arg("inv_B_dev") = pybind11::none(),
         pybind11::arg("row_w") = pybind11::none(), pybind11::arg("w_norm") = pybind11::none(),
-        pybind11::arg("td_abs") = pybind11::none(), pybind11::arg("quantiles") = 0);
+        pybind11::arg("td_abs") = pybind11::none(), pybind11::arg("quantiles") = 0, pybind11::arg("atoms") = 0,
+        pybind11::arg("v_min") = 0.0, pybind11::arg("v_max") = 0.0);
   m.def("set_value_grad_stamps", [](const Tensor& t) { rrl_set_value_grad_stamps(t.numel() ? t.data_ptr() : nullptr); });
   m.def("set_value_grad_tune", [](int64_t t) { return (int64_t)rrl_set_value_grad_tune((int)t); });
   m.def("set_value_grad_mode", [](int64_t mode) { return (int64_t)rrl_set_value_grad_mode((int)mode); },
@@ -574,7 +589,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"), pybind11::arg("tr_obs"),
         pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"), pybind11::arg("seed"),
         pybind11::arg("step0"), pybind11::arg("greedy"), pybind11::arg("max_steps"),
-        pybind11::arg("dueling") = false, pybind11::arg("quantiles") = 0);
+        pybind11::arg("dueling") = false, pybind11::arg("quantiles") = 0, pybind11::arg("atoms") = 0,
+        pybind11::arg("v_min") = 0.0, pybind11::arg("v_max") = 0.0);
   m.def("evaluate_cont", &evaluate_cont, pybind11::arg("env"), pybind11::arg("params"), pybind11::arg("env_consts"),
         pybind11::arg("H"), pybind11::arg("ep_ret"), pybind11::arg("ep_len"), pybind11::arg("ep_code"),
         pybind11::arg("tr_obs"), pybind11::arg("tr_act"), pybind11::arg("tr_rew"), pybind11::arg("tr_done"),
@@ -585,7 +601,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                        RRL_ENUM(MODE_LOGITS), RRL_ENUM(MODE_GAUSS_SAMPLE), RRL_ENUM(MODE_GAUSS_EVAL));
   m.attr("GRAD_HEADS") = pybind11::dict(RRL_ENUM(HEAD_PG_CAT), RRL_ENUM(HEAD_VALUE_MSE), RRL_ENUM(HEAD_PPO_CAT),
                                         RRL_ENUM(HEAD_PPO_GAUSS), RRL_ENUM(HEAD_PG_GAUSS), RRL_ENUM(HEAD_Q_TD),
-                                        RRL_ENUM(HEAD_Q_DUEL), RRL_ENUM(HEAD_Q_QR));
+                                        RRL_ENUM(HEAD_Q_DUEL), RRL_ENUM(HEAD_Q_QR), RRL_ENUM(HEAD_Q_C51));
   m.attr("ENV_IDS") = pybind11::dict(RRL_ENUM(ENV_CARTPOLE), RRL_ENUM(ENV_MOUNTAINCAR), RRL_ENUM(ENV_ACROBOT),
                                      RRL_ENUM(ENV_LUNARLANDER), RRL_ENUM(ENV_HALFCHEETAH));
 #undef RRL_ENUM

@@ -27,6 +27,7 @@ enum GradHead : int {
   HEAD_Q_TD = 5,       // DQN: loss = mean(huber(Q(x)[act] - ret, delta)); delta travels in clip_eps
   HEAD_Q_DUEL = 6,     // HEAD_Q_TD on a dueling net of A + 1 outputs: Q = out[A] + out[act] - mean(out[0 .. A-1])
   HEAD_Q_QR = 7,       // QR-DQN: quantile-Huber loss on a net of A * NQ outputs (rrl_mlp_grad has the contract)
+  HEAD_Q_C51 = 8,      // C51: cross-entropy to the projected target on a net of A * NA outputs (wide output layer)
 };
 
 enum EnvId : int { ENV_CARTPOLE = 0, ENV_MOUNTAINCAR = 1, ENV_ACROBOT = 2, ENV_LUNARLANDER = 3, ENV_HALFCHEETAH = 4 };
@@ -51,6 +52,8 @@ struct DqnTargetsCall {
   int n_step, N, newest;         // walk: N envs per slot, newest the slot written last
   int* last;                     // [B], may be null; n_step, N, newest, last = 1, 1, 0, nullptr is "no walk"
   int quantiles;                 // 0: the scalar forms above; NQ >= 1: nets MLPSpec(D, H, A * NQ) and y [B][NQ]
+  int atoms;                     // 0, or NA >= 2: categorical nets MLPSpec(D, H, A * NA) and y [B][NA]
+  float v_min, v_max;            // the support of the atoms: z_i = v_min + i * (v_max - v_min) / (NA - 1)
 };
 
 // The arguments of rrl_mlp_grad, which has the contract.
@@ -69,6 +72,8 @@ struct MlpGradCall {
   const float* inv_B_dev;
   const float *row_w, *w_norm;   // prioritised replay: [B], [1], both or neither
   float* td_abs;                 // [B], may be null
+  int atoms;                     // NA >= 2 with HEAD_Q_C51 (ret is then m [B][NA]), 0 with every other head
+  float v_min, v_max;            // the support of the atoms, as DqnTargetsCall
 };
 
 }  // namespace rrl
@@ -108,6 +113,16 @@ int rrl_set_value_fwd_mode(int mode);
 //                   of the action's quantiles), [5] += 1.  act[row] is clamped into [0, A) (it indexes the output
 //                   registers): an out-of-range action of a valid row trains action 0 or A - 1, where HEAD_Q_TD would
 //                   give the row no gradient.
+//   HEAD_Q_C51      act, ret (the projected target distribution m [B][NA] of rrl_dqn_targets, NA = atoms); v_min,
+//                   v_max.  The categorical head (Bellemare et al. 2017) on the wide output layer: params / P / the
+//                   slabs are those of MLPSpec(D, H, A * NA), output a * NA + i the logit of atom i of action a,
+//                   p = softmax of the block of act (clamped into [0, A)), loss_row = -sum_i m_i log p_i and
+//                   dout[act block] = inv_B * w * (p - m), every other output 0.  Loss slab: [0] += w * loss_row,
+//                   [4] += Q(act) = sum_i z_i p_i, [5] += 1; td_abs[row] = loss_row.  Refusals, in this order:
+//                   -1 atoms == 0 (or atoms != 0 with another head), a null params, X, act, ret or slab, row_w
+//                   without w_norm or the reverse; -2 A < 1, D outside [1, 16] or B < 1; -3 H not 64 / 128,
+//                   quantiles != 0, atoms < 2, v_max <= v_min, atoms > 64 or A * ceil(atoms / 16) > 8; -2 P not that
+//                   of the net.
 // nvalid / inv_B_dev (each may be null): the batch shape read from device memory; rows >= *nvalid are inert and
 // *inv_B_dev replaces inv_B.  row_w / w_norm / td_abs (the three Q heads, each may be null): the row's weight is
 // w = row_w[row] / *w_norm (else 1) in the loss and the gradient, and td_abs[row] of every valid row receives
@@ -190,7 +205,8 @@ int rrl_rollout_cont(int env, const float* params, const float* env_consts, int 
 // with quantiles < 0, with dueling != 0 as well, or with A * NQ > 16
 int rrl_evaluate(int env, const float* params, int N, int E, int Tc, int H, float* ep_ret, int* ep_len,
                  int* ep_code, float* tr_obs, int* tr_act, float* tr_rew, float* tr_done, uint64_t seed,
-                 uint64_t step0, int greedy, int max_steps, int dueling, int quantiles, int num_cu, void* stream);
+                 uint64_t step0, int greedy, int max_steps, int dueling, int quantiles, int atoms, float v_min,
+                 float v_max, int num_cu, void* stream);
 // continuous-action envs (ENV_HALFCHEETAH); tr_act is [Tc][N][A]
 int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int N, int E, int Tc, int H,
                       float* ep_ret, int* ep_len, int* ep_code, float* tr_obs, float* tr_act, float* tr_rew,
@@ -207,12 +223,18 @@ int rrl_evaluate_cont(int env, const float* params, const float* env_consts, int
 // outputs (HEAD_Q_DUEL) and the greedy action is the lowest-index argmax of its A advantage outputs.
 // quantiles = NQ >= 1: params is a quantile Q-network of A * NQ outputs (HEAD_Q_QR) and the greedy action is the
 // lowest-index argmax of the per-action quantile sums; the draws, the ring and the statistics do not depend on
-// it.  -3 (nothing written) with quantiles < 0, with dueling != 0 as well, or with A * NQ > 16
+// it.  -3 (nothing written) with quantiles < 0, with dueling != 0 as well, or with A * NQ > 16.
+// atoms = NA >= 2 (rrl_dqn_rollout, rrl_evaluate, rrl_dqn_targets): params is a categorical Q-network of A * NA
+// outputs on the wide output layer (wide.h), z_i = v_min + i * (v_max - v_min) / (NA - 1), and the greedy action is
+// the lowest-index argmax of Q(a) = sum_i z_i softmax(out[a * NA ..])[i]; rrl_dqn_targets then writes y [B][NA], the
+// projection of the target net's distribution of a* through G + disc * boot * z_j (wide.h: c51_project).  -3
+// (nothing written) with atoms < 0, atoms == 1, dueling or quantiles as well, v_max <= v_min, NA > 64 or
+// A * ceil(NA / 16) > 8, and in rrl_evaluate with greedy == 0
 int rrl_dqn_rollout_grid(int N, int num_cu);
 int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, int slot0, float* state, int* ep_len,
                     float* ep_ret, float* obs, float* nobs, int* act, float* rew, float* done, float* ep_stats,
                     uint64_t seed, uint64_t step0, float epsilon, int reset_all, int max_steps, int dueling,
-                    int quantiles, int num_cu, void* stream);
+                    int quantiles, int atoms, float v_min, float v_max, int num_cu, void* stream);
 // The TD targets of one update.  Batch row b samples ring row r0, gathers obs[r0] -> Xb[b], act[r0] -> act_b[b],
 // r0 -> idx[b], walks to the row `last` (last[b] <- last) and writes, a* being the lowest-index argmax of
 // Q_target(nobs[last], .) (double_q = 0) or of Q_online (double_q = 1),

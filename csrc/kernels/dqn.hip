@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "actor_step.h"
+#include "wide.h"
 
 namespace rrl {
 
@@ -52,22 +53,34 @@ struct DqnRolloutQrArgs : DqnRolloutArgs {
   int NQ = 1;  // quantiles per action, Env::A * NQ <= kMaxAct
 };
 
+// The categorical instances (TPA > 0) take the support behind the block: Env::A * sup.NA outputs, TPA tiles each.
+struct DqnRolloutC51Args : DqnRolloutArgs {
+  C51Support sup;
+};
+
+template <bool QR, int TPA>
+using DqnRolloutArgsOf =
+    std::conditional_t<(TPA > 0), DqnRolloutC51Args, std::conditional_t<QR, DqnRolloutQrArgs, DqnRolloutArgs>>;
+
 // DUEL = true: the dueling Q-network (heads.h), Env::A + 1 outputs staged and evaluated; the greedy action
 // is the argmax of the A advantage outputs.  The draws, the ring writes and the episode slots do not change.
 // QR = true: the quantile Q-network, Env::A * p.NQ outputs; the greedy action is the argmax of the quantile sums.
-template <class Env, int HT, bool DUEL = false, bool QR = false>
-__global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(
-    std::conditional_t<QR, DqnRolloutQrArgs, DqnRolloutArgs> p) {
+// TPA > 0: the categorical Q-network on the wide output layer (wide.h), Env::A * p.sup.NA outputs; the greedy action
+// is the argmax of the per-action expectations.
+template <class Env, int HT, bool DUEL = false, bool QR = false, int TPA = 0>
+__global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(DqnRolloutArgsOf<QR, TPA> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = 1;
   constexpr int D = Env::D, A = Env::A;
   static_assert(!(DUEL && QR), "quantiles with the dueling head are not built");
+  static_assert(TPA == 0 || !(DUEL || QR), "atoms with the dueling or the quantile head are not built");
   int AO = A + (DUEL ? 1 : 0);  // outputs of the net
   if constexpr (QR) AO = A * p.NQ;
   static_assert(D <= 16, "device envs use one input tile");
   static_assert(Env::A + 1 <= kMaxAct, "the dueling net has one output more than actions");
   const TileCtx c = tile_ctx(p);
-  stage_net<DT, HT>(lds, p.params, D, AO, false);
+  if constexpr (TPA > 0) stage_wide<HT>(lds, p.params, D, A, p.sup.NA, TPA);
+  else stage_net<DT, HT>(lds, p.params, D, AO, false);
   __syncthreads();
 
   EpStats st;
@@ -82,12 +95,20 @@ __global__ __launch_bounds__(256, 2) void dqn_rollout_kernel(
       pack_obs<Env, DT>(e.s, c.g, x);
       if (e.valid) store_obs_row<D, DT>(p.obs + base * D, c.g, x);
       float q[kMaxAct];
-      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), AO, q);
+      int a_wide = 0;
+      if constexpr (TPA > 0) {
+        floatx4 h2[HT];
+        wide_trunk<HT>(lds, x, input_kr_last(D, DT), h2);
+        a_wide = c51_greedy<HT, TPA>(lds, A, p.sup, h2, &q[0]);
+      } else {
+        policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), AO, q);
+      }
       const uint4 rnd = step_draw(e.envc, gstep, c.key);
       const bool explore = u01(rnd.z) < p.epsilon;
       const int a_rand = min(A - 1, (int)floorf(u01(rnd.w) * (float)A));
       int a;
-      if constexpr (QR) a = explore ? a_rand : quantile_argmax(A, p.NQ, q);
+      if constexpr (TPA > 0) a = explore ? a_rand : a_wide;
+      else if constexpr (QR) a = explore ? a_rand : quantile_argmax(A, p.NQ, q);
       else a = explore ? a_rand : argmax_first(A, q);
 
       bool term;
@@ -172,14 +193,39 @@ struct DqnQrArgs : Base {
   int NQ = 1;
 };
 
-template <bool NSTEP, bool QR>
+// The categorical instances (TPA > 0) add the support: y is [B][sup.NA].
+template <class Base>
+struct DqnC51Args : Base {
+  C51Support sup;
+};
+
+template <bool NSTEP, bool QR, int TPA = 0>
 using DqnTargetArgsOf = std::conditional_t<
-    QR, DqnQrArgs<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>,
-    std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>;
+    (TPA > 0), DqnC51Args<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>,
+    std::conditional_t<QR, DqnQrArgs<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>,
+                       std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>>;
 
 RRL_DEV uint32_t dqn_sample_row(int b, const DqnTargetArgs& p) {
   const uint4 r = philox4x32(make_uint4((uint32_t)b, p.upd_lo, p.upd_hi, 0u), make_uint2(p.key_lo, p.key_hi));
   return (uint32_t)(((uint64_t)r.x * (uint64_t)p.filled) >> 32);
+}
+
+// The categorical net's greedy action (or `pick`) at ring row r, its expectation in q[0] and, where keep is given,
+// the probabilities of that action (c51_greedy).
+template <int HT, int TPA>
+RRL_DEV int dqn_c51_greedy(const float* __restrict__ lds, const float* __restrict__ nobs, size_t r, bool ok, int D,
+                           int A, const C51Support& sup, float (&q)[kMaxAct], floatx4 (*keep)[TPA] = nullptr,
+                           int pick = -1) {
+  const int g = lane_id() >> 4;
+  floatx4 x[1], h2[HT];
+  const float* row = nobs + r * (size_t)D;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int f = 4 * k + g;
+    x[0][k] = (ok && f < D) ? row[f] : 0.f;
+  }
+  wide_trunk<HT>(lds, x, (D + 3) >> 2, h2);
+  return c51_greedy<HT, TPA>(lds, A, sup, h2, &q[0], keep, pick);
 }
 
 template <int HT>
@@ -263,10 +309,16 @@ RRL_DEV uint32_t dqn_nstep_last(uint32_t r0, uint32_t m1, const DqnNStepArgs& p)
 // QR = true: both nets are quantile nets (heads.h) with p.A * p.NQ outputs and y is [B][NQ]; a* is the argmax of
 // the selecting net's quantile sums, parked in y[b * NQ], and row b receives the NQ quantiles of the target
 // net at a*, each through the expression of the scalar kernel.  Everything but y is that of QR = false.
-template <int HT, bool PER, bool NSTEP = false, bool DUEL = false, bool QR = false>
-__global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgsOf<NSTEP, QR> p) {
+// TPA > 0: both nets are categorical nets on the wide output layer (wide.h) with p.A * NA outputs, NA = p.sup.NA, and
+// y is m [B][NA]: a* is the argmax of the selecting net's expectations, parked in y[b * NA] and clamped as for QR, and
+// row b receives the projection (c51_project) of the target net's distribution of a* at nobs[last] through
+// Tz_j = G + disc * boot * z_j.  All four lane groups of a row take part (each owns a quarter of the atoms), so what
+// lane group 0 parked or read (a*, G) reaches the others by a lane broadcast.  Everything but y is that of TPA = 0.
+template <int HT, bool PER, bool NSTEP = false, bool DUEL = false, bool QR = false, int TPA = 0>
+__global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgsOf<NSTEP, QR, TPA> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   static_assert(!(DUEL && QR), "quantiles with the dueling head are not built");
+  static_assert(TPA == 0 || !(DUEL || QR), "atoms with the dueling or the quantile head are not built");
   const int l = lane_id();
   const int j = l & 15, g = l >> 4;
   const int wave = threadIdx.x >> 6;
@@ -276,35 +328,42 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgsOf<NST
     NQ = p.NQ;
     AO = p.A * NQ;
   }
+  if constexpr (TPA > 0) NQ = p.sup.NA;
 
   if (p.double_q) {
-    stage_net<1, HT>(lds, p.online, p.D, AO, false);
+    if constexpr (TPA > 0) stage_wide<HT>(lds, p.online, p.D, p.A, p.sup.NA, TPA);
+    else stage_net<1, HT>(lds, p.online, p.D, AO, false);
     __syncthreads();
     for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
       const int b = base + 16 * wave + j;
       const bool ok = b < p.B;
       const size_t r = ok ? (PER ? per_sample_row(b, p) : dqn_sample_row(b, p)) : 0;
       float q[kMaxAct];
+      int a_wide = 0;
       if constexpr (NSTEP) {
         NStepWalk w{0u, 0.f, 0.f, 1};
         if (ok) w = dqn_nstep_walk((uint32_t)r, p);
-        dqn_q_values<HT>(lds, p.nobs, w.last, ok, p.D, AO, q);
+        if constexpr (TPA > 0) a_wide = dqn_c51_greedy<HT, TPA>(lds, p.nobs, w.last, ok, p.D, p.A, p.sup, q);
+        else dqn_q_values<HT>(lds, p.nobs, w.last, ok, p.D, AO, q);
         if (ok && g == 0) {
           p.act_b[b] = w.m - 1;
           p.Xb[(size_t)b * p.D] = w.G;
         }
       } else {
-        dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, AO, q);
+        if constexpr (TPA > 0) a_wide = dqn_c51_greedy<HT, TPA>(lds, p.nobs, r, ok, p.D, p.A, p.sup, q);
+        else dqn_q_values<HT>(lds, p.nobs, r, ok, p.D, AO, q);
       }
       if (ok && g == 0) {
-        if constexpr (QR) p.y[(size_t)b * NQ] = __int_as_float(quantile_argmax(p.A, NQ, q));
+        if constexpr (TPA > 0) p.y[(size_t)b * NQ] = __int_as_float(a_wide);
+        else if constexpr (QR) p.y[(size_t)b * NQ] = __int_as_float(quantile_argmax(p.A, NQ, q));
         else p.y[b] = __int_as_float(argmax_first(p.A, q));
         if (PER) p.idx[b] = (int)r;
       }
     }
     __syncthreads();  // every wave is done with the online image
   }
-  stage_net<1, HT>(lds, p.target, p.D, AO, false);
+  if constexpr (TPA > 0) stage_wide<HT>(lds, p.target, p.D, p.A, p.sup.NA, TPA);
+  else stage_net<1, HT>(lds, p.target, p.D, AO, false);
   __syncthreads();
   for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
     const int b = base + 16 * wave + j;
@@ -331,11 +390,41 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgsOf<NST
         }
       }
     }
-    dqn_q_values<HT>(lds, p.nobs, last, ok, p.D, AO, q);
+    if constexpr (TPA > 0) {
+      // every lane of the wave runs this (MFMAs and lane broadcasts); rows past B compute on ring row 0 and store nothing
+      if constexpr (!NSTEP) G = p.rew[r];
+      else G = __shfl(G, j, 64);  // with double_q lane group 0 read it back
+      int pick = -1;
+      if (p.double_q) {
+        int parked = 0;
+        if (ok && g == 0) parked = min(max(__float_as_int(p.y[(size_t)b * NQ]), 0), p.A - 1);
+        pick = __shfl(parked, j, 64);
+      }
+      floatx4 pr[TPA], m[TPA];
+      dqn_c51_greedy<HT, TPA>(lds, p.nobs, last, ok, p.D, p.A, p.sup, q, &pr, pick);
+      const float boot = (p.done[last] == 1.f) ? 0.f : 1.f;
+      c51_project<TPA>(p.sup, G, disc * boot, pr, m);
+      if (ok) {
+#pragma unroll
+        for (int t = 0; t < TPA; ++t) {
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const int i = 16 * t + 4 * g + rr;
+            if (i < NQ) p.y[(size_t)b * NQ + i] = m[t][rr];
+          }
+        }
+      }
+    } else {
+      dqn_q_values<HT>(lds, p.nobs, last, ok, p.D, AO, q);
+    }
     if (ok) {
       for (int f = g; f < p.D; f += 4) p.Xb[(size_t)b * p.D + f] = p.obs[r * p.D + f];
       if (g == 0) {
-        if constexpr (QR) {
+        if constexpr (TPA > 0) {
+          if constexpr (NSTEP) {
+            if (p.last != nullptr) p.last[b] = (int)last;
+          }
+        } else if constexpr (QR) {
           const float boot = (p.done[last] == 1.f) ? 0.f : 1.f;
           // the parked a* comes back from memory: the clamp keeps the quantile index inside the 16 outputs
           const int astar = p.double_q ? min(max(__float_as_int(p.y[(size_t)b * NQ]), 0), p.A - 1)
@@ -406,14 +495,30 @@ static int launch_dqn_rollout(std::conditional_t<QR, DqnRolloutQrArgs, DqnRollou
   return (int)hipGetLastError();
 }
 
+// The categorical instance of (Env, HT, TPA): the block with the support behind it and the wide LDS image.
+template <class Env, int HT, int TPA>
+static int launch_c51_rollout(DqnRolloutC51Args a, int slot0, int grid, hipStream_t s) {
+  raise_lds_limit<dqn_rollout_kernel<Env, HT, false, false, TPA>>();
+  const size_t off = (size_t)slot0 * a.N;
+  a.obs += off * Env::D;
+  a.nobs += off * Env::D;
+  a.act += off;
+  a.rew += off;
+  a.done += off;
+  const size_t bytes = (size_t)LdsWide<HT>::floats(Env::A * TPA) * sizeof(float);
+  hipLaunchKernelGGL((dqn_rollout_kernel<Env, HT, false, false, TPA>), dim3(grid), dim3(256), bytes, s, a);
+  return (int)hipGetLastError();
+}
+
 extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, int slot0, float* state,
                                int* ep_len, float* ep_ret, float* obs, float* nobs, int* act, float* rew,
                                float* done, float* ep_stats, uint64_t seed, uint64_t step0, float epsilon,
-                               int reset_all, int max_steps, int dueling, int quantiles, int num_cu,
-                               void* stream) {
+                               int reset_all, int max_steps, int dueling, int quantiles, int atoms, float v_min,
+                               float v_max, int num_cu, void* stream) {
   if (!params || !state || !ep_len || !ep_ret || !obs || !nobs || !act || !rew || !done || !ep_stats) return -1;
   if (N <= 0 || T <= 0 || C <= 0 || max_steps < 1) return -2;
   if (quantiles < 0 || (quantiles > 0 && dueling)) return -3;
+  if (atoms < 0 || (atoms > 0 && (dueling || quantiles > 0))) return -3;
   if (slot0 < 0 || C % T != 0 || slot0 % T != 0 || (long long)slot0 + T > C) return -4;
   DqnRolloutArgs a{params, N, T, state, ep_len, ep_ret, obs, nobs, act, rew, done, ep_stats,
                    (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step0, (uint32_t)(step0 >> 32), epsilon,
@@ -421,6 +526,15 @@ extern "C" int rrl_dqn_rollout(int env, const float* params, int N, int T, int H
   const int grid = rrl_dqn_rollout_grid(N, num_cu);
   return dispatch_env_h(env, H, [&](auto k) {
     using K = decltype(k);
+    if (atoms > 0) {
+      using Env = typename K::Env;
+      DqnRolloutC51Args ac;
+      static_cast<DqnRolloutArgs&>(ac) = a;
+      const int tpa = c51_support(Env::A, atoms, v_min, v_max, &ac.sup);
+      return dispatch_tpa<(Env::A <= 2 ? 4 : kMaxWideTiles / Env::A)>(tpa, [&](auto w) {
+        return launch_c51_rollout<Env, K::HT, decltype(w)::TPA>(ac, slot0, grid, (hipStream_t)stream);
+      });
+    }
     if (quantiles > 0) {
       DqnRolloutQrArgs aq;
       static_cast<DqnRolloutArgs&>(aq) = a;
@@ -494,6 +608,33 @@ static int dispatch_quantile_targets(const DqnNStepArgs& a, int NQ, int H, bool 
   }
 }
 
+// The categorical instances of (H, PER, NSTEP, TPA): the same blocks with the support behind them.
+template <int HT, bool PER, bool NSTEP, int TPA>
+static int launch_c51_targets(const DqnNStepArgs& a, const C51Support& sup, int grid, hipStream_t s) {
+  DqnTargetArgsOf<NSTEP, false, TPA> q;
+  static_cast<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>&>(q) = a;
+  q.sup = sup;
+  raise_lds_limit<dqn_targets_kernel<HT, PER, NSTEP, false, false, TPA>>();
+  const size_t bytes = (size_t)LdsWide<HT>::floats(a.A * TPA) * sizeof(float);
+  hipLaunchKernelGGL((dqn_targets_kernel<HT, PER, NSTEP, false, false, TPA>), dim3(grid), dim3(256), bytes, s, q);
+  return (int)hipGetLastError();
+}
+
+template <int TPA>
+static int dispatch_c51_targets(const DqnNStepArgs& a, const C51Support& sup, int H, bool per, bool nstep, int grid,
+                                hipStream_t s) {
+  switch ((per ? 4 : 0) | (nstep ? 2 : 0) | (H == 128 ? 1 : 0)) {
+    case 0: return launch_c51_targets<4, false, false, TPA>(a, sup, grid, s);
+    case 1: return launch_c51_targets<8, false, false, TPA>(a, sup, grid, s);
+    case 2: return launch_c51_targets<4, false, true, TPA>(a, sup, grid, s);
+    case 3: return launch_c51_targets<8, false, true, TPA>(a, sup, grid, s);
+    case 4: return launch_c51_targets<4, true, false, TPA>(a, sup, grid, s);
+    case 5: return launch_c51_targets<8, true, false, TPA>(a, sup, grid, s);
+    case 6: return launch_c51_targets<4, true, true, TPA>(a, sup, grid, s);
+    default: return launch_c51_targets<8, true, true, TPA>(a, sup, grid, s);
+  }
+}
+
 static int dqn_targets_grid(int B, int num_cu) {
   int grid = (B + 63) / 64;
   const int cap = num_cu > 0 ? num_cu : 256;
@@ -511,6 +652,13 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
   if ((c->H != 64 && c->H != 128) || c->D < 1 || c->D > 16 || c->A < 1 || c->A + (duel ? 1 : 0) > kMaxAct) return -3;
   const int NQ = c->quantiles;
   if (NQ < 0 || (NQ > 0 && duel) || (long long)c->A * NQ > kMaxAct) return -3;
+  C51Support sup{};
+  int tpa = 0;
+  if (c->atoms != 0) {
+    if (c->atoms < 0 || duel || NQ > 0) return -3;
+    tpa = c51_support(c->A, c->atoms, c->v_min, c->v_max, &sup);
+    if (tpa == 0) return -3;
+  }
   if (c->n_step < 1 || c->N < 1 || c->filled % c->N != 0) return -2;
   if (c->newest < 0 || c->newest >= c->filled / c->N) return -4;
   DqnNStepArgs a;
@@ -536,8 +684,15 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
     if (e != hipSuccess) return (int)e;
   }
   const int grid = dqn_targets_grid(c->B, num_cu);
-  const int rc = NQ > 0 ? dispatch_quantile_targets(a, NQ, c->H, per, nstep, grid, s)
-                        : dispatch_dqn_targets(a, c->H, per, nstep, duel, grid, s);
+  int rc;
+  if (tpa > 0) {
+    rc = dispatch_tpa<kMaxTpa>(tpa, [&](auto w) {
+      return dispatch_c51_targets<decltype(w)::TPA>(a, sup, c->H, per, nstep, grid, s);
+    });
+  } else {
+    rc = NQ > 0 ? dispatch_quantile_targets(a, NQ, c->H, per, nstep, grid, s)
+                : dispatch_dqn_targets(a, c->H, per, nstep, duel, grid, s);
+  }
   if (rc || nstep || !c->last) return rc;
   // the one-step kernel has no walk: its target bootstraps from the sampled row itself
   return (int)hipMemcpyAsync(c->last, c->idx, (size_t)c->B * sizeof(int), hipMemcpyDeviceToDevice, s);

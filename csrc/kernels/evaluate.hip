@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "actor_step.h"
+#include "wide.h"
 
 namespace rrl {
 
@@ -45,6 +46,14 @@ struct EvalQrArgs : EvalArgs {
   int NQ = 1;  // quantiles per action, Env::A * NQ <= kMaxAct
 };
 
+// The categorical instance (TPA > 0) takes the support behind the block.
+struct EvalC51Args : EvalArgs {
+  C51Support sup;
+};
+
+template <bool QR, int TPA>
+using EvalArgsOf = std::conditional_t<(TPA > 0), EvalC51Args, std::conditional_t<QR, EvalQrArgs, EvalArgs>>;
+
 // One lane of an env that finished episode `ep` records it.
 template <class Env>
 RRL_DEV void store_episode(const EvalArgs& p, const EnvSlot<Env>& e, int ep, int code) {
@@ -57,18 +66,22 @@ RRL_DEV void store_episode(const EvalArgs& p, const EnvSlot<Env>& e, int ep, int
 // DUEL = true: a dueling Q-network (heads.h) of Env::A + 1 outputs, scored greedily: the action is the
 // argmax of the A advantage outputs.  The host refuses greedy = 0 for it.
 // QR = true: a quantile Q-network (heads.h) of Env::A * p.NQ outputs, scored greedily on the quantile sums.
-template <class Env, int HT, bool DUEL = false, bool QR = false>
-__global__ __launch_bounds__(256, 2) void evaluate_kernel(std::conditional_t<QR, EvalQrArgs, EvalArgs> p) {
+// TPA > 0: a categorical Q-network on the wide output layer (wide.h) of Env::A * p.sup.NA outputs, scored greedily on
+// the per-action expectations.
+template <class Env, int HT, bool DUEL = false, bool QR = false, int TPA = 0>
+__global__ __launch_bounds__(256, 2) void evaluate_kernel(EvalArgsOf<QR, TPA> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DT = 1;
   constexpr int D = Env::D, A = Env::A;
   static_assert(!(DUEL && QR), "quantiles with the dueling head are not built");
+  static_assert(TPA == 0 || !(DUEL || QR), "atoms with the dueling or the quantile head are not built");
   int AO = A + (DUEL ? 1 : 0);  // outputs of the net
   if constexpr (QR) AO = A * p.NQ;
   static_assert(D <= 16, "device envs use one input tile");
   static_assert(Env::A + 1 <= kMaxAct, "the dueling net has one output more than actions");
   const TileCtx c = tile_ctx(p);
-  stage_net<DT, HT>(lds, p.params, D, AO, false);
+  if constexpr (TPA > 0) stage_wide<HT>(lds, p.params, D, A, p.sup.NA, TPA);
+  else stage_net<DT, HT>(lds, p.params, D, AO, false);
   __syncthreads();
 
   const int tmax = p.E * p.max_steps;  // < 2^31: checked by the host entry point
@@ -90,10 +103,19 @@ __global__ __launch_bounds__(256, 2) void evaluate_kernel(std::conditional_t<QR,
       pack_obs<Env, DT>(e.s, c.g, x);
       if (tr) store_obs_row<D, DT>(p.tr_obs + base * D, c.g, x);
       float logits[kMaxAct];
-      policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), AO, logits);
+      int a_wide = 0;
+      if constexpr (TPA > 0) {
+        floatx4 h2[HT];
+        wide_trunk<HT>(lds, x, input_kr_last(D, DT), h2);
+        a_wide = c51_greedy<HT, TPA>(lds, A, p.sup, h2, &logits[0]);
+      } else {
+        policy_forward<DT, HT>(lds, x, input_kr_last(D, DT), AO, logits);
+      }
       const uint4 rnd = step_draw(e.envc, gstep, c.key);
       int a;
-      if constexpr (QR) {
+      if constexpr (TPA > 0) {
+        a = a_wide;
+      } else if constexpr (QR) {
         a = quantile_argmax(A, p.NQ, logits);
       } else if (DUEL || p.greedy) {
         a = argmax_first(A, logits);
@@ -232,6 +254,16 @@ int launch_evaluate(const std::conditional_t<QR, EvalQrArgs, EvalArgs>& a, int n
   return (int)hipGetLastError();
 }
 
+template <class Env, int HT, int TPA>
+int launch_evaluate_c51(const EvalC51Args& a, int num_cu, hipStream_t s) {
+  raise_lds_limit<evaluate_kernel<Env, HT, false, false, TPA>>();
+  int grid, block;
+  eval_geometry(a.N, num_cu, &grid, &block);
+  const size_t bytes = (size_t)LdsWide<HT>::floats(Env::A * TPA) * sizeof(float);
+  hipLaunchKernelGGL((evaluate_kernel<Env, HT, false, false, TPA>), dim3(grid), dim3(block), bytes, s, a);
+  return (int)hipGetLastError();
+}
+
 template <class Env, int HT>
 int launch_evaluate_cont(const EvalArgs& a, int num_cu, hipStream_t s) {
   constexpr int DT = (Env::D + 15) / 16;
@@ -248,16 +280,26 @@ int launch_evaluate_cont(const EvalArgs& a, int num_cu, hipStream_t s) {
 
 extern "C" int rrl_evaluate(int env, const float* params, int N, int E, int Tc, int H, float* ep_ret, int* ep_len,
                             int* ep_code, float* tr_obs, int* tr_act, float* tr_rew, float* tr_done, uint64_t seed,
-                            uint64_t step0, int greedy, int max_steps, int dueling, int quantiles, int num_cu,
-                            void* stream) {
+                            uint64_t step0, int greedy, int max_steps, int dueling, int quantiles, int atoms,
+                            float v_min, float v_max, int num_cu, void* stream) {
   if (const int bad = eval_args_bad(N, E, Tc, max_steps, tr_obs, tr_act, tr_rew, tr_done)) return bad;
-  if ((dueling || quantiles) && !greedy) return -3;  // softmax-of-Q is not a DQN policy
+  if ((dueling || quantiles || atoms) && !greedy) return -3;  // softmax-of-Q is not a DQN policy
   if (quantiles < 0 || (quantiles > 0 && dueling)) return -3;
+  if (atoms < 0 || (atoms > 0 && (dueling || quantiles > 0))) return -3;
   EvalArgs a{params, nullptr, N, E, Tc, ep_ret, ep_len, ep_code, tr_obs, tr_act, tr_rew, tr_done,
              (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step0, (uint32_t)(step0 >> 32), greedy ? 1 : 0,
              max_steps};
   return dispatch_env_h(env, H, [&](auto k) {
     using K = decltype(k);
+    if (atoms > 0) {
+      using Env = typename K::Env;
+      EvalC51Args ac;
+      static_cast<EvalArgs&>(ac) = a;
+      const int tpa = c51_support(Env::A, atoms, v_min, v_max, &ac.sup);
+      return dispatch_tpa<(Env::A <= 2 ? 4 : kMaxWideTiles / Env::A)>(tpa, [&](auto w) {
+        return launch_evaluate_c51<Env, K::HT, decltype(w)::TPA>(ac, num_cu, (hipStream_t)stream);
+      });
+    }
     if (quantiles > 0) {
       EvalQrArgs aq;
       static_cast<EvalArgs&>(aq) = a;

@@ -24,10 +24,18 @@
 #include "common.h"
 #include "heads.h"
 #include "grad_args.h"
+#include "actor_step.h"  // raise_lds_limit
+#include "wide.h"
 
 namespace rrl {
 
 constexpr int kStageLd = 68;  // [feature][64 batch + 4 pad]
+
+// The categorical head's block (HEAD_Q_C51): GradQrArgs with qtarget the projected distribution m [B][NA] (NQ is
+// not read) and the support behind it, so that every other instance keeps its block.
+struct GradC51Args : GradQrArgs {
+  C51Support sup;
+};
 
 // The argument block of a head: the quantile head's carries qtarget and NQ behind GradArgs, every other head's is
 // GradArgs itself.
@@ -538,6 +546,251 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgsOf<HEAD> p) {
   }
 }
 
+// ------------------------------------------------------------------ HEAD_Q_C51 on the wide output layer (wide.h)
+// din += W^T dout over the NO tiles of one action's block of the padded W3 (dense_bwd_data without the clear and
+// the mask, so that the actions accumulate into one dh2).
+template <int NI, int NO>
+RRL_DEV void dense_bwd_acc(const float* __restrict__ W, int S, const floatx4 (&dout)[NO], floatx4 (&din)[NI]) {
+  const int l = lane_id();
+  const int i = l & 15, g = l >> 4;
+#pragma unroll
+  for (int to = 0; to < NO; ++to) {
+    float wc[4][NI];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int ti = 0; ti < NI; ++ti) wc[r][ti] = W[(16 * to + 4 * g + r) * S + i + 16 * ti];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int ti = 0; ti < NI; ++ti) din[ti] = mfma4(wc[r][ti], dout[to][r], din[ti]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// The categorical instance.  The net is MLPSpec(D, H, A * NA), D <= 16; p.qtarget is the projected target m [B][NA]
+// of dqn_targets and loss_row = -sum_i m_i log p(act, i), dout[act block] = invB * w * (p - m).
+//
+// LDS: the trunk of LdsNet<1, HT>, b3 padded [16 * OT], then the two staging images of SR = max(H, 16 * OT) rows.
+// The padded W3 (16 * OT rows of H + 4 floats, at most 2 * SR * 68) LIVES IN THE STAGING AREA from the top of a
+// slab until dh2 is formed; phase A then overwrites it and the next slab stages it again behind the "phase-C
+// readers are done" barrier.  At the DQN batch a workgroup runs one slab, so that is one staging, as a resident
+// image would cost; at H = 128 with 8 tiles a resident image does not fit (147,072 + 69,632 B).
+//
+// Head, one action at a time (wave-uniform, a ascending): the action's TPA logit tiles by MFMA, softmax and
+// expectation (wide.h), and the lanes whose row took that action keep d = scale * (p - m) in 4 * TPA registers.
+// dh2 accumulates W3[a]^T (d where act == a, else 0) by MFMA over the actions, so only one action's tiles are live.
+// dW3 / db3: h2 and the OT dout tiles (d under the row's action, 0 elsewhere) go through the staging images into
+// wgrad<1, HT / 4>, every wave taking all OT output tiles of its quarter of the columns; the epilogue un-pads.
+template <int HT, int TPA>
+__global__ __launch_bounds__(256, 1) void mlp_grad_c51_kernel(GradC51Args p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  using L = LdsNet<1, HT>;
+  using LW = LdsWide<HT>;
+  constexpr int H = L::H;
+  constexpr int TO = HT / 4;
+  constexpr int TI3 = HT / 4;
+  constexpr int OTM = TPA == 3 ? 6 : kMaxWideTiles;  // output tiles an instance can meet
+  const int A = p.A, NA = p.sup.NA, OT = A * TPA;
+  const int SR = max(H, 16 * OT);
+  float* b3 = lds + L::fixed_floats();   // [16 * OT]
+  float* st0 = b3 + 16 * OT;             // [SR][68]
+  float* st1 = st0 + SR * kStageLd;      // [SR][68]
+  float* w3 = st0;                       // [16 * OT][H + 4] while the head runs
+
+  stage_net<1, HT>(lds, p.params, p.D, 0, false);
+  stage_wide_w3<HT>(w3, b3, p.params, p.D, A, NA, TPA);
+
+  const int l = lane_id();
+  const int j = l & 15, g = l >> 4;
+  const int wave = threadIdx.x >> 6;
+
+  floatx4 acc2[TO][HT], acc1[TO][1], acc3[OTM][1][TI3];
+  float bacc2[TO], bacc1[TO], bacc3[OTM][1];
+#pragma unroll
+  for (int a = 0; a < TO; ++a) {
+    bacc2[a] = 0.f;
+    bacc1[a] = 0.f;
+    acc1[a][0] = zero4();
+#pragma unroll
+    for (int b = 0; b < HT; ++b) acc2[a][b] = zero4();
+  }
+#pragma unroll
+  for (int a = 0; a < OTM; ++a) {
+    bacc3[a][0] = 0.f;
+#pragma unroll
+    for (int b = 0; b < TI3; ++b) acc3[a][0][b] = zero4();
+  }
+  float s_loss = 0.f, s_val = 0.f, s_cnt = 0.f;
+  const int kr1 = input_kr_last(p.D, 1);
+  const int Bv = p.nvalid ? min(*p.nvalid, p.B) : p.B;
+  const float invB = p.inv_B_dev ? *p.inv_B_dev : p.inv_B;
+  bool staged = true;  // the first slab's W3 came with the net
+
+  for (int base = blockIdx.x * 64; base < Bv; base += gridDim.x * 64) {
+    __syncthreads();  // the net is staged / the previous slab's phase-C readers are done with st0, st1
+    if (!staged) {
+      stage_wide_w3<HT>(w3, nullptr, p.params, p.D, A, NA, TPA);
+      __syncthreads();
+    }
+    staged = false;
+    const int row0 = base + 16 * wave;
+    const int nrows = max(0, min(16, Bv - row0));
+    const bool valid = j < nrows;
+    const int row = row0 + j;
+
+    floatx4 x[1], h1[HT], h2[HT];
+    load_x_tile<1>(p.X, p.D, p.D, row0, nrows, x);
+    dense_fwd<1, HT, true>(lds + L::W1, L::S1, lds + L::B1, x, h1, kr1);
+    dense_fwd<HT, HT, true>(lds + L::W2, L::S2, lds + L::B2, h1, h2);
+
+    // ------------------------------------------------------------ head, dout and dh2, one action at a time
+    const int act = valid ? min(max(p.act[row], 0), A - 1) : 0;
+    float wi = 1.f;
+    if (p.row_w != nullptr) wi = valid ? p.row_w[row] / *p.w_norm : 0.f;
+    const float scale = (valid ? invB : 0.f) * wi;
+    const float* mrow = p.qtarget + (size_t)(valid ? row : 0) * NA;
+    floatx4 d[TPA], dh2[HT];
+#pragma unroll
+    for (int t = 0; t < TPA; ++t) d[t] = zero4();
+#pragma unroll
+    for (int t = 0; t < HT; ++t) dh2[t] = zero4();
+    float loss_row = 0.f, q_act = 0.f;
+    for (int a = 0; a < A; ++a) {
+      const float* w3a = w3 + 16 * TPA * a * LW::S3;
+      floatx4 lg[TPA], da[TPA];
+      wide_logits_at<HT, TPA>(w3a, b3 + 16 * TPA * a, NA, h2, lg);
+      const bool mine = act == a;
+      // sum_i m_i and sum_i m_i logit_i of this lane's atoms: loss_row = lse * sum m - sum m logit
+      float ms = 0.f, ml = 0.f;
+#pragma unroll
+      for (int t = 0; t < TPA; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = 16 * t + 4 * g + r;
+          const float m = (valid && mine && i < NA) ? mrow[i] : 0.f;
+          da[t][r] = m;
+          ms += m;
+          if (i < NA) ml = fmaf(m, lg[t][r], ml);
+        }
+      }
+      ms = group_sum(ms);
+      ml = group_sum(ml);
+      float lse;
+      const float q = c51_softmax_q<TPA>(p.sup, lg, &lse);  // lg becomes p, 0 on the padding
+#pragma unroll
+      for (int t = 0; t < TPA; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) da[t][r] = mine ? scale * (lg[t][r] - da[t][r]) : 0.f;
+      }
+      if (mine) {
+        loss_row = fmaf(lse, ms, -ml);
+        q_act = q;
+#pragma unroll
+        for (int t = 0; t < TPA; ++t) d[t] = da[t];
+      }
+      dense_bwd_acc<HT, TPA>(w3a, LW::S3, da, dh2);
+    }
+#pragma unroll
+    for (int t = 0; t < HT; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dh2[t][r] = h2[t][r] > 0.f ? dh2[t][r] : 0.f;
+    }
+    if (valid && g == 0) {
+      s_loss += wi * loss_row;
+      s_val += q_act;
+      s_cnt += 1.f;
+      if (p.td_abs != nullptr) p.td_abs[row] = loss_row;
+    }
+
+    // ------------------------------------------------------------ phase A: dW3, db3 (W3 is overwritten)
+    __syncthreads();  // every wave has read its last W3 fragment
+    stage_tiles<HT>(st0, wave, h2);
+    for (int a = 0; a < A; ++a) {
+#pragma unroll
+      for (int t = 0; t < TPA; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          st1[(16 * (a * TPA + t) + 4 * g + r) * kStageLd + 16 * wave + j] = (act == a) ? d[t][r] : 0.f;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int to = 0; to < OTM; ++to)
+      if (to < OT) wgrad<1, TI3>(st1, st0, to, wave * TI3, acc3[to], bacc3[to]);
+
+    // ------------------------------------------------------------ phase B: dW2, db2
+    __syncthreads();
+    stage_tiles<HT>(st0, wave, h1);
+    stage_tiles<HT>(st1, wave, dh2);
+    floatx4 dh1[HT];
+    dense_bwd_data<HT, HT, true>(lds + L::W2, L::S2, dh2, h1, dh1);
+    __syncthreads();
+    wgrad<TO, HT>(st1, st0, wave * TO, 0, acc2, bacc2);
+
+    // ------------------------------------------------------------ phase C: dW1, db1
+    __syncthreads();
+    stage_x_tiles<1>(st0, wave, x);
+    stage_tiles<HT>(st1, wave, dh1);
+    __syncthreads();
+    wgrad<TO, 1>(st1, st0, wave * TO, 0, acc1, bacc1);
+  }
+
+  // ------------------------------------------------------------------ epilogue
+  const FlatOffsets o = flat_offsets(p.D, H, A * NA);
+  float* slab = p.grad_slab + (size_t)blockIdx.x * p.P;
+#pragma unroll
+  for (int to = 0; to < TO; ++to) {
+    const int ot = wave * TO + to;
+#pragma unroll
+    for (int ti = 0; ti < HT; ++ti) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) slab[o.w2 + (16 * ot + 4 * g + r) * H + 16 * ti + j] = acc2[to][ti][r];
+    }
+    const float b2 = group_sum(bacc2[to]);
+    if (g == 0) slab[o.b2 + 16 * ot + j] = b2;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (j < p.D) slab[o.w1 + (16 * ot + 4 * g + r) * p.D + j] = acc1[to][0][r];
+    const float b1 = group_sum(bacc1[to]);
+    if (g == 0) slab[o.b1 + 16 * ot + j] = b1;
+  }
+  // dW3 / db3: padded tile `to` is rows 16 (to % TPA) .. + 15 of action to / TPA; the padding rows are dropped
+#pragma unroll
+  for (int to = 0; to < OTM; ++to) {
+    if (to < OT) {
+      const int a = to / TPA, i0 = 16 * (to - a * TPA);
+#pragma unroll
+      for (int ti = 0; ti < TI3; ++ti) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = i0 + 4 * g + r;
+          if (i < NA) slab[o.w3 + (a * NA + i) * H + 16 * (wave * TI3 + ti) + j] = acc3[to][0][ti][r];
+        }
+      }
+      const float b3g = group_sum(bacc3[to][0]);
+      if (wave == 0 && g == 0 && i0 + j < NA) slab[o.b3 + a * NA + i0 + j] = b3g;
+    }
+  }
+
+  __syncthreads();
+  float* red = st0;  // [4 waves][8]
+  float stats[3] = {s_loss, s_val, s_cnt};
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const float v = wave_sum(stats[s]);
+    if (l == 0) red[wave * 8 + s] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 8) {
+    const int s = threadIdx.x;  // loss slab: [0] loss, [4] Q(act), [5] rows
+    const int src = s == 0 ? 0 : s == 4 ? 1 : s == 5 ? 2 : -1;
+    p.loss_slab[blockIdx.x * 8 + s] = src < 0 ? 0.f : red[src] + red[8 + src] + red[16 + src] + red[24 + src];
+  }
+}
+
 }  // namespace rrl
 
 using namespace rrl;
@@ -601,6 +854,19 @@ static int dispatch_head(int head, const GradQrArgs& a, int grid, hipStream_t s)
   return -1;
 }
 
+template <int HT>
+static int launch_grad_c51(const GradC51Args& a, int tpa, int grid, hipStream_t s) {
+  const int OT = a.A * tpa, SR = std::max(16 * HT, 16 * OT);
+  const size_t bytes = sizeof(float) * ((size_t)LdsNet<1, HT>::fixed_floats() + 16 * OT + 2 * (size_t)SR * kStageLd);
+  if (bytes > 163840) return -4;
+  return dispatch_tpa<kMaxTpa>(tpa, [&](auto tag) {
+    constexpr int TPA = decltype(tag)::TPA;
+    raise_lds_limit<mlp_grad_c51_kernel<HT, TPA>>();
+    hipLaunchKernelGGL((mlp_grad_c51_kernel<HT, TPA>), dim3(grid), dim3(256), bytes, s, a);
+    return (int)hipGetLastError();
+  });
+}
+
 // Value-MSE and policy gradient path: 1 = weight-stationary bf16x6 kernels (value_grad.hip)
 // where they apply (value: H = 128, D <= 24; categorical: D <= 8, A = 2..4; Gaussian: D <= 24,
 // A = 1 or 6), 0 = the fp32-MFMA kernel above for every shape.
@@ -622,8 +888,31 @@ extern "C" int rrl_mlp_grad_slabs(int B, int num_cu) {
 
 extern "C" int rrl_mlp_grad(const MlpGradCall* c, int num_cu, void* stream) {
   const int head = c->head, D = c->D, A = c->A, H = c->H, NQ = c->quantiles;
-  const bool qr = head == HEAD_Q_QR, qhead = qr || head == HEAD_Q_TD || head == HEAD_Q_DUEL;
-  if (head < HEAD_PG_CAT || head > HEAD_Q_QR) return -1;
+  const bool c51 = head == HEAD_Q_C51;
+  const bool qr = head == HEAD_Q_QR, qhead = c51 || qr || head == HEAD_Q_TD || head == HEAD_Q_DUEL;
+  if (head < HEAD_PG_CAT || head > HEAD_Q_C51) return -1;
+  if (c51 != (c->atoms != 0)) return -1;
+  if (c51) {
+    GradC51Args a;
+    if (!c->params || !c->X || !c->act || !c->ret || !c->grad_slab || !c->loss_slab) return -1;
+    if ((c->row_w == nullptr) != (c->w_norm == nullptr)) return -1;
+    if (A < 1 || D < 1 || D > 16 || c->B < 1) return -2;
+    if (H != 64 && H != 128) return -3;
+    const int tpa = NQ == 0 ? c51_support(A, c->atoms, c->v_min, c->v_max, &a.sup) : 0;
+    if (tpa == 0) return -3;  // with quantiles, atoms < 2, v_max <= v_min or past the tile limit
+    if (c->P != H * D + H + H * H + H + A * c->atoms * H + A * c->atoms) return -2;  // not MLPSpec(D, H, A * NA)
+    static_cast<GradArgs&>(a) = {c->params, c->X, c->B, D, A, nullptr, c->act, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, c->inv_B, 0.f, 0.f, c->grad_slab, c->loss_slab, c->P};
+    a.nvalid = c->nvalid;
+    a.inv_B_dev = c->inv_B_dev;
+    a.row_w = c->row_w;
+    a.w_norm = c->w_norm;
+    a.td_abs = c->td_abs;
+    a.qtarget = c->ret;
+    const int grid = rrl_mlp_grad_slabs(c->B, num_cu);
+    return H == 128 ? launch_grad_c51<8>(a, tpa, grid, (hipStream_t)stream)
+                    : launch_grad_c51<4>(a, tpa, grid, (hipStream_t)stream);
+  }
   if (qr ? NQ < 1 : NQ != 0) return -1;
   if (qr && (!c->params || !c->X || !c->act || !c->ret || !c->grad_slab || !c->loss_slab)) return -1;
   if ((c->row_w == nullptr) != (c->w_norm == nullptr)) return -1;

@@ -26,6 +26,25 @@ def q_outputs(A: int, dueling: bool = False, quantiles: int = 0) -> int:
     return A * NQ if NQ else A + 1 if dueling else A
 
 
+def c51_outputs(A: int, atoms: int, v_min: float, v_max: float, dueling: bool = False, quantiles: int = 0) -> int:
+    """Outputs of a categorical (C51) Q-network over ``A`` actions, ``A * atoms``, as the wide output layer holds them:
+    every action's atoms are rounded up to whole tiles of 16 outputs and 8 tiles are the limit, so CartPole takes up
+    to 64 atoms and the envs of 3 or 4 actions up to 32.  Raises ``ValueError`` for what is not built: ``atoms`` with
+    ``quantiles`` or with ``dueling``, ``atoms < 2``, ``v_max <= v_min``, or a head past the tile limit."""
+    A, NA = int(A), int(atoms)
+    if int(quantiles):
+        raise ValueError(f"atoms = {NA} with quantiles = {quantiles} is not built: set one of the two")
+    if dueling:
+        raise ValueError(f"atoms = {NA} with dueling = True is not built: set one of the two")
+    if NA < 2:
+        raise ValueError(f"atoms must be 0 or >= 2, got {atoms}")
+    if not float(v_max) > float(v_min):
+        raise ValueError(f"atoms needs v_min < v_max, got v_min = {v_min} and v_max = {v_max}")
+    if A < 1 or NA > 64 or A * ((NA + 15) // 16) > 8:
+        raise ValueError(f"a categorical net has A * ceil(atoms / 16) <= 8 output tiles, got A = {A} and atoms = {NA}")
+    return A * NA
+
+
 @dataclass(frozen=True)
 class MLPSpec:
     """Linear(D,H)-ReLU-Linear(H,H)-ReLU-Linear(H,A) [+ log_std(A)]."""

@@ -18,7 +18,7 @@ import torch
 
 from . import philox
 from . import reference as ref
-from ..models.mlp_spec import MLPSpec, q_outputs
+from ..models.mlp_spec import MLPSpec, c51_outputs, q_outputs
 
 
 class ReplayRing(NamedTuple):
@@ -50,13 +50,26 @@ def check_quantiles(A: int, quantiles, dueling: bool = False) -> int:
     return int(quantiles)
 
 
-def check_q_params(params, D: int, H: int, A: int, dueling: bool, name: str = "params", quantiles: int = 0):
-    """A Q-network over ``A`` actions is ``MLPSpec(D, H, q_outputs(A, dueling, quantiles))``: ``params`` must have
-    exactly that many floats."""
-    NQ = int(quantiles)
-    want = MLPSpec(int(D), int(H), q_outputs(A, dueling, NQ)).P
+def check_atoms(A: int, atoms, v_min, v_max, dueling: bool = False, quantiles: int = 0) -> int:
+    """``atoms`` as the kernels take it -> NA: 0 is no categorical head; NA >= 2 a categorical net of ``A * NA``
+    outputs on the support ``[v_min, v_max]`` (``c51_outputs`` has the rule)."""
+    if not int(atoms):
+        return 0
+    c51_outputs(A, atoms, v_min, v_max, dueling, quantiles)
+    return int(atoms)
+
+
+def check_q_params(params, D: int, H: int, A: int, dueling: bool, name: str = "params", quantiles: int = 0,
+                   atoms: int = 0):
+    """A Q-network over ``A`` actions is ``MLPSpec(D, H, q_outputs(A, dueling, quantiles))``, a categorical one
+    ``MLPSpec(D, H, A * atoms)``: ``params`` must have exactly that many floats."""
+    NQ, NA = int(quantiles), int(atoms)
+    want = MLPSpec(int(D), int(H), A * NA if NA else q_outputs(A, dueling, NQ)).P
     if params is None or params.numel() == want:
         return
+    if NA:
+        raise ValueError(f"{name} has {params.numel()} floats; a categorical Q-network of D = {D}, H = {H}, A = {A}, "
+                         f"atoms = {NA} has {want}")
     if NQ:
         raise ValueError(f"{name} has {params.numel()} floats; a quantile Q-network of D = {D}, H = {H}, A = {A}, "
                          f"quantiles = {NQ} has {want}")
@@ -66,7 +79,8 @@ def check_q_params(params, D: int, H: int, A: int, dueling: bool, name: str = "p
 
 def dqn_rollout(env_id: int, params: torch.Tensor, hidden: int, rollout_len: int, slot0: int, ring: ReplayRing,
                 state, ep_len, ep_ret, ep_stats, *, seed: int, step0: int, epsilon: float, reset_all: bool,
-                max_steps: int, dueling: bool = False, quantiles: int = 0) -> int:
+                max_steps: int, dueling: bool = False, quantiles: int = 0, atoms: int = 0, v_min: float = 0.0,
+                v_max: float = 0.0) -> int:
     """T = ``rollout_len`` epsilon-greedy steps of every env into ring slots ``slot0 .. slot0 + T - 1``.
     Returns 0, or the kernel's negative code (nothing written) for a launch that would wrap: unless
     ``C % T == 0``, ``slot0 % T == 0`` and ``slot0 + T <= C``.  Asynchronous on the current stream.
@@ -75,18 +89,24 @@ def dqn_rollout(env_id: int, params: torch.Tensor, hidden: int, rollout_len: int
     takes the lowest-index argmax of its ``A`` advantage outputs.  The draws and the ring do not change.
 
     ``quantiles`` = NQ >= 1: ``params`` is a quantile net of ``A * NQ`` outputs (``reference.quantile_q``); a greedy
-    step takes the lowest-index argmax of the per-action quantile sums.  Again the draws and the ring do not change."""
+    step takes the lowest-index argmax of the per-action quantile sums.  Again the draws and the ring do not change.
+
+    ``atoms`` = NA >= 2 (with ``v_min < v_max``): ``params`` is a categorical net of ``A * NA`` outputs on the wide output
+    layer (``reference.c51_q``); a greedy step takes the lowest-index argmax of the per-action expectations.  It is
+    refused with ``dueling`` or ``quantiles`` and past 8 output tiles (``c51_outputs``)."""
     from . import hip
 
     h = hip()  # raises NativeExtensionMissing: there is no fallback
     if not params.is_cuda:
         raise ValueError("dqn_rollout runs the HIP kernel only: params must be a GPU tensor")
-    if dueling or quantiles:
+    if dueling or quantiles or atoms:
         D, A, _, _ = h.env_dims(int(env_id))
-        check_q_params(params, D, hidden, A, bool(dueling), quantiles=quantiles)
+        NA = check_atoms(A, atoms, v_min, v_max, bool(dueling), quantiles)
+        check_q_params(params, D, hidden, A, bool(dueling), quantiles=quantiles, atoms=NA)
     return int(h.dqn_rollout(int(env_id), params, int(hidden), int(rollout_len), int(slot0), state, ep_len, ep_ret,
                              ring.obs, ring.nobs, ring.act, ring.rew, ring.done, ep_stats, int(seed), int(step0),
-                             float(epsilon), bool(reset_all), int(max_steps), bool(dueling), int(quantiles)))
+                             float(epsilon), bool(reset_all), int(max_steps), bool(dueling), int(quantiles),
+                             *((int(atoms), float(v_min), float(v_max)) if atoms else ())))
 
 
 def dqn_sample_rows_ref(seed: int, update: int, B: int, filled: int) -> np.ndarray:
@@ -151,7 +171,8 @@ def dqn_nstep_walk_ref(rows, ring: ReplayRing, filled: int, newest: int, n_step:
 @torch.no_grad()
 def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: int, gamma: float, double_q: bool,
                     seed: int, update: int, B: int, dtype=torch.float32, tree=None, beta: Optional[float] = None,
-                    n_step: int = 1, newest: Optional[int] = None, dueling: bool = False, quantiles: int = 0):
+                    n_step: int = 1, newest: Optional[int] = None, dueling: bool = False, quantiles: int = 0,
+                    atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0):
     """-> ``(Xb [B, D], act_b [B] int32, y [B], idx [B] int64)`` in ``dtype``;
     ``y = rew + gamma * (done == 1 ? 0 : 1) * Q_target(nobs, a*)`` with ``a*`` the lowest-index argmax of the
     target (``double_q`` false) or online net.  With ``tree`` (the priority sum tree of ops/per.py) the rows
@@ -168,11 +189,17 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
 
     ``quantiles`` = NQ >= 1: both nets are quantile nets of ``A * NQ`` outputs, ``a*`` is the lowest-index argmax of
     the selecting net's quantile sums (``reference.quantile_q``), ``y`` is [B, NQ] and
-    ``y[b, j] = G + disc * boot * theta_target[a* * NQ + j]``.  Everything but ``y`` is that of the scalar call."""
+    ``y[b, j] = G + disc * boot * theta_target[a* * NQ + j]``.  Everything but ``y`` is that of the scalar call.
+
+    ``atoms`` = NA >= 2: both nets are categorical nets of ``A * NA`` outputs on ``[v_min, v_max]``, ``a*`` is the
+    lowest-index argmax of the selecting net's expectations (``reference.c51_q``) and ``y`` is m [B, NA], the projection
+    (``reference.c51_project``) of the target net's distribution of ``a*`` through ``Tz_j = G + disc * boot * z_j``.
+    Again everything but ``y`` is that of the scalar call."""
     D = ring.obs.shape[-1]
     dev = ring.obs.device
+    NA = check_atoms(A, atoms, v_min, v_max, dueling, quantiles) if atoms else 0
     NQ = check_quantiles(A, quantiles, dueling)
-    _check_q_nets(online if double_q else None, target, D, H, A, dueling, NQ)
+    _check_q_nets(online if double_q else None, target, D, H, A, dueling, NQ, NA)
     n_step = int(n_step)
     if n_step != 1:
         check_nstep(n_step, newest, int(ring.act.shape[1]), int(filled))
@@ -191,7 +218,14 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
                          for x in dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)[:3])
     nobs = ring.nobs.reshape(-1, D)[last].to(dtype)
     boot = (ring.done.reshape(-1)[last] != 1).to(dtype)
-    if NQ > 0:
+    if NA > 0:
+        q_t, p_t = ref.c51_q(ref.trunk(target.to(dtype), nobs, D, H, A * NA)[0], A, NA, v_min, v_max)
+        q_sel = ref.c51_q(ref.trunk(online.to(dtype), nobs, D, H, A * NA)[0], A, NA, v_min, v_max)[0] if double_q else q_t
+        astar, _ = ref.greedy_from_logits(q_sel)
+        p_star = p_t.gather(1, astar.reshape(-1, 1, 1).expand(-1, 1, NA)).squeeze(1)
+        c = (disc if torch.is_tensor(disc) else torch.full_like(G, disc)) * boot
+        y = ref.c51_project(p_star, G, c, v_min, v_max)
+    elif NQ > 0:
         out_t = ref.trunk(target.to(dtype), nobs, D, H, A * NQ)[0]
         sel = ref.trunk(online.to(dtype), nobs, D, H, A * NQ)[0] if double_q else out_t
         astar, _ = ref.greedy_from_logits(ref.quantile_q(sel, A, NQ))
@@ -207,13 +241,13 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
     return res if n_step == 1 else res + (last,)
 
 
-def _check_q_nets(online, target, D, H, A, dueling, quantiles=0):
+def _check_q_nets(online, target, D, H, A, dueling, quantiles=0, atoms=0):
     """The sizes of the nets a targets call reads.  A hidden size the kernels do not have is the launch's to
     refuse (a GPU call), so it is not judged here."""
     if target.is_cuda and int(H) not in (64, 128):
         return
-    check_q_params(target, D, H, A, dueling, "target", quantiles)
-    check_q_params(online, D, H, A, dueling, "online", quantiles)
+    check_q_params(target, D, H, A, dueling, "target", quantiles, atoms)
+    check_q_params(online, D, H, A, dueling, "online", quantiles, atoms)
 
 
 def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
@@ -229,7 +263,7 @@ def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
 def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
                 gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32,
                 tree=None, beta: Optional[float] = None, n_step: int = 1, newest: Optional[int] = None,
-                dueling: bool = False, quantiles: int = 0):
+                dueling: bool = False, quantiles: int = 0, atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0):
     """Sample, gather and TD target in one launch -> ``(Xb, act_b, y, idx)``; ``out`` = the four tensors to
     write into (``idx`` int32 on the GPU, or None to skip it).  CPU tensors take the torch reference in
     ``dtype``; a GPU tensor without the extension raises.
@@ -249,13 +283,19 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
 
     ``quantiles`` = NQ >= 1 selects the quantile instances: ``online`` / ``target`` are ``MLPSpec(D, H, A * NQ)``
     nets and ``y`` is [B, NQ] (``dqn_targets_ref`` has the semantics); again only ``y`` differs from the scalar
-    launch.  It is refused together with ``dueling``."""
+    launch.  It is refused together with ``dueling``.
+
+    ``atoms`` = NA >= 2 (with ``v_min < v_max``) selects the categorical instances on the wide output layer: ``online`` /
+    ``target`` are ``MLPSpec(D, H, A * NA)`` nets and ``y`` is the projected distribution m [B, NA] (``dqn_targets_ref``
+    has the semantics); only ``y`` differs from the scalar launch.  It is refused with ``dueling`` or ``quantiles``."""
     from . import use_hip, hip
 
     per = tree is not None
     dueling = bool(dueling)
+    NA = check_atoms(A, atoms, v_min, v_max, dueling, quantiles) if atoms else 0
     NQ = check_quantiles(A, quantiles, dueling) if quantiles else 0
-    _check_q_nets(online if double_q else None, target, ring.obs.shape[-1], H, A, dueling, NQ)
+    _check_q_nets(online if double_q else None, target, ring.obs.shape[-1], H, A, dueling, NQ, NA)
+    NY = NA or NQ  # targets per batch row past the scalar one
     if per and not (beta is not None and 0.0 < beta <= 1.0):
         raise ValueError(f"the prioritised form needs beta in (0, 1], got {beta}")
     n_step = int(n_step)
@@ -270,7 +310,7 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
         raise ValueError("at n_step = 1 last is idx: it cannot be written without idx")
     if not use_hip(target):
         res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
-                              n_step, newest, dueling, NQ)
+                              n_step, newest, dueling, NQ, NA, v_min, v_max)
         if out is None:
             return res
         if n_step == 1:
@@ -282,20 +322,22 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
     dev = target.device
     if out is None:
         out = (torch.empty(B, ring.obs.shape[-1], device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty((B, NQ) if NQ else (B,), device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+               torch.empty((B, NY) if NY else (B,), device=dev), torch.empty(B, dtype=torch.int32, device=dev))
         if per:
             out += (torch.empty(B, device=dev), torch.empty(1, device=dev))
         if n_step != 1:
             out += (torch.empty(B, dtype=torch.int32, device=dev),)
-    if out[2].numel() != (B * NQ if NQ else B):
-        raise ValueError(f"y must hold {B * NQ if NQ else B} targets, got {out[2].numel()}")
+    if out[2].numel() != (B * NY if NY else B):
+        raise ValueError(f"y must hold {B * NY if NY else B} targets, got {out[2].numel()}")
     if per and out[3] is None:
         raise ValueError("the prioritised form writes idx: it cannot be skipped")
     w, wmax = out[4:6] if per else (None, None)
-    # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling, quantiles) in its order: a
+    # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling, quantiles, atoms, v_min, v_max)
+    # in its order: a
     # positional call parses faster than a keyword one, and this is the one place that makes it
     hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
                       ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), *out[:4], tree,
                       float(beta) if per else None, w, wmax, n_step, newest,
-                      out[base] if len(out) > base else None, dueling, NQ)
+                      out[base] if len(out) > base else None, dueling, NQ,
+                      *((NA, float(v_min), float(v_max)) if NA else ()))
     return out

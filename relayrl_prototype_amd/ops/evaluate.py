@@ -24,7 +24,8 @@ class EvalTrace(NamedTuple):
 def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes: int, num_envs: int, *,
                        greedy: bool = True, seed: int = 0, step0: int = 0, max_steps: Optional[int] = None,
                        env_consts: Optional[torch.Tensor] = None, trace_steps: int = 0, out=None,
-                       trace: Optional[EvalTrace] = None, dueling: bool = False, quantiles: int = 0):
+                       trace: Optional[EvalTrace] = None, dueling: bool = False, quantiles: int = 0, atoms: int = 0,
+                       v_min: float = 0.0, v_max: float = 0.0):
     """-> ``(ep_ret, ep_len, ep_code, trace-or-None)``: float32 / int32 / int32 ``[episodes, num_envs]``
     (code 1 terminal, 2 time limit).  ``out`` = the three tensors to write into; ``trace`` = an
     ``EvalTrace`` to write into, or ``trace_steps`` > 0 to have one allocated (zero-filled).
@@ -35,7 +36,10 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     the action is the lowest-index argmax of its ``A`` advantage outputs.
 
     ``quantiles`` = NQ >= 1 (discrete envs, ``greedy`` only): ``params`` is a quantile Q-network of ``A * NQ``
-    outputs and the action is the lowest-index argmax of the per-action quantile sums."""
+    outputs and the action is the lowest-index argmax of the per-action quantile sums.
+
+    ``atoms`` = NA >= 2 with ``v_min < v_max`` (discrete envs, ``greedy`` only): ``params`` is a categorical Q-network of
+    ``A * NA`` outputs and the action is the lowest-index argmax of the per-action expectations."""
     from . import hip
 
     h = hip()  # raises NativeExtensionMissing: there is no fallback
@@ -45,15 +49,16 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     continuous = int(env_id) == h.ENV_IDS["ENV_HALFCHEETAH"]
     if continuous and env_consts is None:
         raise ValueError("the continuous device env needs env_consts")
-    if dueling or quantiles:
-        from .dqn import check_q_params
+    if dueling or quantiles or atoms:
+        from .dqn import check_atoms, check_q_params
 
-        kind = "dueling" if dueling else "quantile"
+        kind = "dueling" if dueling else "quantile" if quantiles else "categorical"
         if continuous:
             raise ValueError(f"a {kind} Q-network needs a discrete action space")
         if not greedy:
             raise ValueError(f"a {kind} Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
-        check_q_params(params, D, hidden, A, bool(dueling), quantiles=quantiles)
+        NA = check_atoms(A, atoms, v_min, v_max, bool(dueling), quantiles)
+        check_q_params(params, D, hidden, A, bool(dueling), quantiles=quantiles, atoms=NA)
     E, N = int(episodes), int(num_envs)
     if E < 1 or N < 1:
         raise ValueError(f"episodes and num_envs must be >= 1, got {E} and {N}")
@@ -75,5 +80,5 @@ def evaluate_policy_op(env_id: int, params: torch.Tensor, hidden: int, episodes:
     if continuous:
         h.evaluate_cont(int(env_id), params, env_consts, *args)
     else:
-        h.evaluate(int(env_id), params, *args, bool(dueling), int(quantiles))
+        h.evaluate(int(env_id), params, *args, bool(dueling), int(quantiles), int(atoms), float(v_min), float(v_max))
     return ep_ret, ep_len, ep_code, trace

@@ -34,9 +34,10 @@ class GradHead(IntEnum):
     Q_TD = 5  # DQN: Huber loss on Q(x)[act] - ret; the threshold delta travels in clip_eps
     Q_DUEL = 6  # Q_TD on a dueling net of A + 1 outputs: Q = V + adv[act] - mean(adv) (reference.dueling_q)
     Q_QR = 7  # QR-DQN: quantile-Huber loss on a net of A * quantiles outputs; ret is [B, quantiles]
+    Q_C51 = 8  # C51: cross-entropy to the projected target on a net of A * atoms outputs; ret is m [B, atoms]
 
 
-from ..models.mlp_spec import MLPSpec, q_outputs  # noqa: E402,F401 -- torch-free (CPU agents import it)
+from ..models.mlp_spec import MLPSpec, c51_outputs, q_outputs  # noqa: E402,F401 -- torch-free (CPU agents import it)
 
 
 def _hip_for(t):
@@ -132,14 +133,15 @@ def set_value_grad_mode(mode: int) -> int:
 
 # The heads as plain ints: mlp_grad runs once per update, and an enum member costs a metaclass lookup each time.
 _VALUE, _DUEL, _QR = int(GradHead.VALUE_MSE), int(GradHead.Q_DUEL), int(GradHead.Q_QR)
-_Q_HEADS = (int(GradHead.Q_TD), _DUEL, _QR)  # read act + ret, and may take row_w / w_norm / td_abs
+_C51 = int(GradHead.Q_C51)
+_Q_HEADS = (int(GradHead.Q_TD), _DUEL, _QR, _C51)  # read act + ret, and may take row_w / w_norm / td_abs
 _GAUSS_HEADS = (int(GradHead.PPO_GAUSS), int(GradHead.PG_GAUSS))
 
 
 def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=None, adv=None, ret=None,
              logp_old=None, adv_stats=None, inv_B: Optional[float] = None, clip_eps: float = 0.2,
              ent_coef: float = 0.0, grad_slab=None, loss_slab=None, nvalid=None, inv_B_dev=None, row_w=None,
-             w_norm=None, td_abs=None, quantiles: int = 0):
+             w_norm=None, td_abs=None, quantiles: int = 0, atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0):
     """Fused forward+backward.  GPU: fills grad_slab [nslab, P] and loss_slab [nslab, 8] and
     returns them; CPU: returns (grad [1, P], loss stats [1, 8]) computed with autograd.
 
@@ -157,9 +159,14 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
     ``Q_QR``, the quantile-regression head of QR-DQN, comes with ``quantiles`` = NQ >= 1 (``A * NQ <= 16``) and no
     other head does: ``params`` and the slab are those of ``MLPSpec(D, H, A * NQ)`` (output ``a * NQ + i`` is quantile
     ``i`` of action ``a``), ``ret`` is [B, NQ], ``clip_eps`` > 0 is the Huber threshold kappa and ``td_abs[i]``
-    receives the row's UNWEIGHTED quantile-Huber loss (``reference.mlp_grad_ref`` has the formula)."""
-    head, NQ = int(head), int(quantiles)
-    qr = head == _QR
+    receives the row's UNWEIGHTED quantile-Huber loss (``reference.mlp_grad_ref`` has the formula).
+
+    ``Q_C51``, the categorical head on the wide output layer, comes with ``atoms`` = NA >= 2 and its support
+    ``v_min`` < ``v_max`` (``models.mlp_spec.c51_outputs`` has the limits) and no other head does: ``params`` and the
+    slab are those of ``MLPSpec(D, H, A * NA)``, D <= 16, ``ret`` is the projected target m [B, NA] of ``dqn_targets``,
+    the row loss is ``-sum_i m_i log p(act, i)`` and ``td_abs[i]`` receives it UNWEIGHTED."""
+    head, NQ, NA = int(head), int(quantiles), int(atoms) if atoms else 0
+    qr, c51 = head == _QR, head == _C51
     X = X.contiguous().float()
     B, D = X.shape
     if inv_B is None:
@@ -168,11 +175,21 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
         raise ValueError("row_w and w_norm come together")
     if head not in _Q_HEADS and (row_w is not None or td_abs is not None):
         raise ValueError("row_w / w_norm / td_abs apply to the Q_TD, Q_DUEL and Q_QR heads only")
-    if NQ and not qr:
-        raise ValueError(f"quantiles ({quantiles}) goes with the Q_QR head")
-    if qr and NQ < 1:
-        raise ValueError(f"the Q_QR head needs quantiles >= 1, got {quantiles}")
-    outputs = 1 if head == _VALUE else q_outputs(A, head == _DUEL, NQ)
+    if c51 or NA:  # apart from this test, the other heads' calls run what they ran before
+        if not (c51 and NA):
+            raise ValueError(f"atoms ({atoms}) goes with the Q_C51 head, where it is >= 2")
+        outputs = c51_outputs(A, NA, v_min, v_max, False, NQ)
+        if D > 16 or params.numel() != MLPSpec(D, H, outputs).P:
+            raise ValueError(f"params has {params.numel()} floats; a categorical Q-network of D = {D} <= 16, H = {H}, "
+                             f"A = {A}, atoms = {NA} has {MLPSpec(D, H, outputs).P}")
+        if act is None or ret is None or ret.numel() != B * NA:
+            raise ValueError(f"act [B] and ret [B, atoms] = [{B}, {NA}] targets are required")
+    else:
+        if NQ and not qr:
+            raise ValueError(f"quantiles ({quantiles}) goes with the Q_QR head")
+        if qr and NQ < 1:
+            raise ValueError(f"the Q_QR head needs quantiles >= 1, got {quantiles}")
+        outputs = 1 if head == _VALUE else q_outputs(A, head == _DUEL, NQ)
     P = MLPSpec(D, H, outputs, head in _GAUSS_HEADS).P
     if qr:
         if not clip_eps > 0:
@@ -184,8 +201,8 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
             raise ValueError(f"act [B] and ret [B, quantiles] = [{B}, {NQ}] targets are required")
     h = _hip_for(X)
     if h is None:
-        if qr:
-            ret = ret.reshape(B, NQ)
+        if qr or c51:
+            ret = ret.reshape(B, NQ or NA)
         n = B if nvalid is None else int(nvalid.reshape(-1)[0])
         ib = inv_B if inv_B_dev is None else float(inv_B_dev.reshape(-1)[0])
 
@@ -194,7 +211,7 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
 
         g, st = ref.mlp_grad_ref(head, params, X[:n], A, H, cut(mask), cut(act), cut(actc), cut(adv), cut(ret),
                                  cut(logp_old), adv_stats, ib, clip_eps, ent_coef, row_w=cut(row_w), w_norm=w_norm,
-                                 quantiles=NQ)
+                                 quantiles=NQ, atoms=NA, v_min=v_min, v_max=v_max)
         if td_abs is not None:
             td_abs[:n].copy_(st["td_abs"])
         ls = torch.zeros(1, 8)
@@ -206,8 +223,8 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
         ls[0, 5] = st.get("count", n)
         return g.view(1, -1), ls
     chunks = grad_chunks(B)
-    if len(chunks) > 1 and qr:
-        raise ValueError(f"the quantile head takes a single-launch batch (<= {GRAD_CHUNK_ROWS} rows)")
+    if len(chunks) > 1 and (qr or c51):
+        raise ValueError(f"the quantile and categorical heads take a single-launch batch (<= {GRAD_CHUNK_ROWS} rows)")
     if len(chunks) > 1 and nvalid is not None:
         raise ValueError("a device-side row count needs a single-launch batch (< 2^25 rows)")
     if td_abs is not None and not (td_abs.is_contiguous() and td_abs.dtype == torch.float32):
@@ -229,7 +246,8 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
 
         h.mlp_grad(head, params, rows(X), A, H, rows(mask), rows(act), rows(actc), rows(adv), rows(ret),
                    rows(logp_old), adv_stats, float(inv_B), float(clip_eps), float(ent_coef), grad_slab[off:off + n],
-                   loss_slab[off:off + n], nvalid, inv_B_dev, rows(row_w), w_norm, rows(td_abs), NQ)
+                   loss_slab[off:off + n], nvalid, inv_B_dev, rows(row_w), w_norm, rows(td_abs), NQ,
+                   *((NA, float(v_min), float(v_max)) if NA else ()))
         off += n
     return grad_slab[:ns], loss_slab[:ns]
 

@@ -12,9 +12,11 @@ import numpy as np
 import torch
 
 from . import philox
+from ..models.mlp_spec import c51_outputs
 
 MODE_VALUE, MODE_CAT_SAMPLE, MODE_CAT_EVAL, MODE_LOGITS, MODE_GAUSS_SAMPLE, MODE_GAUSS_EVAL = range(6)
 HEAD_PG_CAT, HEAD_VALUE_MSE, HEAD_PPO_CAT, HEAD_PPO_GAUSS, HEAD_PG_GAUSS, HEAD_Q_TD, HEAD_Q_DUEL, HEAD_Q_QR = range(8)
+HEAD_Q_C51 = 8
 HALF_LOG_2PI = 0.91893853320467274
 
 
@@ -163,6 +165,94 @@ def quantile_q(out: torch.Tensor, A: int, NQ: int) -> torch.Tensor:
     return s
 
 
+def _stepwise(dtype):
+    """Categorical-head oracles work on float64 tensors; in float32 every operation's result is rounded to fp32, which
+    turns ``a * b + c`` into the kernels' fused multiply-add (the float64 product of two fp32 values is exact)."""
+    if dtype == torch.float64:
+        return lambda t: t
+    if dtype != torch.float32:
+        raise ValueError(f"the categorical oracles take float32 or float64, got {dtype}")
+    return lambda t: t.to(torch.float32).to(torch.float64)
+
+
+def c51_support(NA: int, v_min: float, v_max: float, dtype=torch.float64, device=None) -> torch.Tensor:
+    """The support ``z_i = v_min + i * dz``, ``dz = (v_max - v_min) / (NA - 1)`` as float64 values of ``dtype``'s
+    precision (rrl::c51_atom: one fused multiply-add on fp32 ``v_min`` / ``dz``)."""
+    NA = int(NA)
+    if NA < 2 or not v_max > v_min:
+        raise ValueError(f"a categorical head needs atoms >= 2 and v_min < v_max, got {NA}, {v_min}, {v_max}")
+    rnd = _stepwise(dtype)
+    lo, hi = rnd(torch.tensor(float(v_min), dtype=torch.float64)), rnd(torch.tensor(float(v_max), dtype=torch.float64))
+    dz = rnd(rnd(hi - lo) / (NA - 1))
+    return rnd(torch.arange(NA, dtype=torch.float64) * dz + lo).to(device)
+
+
+def _lane_group_sum(terms, rnd):
+    """Sum a list of per-atom tensors (atom i = 16 t + 4 g + r) in the wide layer's order: each lane group g adds its
+    atoms ascending, then (g0 + g1) + (g2 + g3)."""
+    part = []
+    for g in range(4):
+        acc = None
+        for i, x in enumerate(terms):
+            if (i % 16) // 4 == g:
+                acc = x if acc is None else rnd(acc + x)
+        part.append(acc if acc is not None else torch.zeros_like(terms[0]))
+    return rnd(rnd(part[0] + part[1]) + rnd(part[2] + part[3]))
+
+
+def c51_q(out: torch.Tensor, A: int, NA: int, v_min: float, v_max: float):
+    """The categorical head of ``out`` [..., A * NA] (column ``a * NA + i`` is the logit of atom ``i`` of action ``a``)
+    -> ``(Q [..., A], p [..., A, NA])`` in ``out``'s dtype: ``p(a, .) = softmax`` of the action's block and
+    ``Q(a) = sum_i z_i p(a, i)``, in the kernels' operation order (rrl::c51_softmax_q): with ``e_i = exp(l_i - max l)``,
+    ``s = sum e_i`` and ``sz = sum z_i e_i`` (a fused multiply-add per atom) are summed per lane group and combined
+    ``(g0 + g1) + (g2 + g3)``; ``p_i = e_i / s`` and ``Q = sz / s``.  The greedy action is ``greedy_from_logits(Q)``."""
+    A, NA = int(A), int(NA)
+    if out.shape[-1] != A * NA:
+        raise ValueError(f"a categorical net over {A} actions with {NA} atoms has {A * NA} outputs, got {out.shape[-1]}")
+    rnd = _stepwise(out.dtype)
+    z = c51_support(NA, v_min, v_max, out.dtype, out.device)
+    lg = out.to(torch.float64).reshape(*out.shape[:-1], A, NA)
+    shifted = rnd(lg - lg.max(dim=-1, keepdim=True).values)
+    e = torch.exp(shifted.to(out.dtype)).to(torch.float64)  # the exponential itself in out's dtype
+    es = [e[..., i] for i in range(NA)]
+    s = _lane_group_sum(es, rnd)
+    # the fused multiply-add chain of a lane group: acc = z_i * e_i + acc, one rounding each
+    part = []
+    for g in range(4):
+        acc = torch.zeros_like(es[0])
+        for i in range(NA):
+            if (i % 16) // 4 == g:
+                acc = rnd(z[i] * es[i] + acc)
+        part.append(acc)
+    sz = rnd(rnd(part[0] + part[1]) + rnd(part[2] + part[3]))
+    return rnd(sz / s).to(out.dtype), rnd(e / s.unsqueeze(-1)).to(out.dtype)
+
+
+def c51_project(p: torch.Tensor, G: torch.Tensor, c: torch.Tensor, v_min: float, v_max: float) -> torch.Tensor:
+    """The categorical projection of ``p`` [B, NA] through ``Tz_j = G + c * z_j`` (``G``, ``c`` [B]) onto the support, in
+    the gather form of rrl::c51_project, in ``p``'s dtype:
+
+        b_j = (clamp(G + c * z_j, z_0, z_{NA-1}) - v_min) / dz,    m_i = sum_j p_j * max(0, 1 - |b_j - i|)
+
+    It conserves the mass of ``p`` and is right where ``b_j`` is an integer (the textbook l / u scatter drops that
+    mass when ``l == u``).  ``j`` runs lane group by lane group (j = 16 t + 4 k + r: k outer, then t, then r), one fused
+    multiply-add each."""
+    NA = p.shape[-1]
+    rnd = _stepwise(p.dtype)
+    z = c51_support(NA, v_min, v_max, p.dtype, p.device)
+    lo = rnd(torch.tensor(float(v_min), dtype=torch.float64))
+    dz = rnd(rnd(rnd(torch.tensor(float(v_max), dtype=torch.float64)) - lo) / (NA - 1))
+    p64, G64, c64 = p.to(torch.float64), G.to(torch.float64).reshape(-1), c.to(torch.float64).reshape(-1)
+    i = torch.arange(NA, dtype=torch.float64, device=p.device)
+    m = torch.zeros_like(p64)
+    for j in sorted(range(NA), key=lambda j: ((j % 16) // 4, j)):
+        tz = torch.clamp(rnd(c64 * z[j] + G64), min=float(lo), max=float(z[NA - 1]))
+        b = rnd(rnd(tz - lo) / dz)
+        w = torch.clamp(rnd(1.0 - rnd(b.unsqueeze(-1) - i).abs()), min=0.0)
+        m = rnd(p64[:, j].unsqueeze(-1) * w + m)
+    return m.to(p.dtype)
+
+
 @torch.no_grad()
 def greedy_actions_ref(params, obs, A, H, dtype=torch.float64):
     """The greedy action of the categorical policy at ``obs`` [..., D] and the gap between its two
@@ -185,7 +275,7 @@ def normalize_adv(adv, adv_stats):
 
 def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None, ret=None, logp_old=None,
                  adv_stats=None, inv_B=None, clip_eps=0.2, ent_coef=0.0, dtype=torch.float32, row_w=None,
-                 w_norm=None, quantiles=0):
+                 w_norm=None, quantiles=0, atoms=0, v_min=0.0, v_max=0.0):
     """Returns (flat gradient, stats dict) of sum_i loss_i * inv_B (+ entropy bonus);
     ``dtype=torch.float64`` gives the float64 oracle (tools/grad_fuzz_probe.py).
     ``HEAD_Q_TD``: loss_i = huber(Q(x_i)[act_i] - ret_i, delta) with delta = ``clip_eps``, times
@@ -195,7 +285,11 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
     ``HEAD_Q_QR`` (``quantiles`` = NQ >= 1): ``params`` has ``A * NQ`` outputs, ``ret`` is [B, NQ] and with
     theta_i = out[act * NQ + i], tau_i = (2 i + 1) / (2 NQ), u_ij = ret_j - theta_i, kappa = ``clip_eps`` > 0
     loss_i = rho = (1 / NQ) sum_i sum_j |tau_i - [u_ij < 0]| huber_kappa(u_ij) / kappa, times the weight;
-    ``stats["td_abs"]`` is the UNWEIGHTED rho per row and ``stats["v"]`` sums ``quantile_q(out)[act] / NQ``."""
+    ``stats["td_abs"]`` is the UNWEIGHTED rho per row and ``stats["v"]`` sums ``quantile_q(out)[act] / NQ``.
+    ``HEAD_Q_C51`` (``atoms`` = NA >= 2 on ``v_min`` .. ``v_max``): ``params`` has ``A * NA`` outputs, ``ret`` is the
+    projected target distribution m [B, NA] and loss_i = -sum_k m_k log softmax(out[act block])_k, times the weight;
+    ``stats["td_abs"]`` is the UNWEIGHTED row loss, ``stats["q_act"]`` the rows' ``Q(act) = sum_k z_k p_k`` and
+    ``stats["v"]`` their sum."""
     B, D = X.shape
     gaussian = head in (HEAD_PPO_GAUSS, HEAD_PG_GAUSS)
     NQ = int(quantiles)
@@ -206,6 +300,11 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
     if head == HEAD_Q_QR and not clip_eps > 0:
         raise ValueError(f"the quantile head needs a Huber threshold (clip_eps / huber_delta) > 0, got {clip_eps}")
     Aeff = 1 if head == HEAD_VALUE_MSE else A + 1 if head == HEAD_Q_DUEL else A * NQ if head == HEAD_Q_QR else A
+    NA = int(atoms)
+    if (head == HEAD_Q_C51) != (NA != 0):
+        raise ValueError(f"atoms ({NA}) goes with HEAD_Q_C51, where it is >= 2")
+    if head == HEAD_Q_C51:
+        Aeff = c51_outputs(A, NA, v_min, v_max, False, NQ)
     if inv_B is None:
         inv_B = 1.0 / max(B, 1)
     p = params.detach().to(dtype).clone().requires_grad_(True)
@@ -230,6 +329,17 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
         loss = li.sum() * inv_B
         s_act = quantile_q(out, A, NQ).gather(-1, act.long().unsqueeze(-1)).squeeze(-1)
         stats.update(loss=li.sum().item(), v=(s_act / NQ).sum().item(), count=B, td_abs=rho.detach())
+    elif head == HEAD_Q_C51:
+        idx = act.long().clamp(0, A - 1).reshape(B, 1, 1).expand(B, 1, NA)
+        logp = torch.log_softmax(out.reshape(B, A, NA).gather(1, idx).squeeze(1), dim=-1)  # [B, NA]
+        ce = -(ret.to(dtype).reshape(B, NA) * logp).sum(-1)
+        li = ce
+        if row_w is not None:
+            li = (row_w.to(dtype) / torch.as_tensor(w_norm).to(dtype).reshape(-1)[0]) * ce
+        loss = li.sum() * inv_B
+        # Q(act) in the kernels' operation order (c51_q), which is what the loss slab sums
+        q_act = c51_q(out.detach(), A, NA, v_min, v_max)[0].gather(-1, idx[:, :, 0]).squeeze(-1)
+        stats.update(loss=li.sum().item(), v=q_act.sum().item(), count=B, td_abs=ce.detach(), q_act=q_act)
     elif head in (HEAD_Q_TD, HEAD_Q_DUEL):
         qs = dueling_q(out, A) if head == HEAD_Q_DUEL else out
         q = qs.gather(-1, act.long().unsqueeze(-1)).squeeze(-1)

@@ -62,6 +62,12 @@ the row's unweighted loss, as in Rainbow.  ``QVals`` is the mean of ``sum / NQ``
 refused: 16 outputs would leave CartPole 5 quantiles and the combination needs its own design.  ``quantiles = 0``
 launches the kernels it always launched, with the arguments it always passed.
 
+``atoms = NA >= 2`` with ``v_min < v_max`` is the categorical head of C51 (Bellemare et al. 2017) on the wide output
+layer (csrc/kernels/wide.h): nets of ``A * NA`` logits, the actor and the evaluator act on the expectations, ``y`` is
+the projected target distribution ``[B, NA]`` and ``GradHead.Q_C51`` applies the cross-entropy, whose unweighted row
+loss is the priority.  It composes with ``double_q``, ``prioritized`` and ``n_step`` and is refused with ``quantiles``,
+``dueling`` and ``noisy``; ``models.mlp_spec.c51_outputs`` has the tile limit.
+
 Left for later: quantiles with the dueling head, more than 16 outputs, per-env noise, several ranks, hipGraph
 capture, serving the policy to agents (the trainer exposes no ``learner``, so a TrainingServer engine publishes no
 model).
@@ -77,6 +83,7 @@ from ..algorithms.core import FlatNet
 from ..ops import GradHead, MLPSpec, ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_targets, grad_slabs, hip, mlp_grad
 from ..ops import PriorityTree, per_insert, per_update
 from ..ops import adam_step, noisy_compose, noisy_grad, noisy_sigma_init
+from ..models.mlp_spec import c51_outputs
 from ..parallel.comm import Comm
 from .rollout_learn import episode_metrics
 from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
@@ -128,6 +135,9 @@ class DQNConfig:
     noisy: bool = False             # NoisyNet exploration: W = mu + sigma * eps in all three layers
     noisy_sigma0: float = 0.5       # sigma starts at noisy_sigma0 / sqrt(fan_in)
     quantiles: int = 0              # QR-DQN: quantiles per action, A * quantiles <= 16 outputs (0: scalar DQN)
+    atoms: int = 0                  # C51: atoms per action on the wide output layer (0: off; mlp_spec.c51_outputs)
+    v_min: float = 0.0              # the support of the atoms: z_i = v_min + i * (v_max - v_min) / (atoms - 1)
+    v_max: float = 0.0
 
     def __post_init__(self):
         self.dueling = _as_bool("dueling", self.dueling)
@@ -160,6 +170,18 @@ class DQNConfig:
         if self.quantiles > 0 and not float(self.huber_delta) > 0.0:
             raise ValueError(f"quantiles needs huber_delta > 0 (the kappa of the quantile-Huber loss), got "
                              f"{self.huber_delta}")
+        try:
+            na = int(self.atoms)
+        except (TypeError, ValueError):
+            raise ValueError(f"atoms must be an integer, got {self.atoms!r}") from None
+        if isinstance(self.atoms, float) and na != self.atoms:
+            raise ValueError(f"atoms must be an integer, got {self.atoms!r}")
+        self.atoms, self.v_min, self.v_max = na, float(self.v_min), float(self.v_max)
+        if na != 0:  # with quantiles or dueling, atoms < 2, v_max <= v_min; the tile limit needs the env's actions
+            c51_outputs(1, na, self.v_min, self.v_max, self.dueling, self.quantiles)
+            if self.noisy:
+                raise ValueError(f"atoms = {na} with noisy = True is not built: the noisy layers hold at most 16 "
+                                 "outputs; set one of the two")
         if not 1 <= self.n_step <= int(self.buffer_slots):
             raise ValueError(f"n_step must be in [1, buffer_slots = {self.buffer_slots}], got {self.n_step}")
         self.prioritized = _as_bool("prioritized", self.prioritized)
@@ -233,14 +255,21 @@ class DQNTrainer:
         if A * NQ > MAX_Q_OUTPUTS:
             raise ValueError(f"quantiles needs A * quantiles <= {MAX_Q_OUTPUTS} outputs: {cfg.env!r} has {A} actions, "
                              f"so at most {MAX_Q_OUTPUTS // A} quantiles; got {NQ}")
+        NA = self.NA = int(cfg.atoms)
+        if NA:  # the tile limit: A * ceil(atoms / 16) <= 8
+            c51_outputs(A, NA, cfg.v_min, cfg.v_max, cfg.dueling, NQ)
         # the online net: the seeded init of PGLearner's policy, with its fused-Adam state; the dueling net
         # has one output more, the state value (row A); the quantile net NQ outputs per action
         g = torch.Generator().manual_seed(int(cfg.seed))
-        self.q = FlatNet(MLPSpec(D, H, A * NQ if NQ else A + 1 if cfg.dueling else A), cfg.q_lr, dev, g)
-        self.head = GradHead.Q_QR if NQ else GradHead.Q_DUEL if cfg.dueling else GradHead.Q_TD
+        self.q = FlatNet(MLPSpec(D, H, A * NA if NA else A * NQ if NQ else A + 1 if cfg.dueling else A), cfg.q_lr, dev, g)
+        self.head = (GradHead.Q_C51 if NA else GradHead.Q_QR if NQ else GradHead.Q_DUEL if cfg.dueling
+                     else GradHead.Q_TD)
         # what the head adds to the actor's, the evaluator's and the targets' calls; a plain trainer passes what it
         # always passed.  The gradient takes the head, and quantiles with it
         self._head_kw = dict(quantiles=NQ) if NQ else dict(dueling=True) if cfg.dueling else {}
+        self._grad_kw = dict(quantiles=NQ)
+        if NA:  # the categorical head: the same three keywords everywhere, the gradient included
+            self._head_kw = self._grad_kw = dict(atoms=NA, v_min=cfg.v_min, v_max=cfg.v_max)
         self.target = self.q.params.clone()
         self.theta = None
         if cfg.noisy:  # theta = [mu; sigma] with Adam state of 2P; the net's own tensors are its mu half
@@ -261,7 +290,7 @@ class DQNTrainer:
         B = cfg.batch_size
         self.Xb = torch.zeros(B, D, device=dev)
         self.act_b = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.y = torch.zeros((B, NQ) if NQ else (B,), device=dev)
+        self.y = torch.zeros((B, NA or NQ) if NA or NQ else (B,), device=dev)
         ns = grad_slabs(B, dev)
         self.slab = torch.zeros(ns, self.q.P, device=dev)
         self.loss = torch.zeros(ns, 8, device=dev)
@@ -348,7 +377,7 @@ class DQNTrainer:
                         self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None),
                         **nstep, **self._head_kw)
             mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
-                     clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, quantiles=self.NQ)
+                     clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, **self._grad_kw)
             self._apply()
         else:
             dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
@@ -356,7 +385,7 @@ class DQNTrainer:
                         out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep, **self._head_kw)
             mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
-                     w_norm=self.wmax, td_abs=self.td_abs, quantiles=self.NQ)
+                     w_norm=self.wmax, td_abs=self.td_abs, **self._grad_kw)
             self._apply()
             per_update(self.per, self.idx, self.td_abs, cfg.per_alpha, cfg.per_eps)
         self.updates += 1
@@ -408,7 +437,7 @@ class DQNTrainer:
                 loss_q, q_vals = ls[0] / ls[5], ls[4] / ls[5]
         out.update(LossQ=loss_q, QVals=q_vals, Epsilon=self.last_epsilon, Updates=self.updates,
                    EnvSteps=self.env_steps, WorldSize=1, NStep=self.cfg.n_step, Dueling=bool(self.cfg.dueling),
-                   Noisy=bool(self.cfg.noisy), Quantiles=int(self.cfg.quantiles))
+                   Noisy=bool(self.cfg.noisy), Quantiles=int(self.cfg.quantiles), Atoms=int(self.cfg.atoms))
         if self.theta is not None:
             out.update(SigmaMeanAbs=float(self.theta[self.q.P:].abs().mean().item()))
         if self.per is not None:
@@ -470,6 +499,10 @@ class DQNTrainer:
             raise ValueError(f"this trainer has quantiles={mine} ({self.q.P} parameters); the checkpoint has "
                              f"quantiles={theirs} ({got} parameters): build the trainer with the checkpoint's "
                              "quantiles setting")
+        mine, theirs = int(self.cfg.atoms), int(sd.get("cfg", {}).get("atoms", 0) or 0)  # absent: not categorical
+        if mine != theirs:
+            raise ValueError(f"this trainer has atoms={mine} ({self.q.P} parameters); the checkpoint has "
+                             f"atoms={theirs} ({got} parameters): build the trainer with the checkpoint's atoms setting")
         mine = bool(self.cfg.dueling)
         theirs = sd.get("cfg", {}).get("dueling")  # absent in a checkpoint from before the dueling head: plain
         if got != self.q.P or (theirs is not None and bool(theirs) != mine):

@@ -57,7 +57,8 @@ class EvalResult:
 
 def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, num_envs: int, greedy: bool = True,
                     seed: int = 0, step0: int = 0, max_episode_steps: Optional[int] = None, device=None,
-                    dueling: bool = False, quantiles: int = 0) -> EvalResult:
+                    dueling: bool = False, quantiles: int = 0, atoms: int = 0, v_min: float = 0.0,
+                    v_max: float = 0.0) -> EvalResult:
     """Score the flat policy weights ``params`` on the device env ``env``: ``num_envs`` envs x
     ``episodes`` complete episodes each, greedy (argmax / mean action) or sampled like training.
     Env resets and env noise come from the Philox stream ``(seed, step0 + t)``.
@@ -66,7 +67,11 @@ def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, 
     its advantage outputs; ``greedy=False`` raises.
 
     ``quantiles`` = NQ >= 1: ``params`` is a quantile Q-network (``A * NQ`` outputs) of a discrete env, scored
-    greedily on the per-action quantile sums; ``greedy=False`` and ``dueling`` raise."""
+    greedily on the per-action quantile sums; ``greedy=False`` and ``dueling`` raise.
+
+    ``atoms`` = NA >= 2 on the support ``[v_min, v_max]``: ``params`` is a categorical (C51) Q-network (``A * NA`` outputs)
+    of a discrete env, scored greedily on the per-action expectations; ``greedy=False``, ``dueling`` and ``quantiles``
+    raise (``models.mlp_spec.c51_outputs`` has the rule)."""
     from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
 
     if env not in DEVICE_ENVS:
@@ -84,6 +89,11 @@ def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, 
         raise ValueError(f"a quantile Q-network needs a discrete action space; {env!r} is continuous")
     if quantiles and not greedy:
         raise ValueError("a quantile Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
+    atoms = int(atoms)
+    if atoms and env in CONTINUOUS_DEVICE_ENVS:
+        raise ValueError(f"a categorical Q-network needs a discrete action space; {env!r} is continuous")
+    if atoms and not greedy:
+        raise ValueError("a categorical Q-network is evaluated greedily: softmax-of-Q is not this algorithm's policy")
     if device is None:
         device = params.device if params.is_cuda else torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -96,7 +106,8 @@ def evaluate_policy(env: str, params: torch.Tensor, hidden: int, episodes: int, 
     ep_ret, ep_len, ep_code, _ = evaluate_policy_op(DEVICE_ENVS[env], p, hidden, episodes, num_envs, greedy=greedy,
                                                     seed=seed, step0=step0, max_steps=max_episode_steps,
                                                     env_consts=consts, dueling=bool(dueling),
-                                                    **(dict(quantiles=quantiles) if quantiles else {}))
+                                                    **(dict(quantiles=quantiles) if quantiles else {}),
+                                                    **(dict(atoms=atoms, v_min=v_min, v_max=v_max) if atoms else {}))
     return EvalResult(ep_ret, ep_len, ep_code, greedy, seed, step0)
 
 
