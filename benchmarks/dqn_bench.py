@@ -55,6 +55,13 @@ against the scalar one at the shape of ``cartpole-dqn-nstep`` (with ``NA = 51`` 
 unless ``--out`` names another file.  ``--c51-learning EPOCHS`` instead records, for seeds 1..3 of
 ``cartpole-dqn-nstep``, ``cartpole-dqn-quantile`` and ``cartpole-dqn-c51``, the greedy mean return over 256 episodes
 every 100 epochs: one line per run in ``profiles/dqn_c51_learning.jsonl``.
+
+``--munchausen`` adds, from the same process, the microseconds per launch of the Munchausen (soft) ``dqn_targets`` against
+the hard-max one on the filled rings of ``cartpole-dqn``, ``-per``, ``-nstep`` and ``-quantile``
+(``dqn_targets_<preset>_<double_q|hard_max|soft>_us``); the line goes to ``profiles/dqn_munchausen_bench.jsonl`` unless
+``--out`` names another file.  ``--munchausen-learning EPOCHS`` instead records, for seeds 1..3 of ``cartpole-dqn-nstep``,
+``cartpole-dqn-munchausen``, ``cartpole-dqn-quantile`` and ``cartpole-dqn-munchausen-qr``, the greedy mean return over 256
+episodes every 100 epochs: one line per run in ``profiles/dqn_munchausen_learning.jsonl``.
 """
 import argparse
 import json
@@ -363,12 +370,52 @@ def quantile_learning(a, dev, presets=("cartpole-dqn-nstep", "cartpole-dqn-quant
                 if epoch % 100 == 0:
                     curve.append(round(tr.evaluate(episodes=1, num_envs=256).stats()["mean_return"], 1))
             lines.append(json.dumps(dict(preset=preset, quantiles=cfg.quantiles, atoms=cfg.atoms, n_step=cfg.n_step,
+                                         munchausen=cfg.munchausen,
                                          seed=seed, eval_every=100, env_steps_per_epoch=cfg.num_envs * cfg.rollout_len,
                                          greedy_mean_return_256=curve)))
             print(lines[-1], flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
         f.write("\n".join(lines) + "\n")
+
+
+def munchausen_records(a, dev, event_us):
+    """The Munchausen (soft) targets launch against the hard-max one in one process, per launch, on the filled ring
+    of ``cartpole-dqn`` (uniform, one-step), ``-per``, ``-nstep`` (prioritised, 3-step) and ``-quantile``: the preset's
+    own double-Q launch (two staged nets, two passes), the hard max of the target net alone (one pass) and the soft
+    target (one staged net, two trunk passes run as one pass over the weights)."""
+    from relayrl_prototype_amd.ops import dqn_targets
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    rec = dict(munchausen=0.9, m_tau=0.03, m_clip=-1.0)
+    for preset in ("cartpole-dqn", "cartpole-dqn-per", "cartpole-dqn-nstep", "cartpole-dqn-quantile"):
+        cfg = DQNConfig(**PRESETS[preset].overrides)
+        tr = DQNTrainer(cfg, device=dev)
+        for _ in range(a.warmup):
+            tr.train_epoch()
+        assert tr.updates > 0, "the warm-up must reach learning_starts"
+        N, B, C = cfg.num_envs, cfg.batch_size, cfg.buffer_slots
+        filled = min(tr.slots_written, C) * N
+        kw = dict(out=(tr.Xb, tr.act_b, tr.y, None), **tr._head_kw)
+        if tr.per is not None:
+            kw.update(tree=tr.per.tree, beta=0.7, out=(tr.Xb, tr.act_b, tr.y, tr.idx, tr.w, tr.wmax))
+        if cfg.n_step > 1:
+            kw.update(n_step=cfg.n_step, newest=(tr.cursor - 1) % C)
+        forms = (("double_q", True, {}), ("hard_max", False, {}),
+                 ("soft", False, dict(munchausen=0.9, m_tau=0.03, m_clip=-1.0)))
+        for form, double_q, soft in forms:
+            def targets():
+                dqn_targets(tr.q.params, tr.target, cfg.hidden, tr.A, tr.ring, filled, cfg.gamma, double_q,
+                            tr.sample_seed, 7, B, **kw, **soft)
+
+            targets()
+            torch.cuda.synchronize()
+            med, lo, hi = event_us(targets, a.iters, a.reps)
+            key = f"dqn_targets_{preset[len('cartpole-'):].replace('-', '_')}_{form}"
+            rec[key + "_us"] = med
+            rec[key + "_us_range"] = [lo, hi]
+    return rec
 
 
 def noisy_records(a, dev, event_us):
@@ -464,6 +511,10 @@ def main():
                     help="also measure the categorical head (C51) with NA atoms against the scalar one")
     ap.add_argument("--c51-learning", type=int, default=0, metavar="EPOCHS",
                     help="record greedy-return curves of cartpole-dqn-c51, -quantile and -nstep instead")
+    ap.add_argument("--munchausen", action="store_true",
+                    help="also measure the Munchausen (soft) targets launch against the hard-max one")
+    ap.add_argument("--munchausen-learning", type=int, default=0, metavar="EPOCHS",
+                    help="record greedy-return curves of cartpole-dqn-munchausen and -munchausen-qr beside their parents instead")
     a = ap.parse_args()
     if a.atoms and not 2 <= a.atoms <= 64:
         raise SystemExit("--atoms takes 2 .. 64 (CartPole has 2 actions and the wide layer 8 tiles of 16 outputs)")
@@ -472,8 +523,10 @@ def main():
     if any(k < 1 for k in a.n_step):
         raise SystemExit("--n-step takes values >= 1")
     if (a.prioritized or a.n_step or a.dueling or a.noisy or a.noisy_learning or a.quantiles
-            or a.quantile_learning or a.atoms or a.c51_learning) and not a.out:
+            or a.quantile_learning or a.atoms or a.c51_learning or a.munchausen or a.munchausen_learning) and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "dqn_munchausen_learning.jsonl" if a.munchausen_learning else
+                             "dqn_munchausen_bench.jsonl" if a.munchausen else
                              "dqn_c51_learning.jsonl" if a.c51_learning else
                              "dqn_c51_bench.jsonl" if a.atoms else
                              "dqn_quantile_learning.jsonl" if a.quantile_learning else
@@ -497,6 +550,9 @@ def main():
     if a.c51_learning:
         return quantile_learning(a, dev, ("cartpole-dqn-nstep", "cartpole-dqn-quantile", "cartpole-dqn-c51"),
                                  a.c51_learning)
+    if a.munchausen_learning:
+        return quantile_learning(a, dev, ("cartpole-dqn-nstep", "cartpole-dqn-munchausen", "cartpole-dqn-quantile",
+                                          "cartpole-dqn-munchausen-qr"), a.munchausen_learning)
     cfg = DQNConfig(**PRESETS["cartpole-dqn"].overrides)
     tr = DQNTrainer(cfg, device=dev)
     for _ in range(a.warmup):
@@ -557,6 +613,8 @@ def main():
         rec.update(quantile_records(a, dev, event_us))
     if a.atoms:
         rec.update(c51_records(a, dev, event_us))
+    if a.munchausen:
+        rec.update(munchausen_records(a, dev, event_us))
     rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
     line = json.dumps(rec)
     print(line, flush=True)

@@ -70,6 +70,19 @@ inline int64_t c51_outputs(int64_t A, int64_t atoms, double v_min, double v_max,
   return A * atoms;
 }
 
+// Munchausen targets (alpha = munchausen): alpha in [0, 1]; alpha > 0 needs a temperature > 0 and a clip < 0, has no
+// argmax for double_q to select and is built for the plain and the quantile net.  Returns whether they are on.
+inline bool munchausen_on(double munchausen, double m_tau, double m_clip, bool double_q, bool dueling, int64_t atoms) {
+  TORCH_CHECK(munchausen >= 0.0 && munchausen <= 1.0, "munchausen must be in [0, 1], got ", munchausen);
+  if (munchausen == 0.0) return false;
+  TORCH_CHECK(m_tau > 0.0, "munchausen needs m_tau > 0, got ", m_tau);
+  TORCH_CHECK(m_clip < 0.0, "munchausen needs m_clip < 0, got ", m_clip);
+  TORCH_CHECK(!double_q, "munchausen with double_q is not built: the soft target has no argmax to select");
+  TORCH_CHECK(!dueling, "munchausen with dueling is not built: set one of the two");
+  TORCH_CHECK(atoms == 0, "munchausen with atoms is not built: set one of the two");
+  return true;
+}
+
 // Floats of MLPSpec(D, H, A) (+ log_std).
 inline int64_t flat_size(int64_t D, int64_t H, int64_t A, bool log_std = false) {
   return H * D + H + H * H + H + A * H + A + (log_std ? A : 0);

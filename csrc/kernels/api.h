@@ -54,6 +54,8 @@ struct DqnTargetsCall {
   int quantiles;                 // 0: the scalar forms above; NQ >= 1: nets MLPSpec(D, H, A * NQ) and y [B][NQ]
   int atoms;                     // 0, or NA >= 2: categorical nets MLPSpec(D, H, A * NA) and y [B][NA]
   float v_min, v_max;            // the support of the atoms: z_i = v_min + i * (v_max - v_min) / (NA - 1)
+  float munchausen;              // 0: the hard-max targets above; alpha in (0, 1]: Munchausen targets (scalar or quantile)
+  float m_tau, m_clip;           // with munchausen > 0: the temperature (> 0) and the lower clip of tau * log pi (< 0)
 };
 
 // The arguments of rrl_mlp_grad, which has the contract.
@@ -253,7 +255,14 @@ int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, in
 // (HEAD_Q_QR), a* is the argmax of the selecting net's per-action quantile sums, y is [B][NQ] and
 //   y[b][j] = G + disc * (done[last] == 1 ? 0 : 1) * theta_target(nobs[last])[a* * NQ + j]
 // (at n_step == 1: rew[r0] + gamma * ...); again only y depends on it.  -3 also for quantiles < 0, quantiles with
-// dueling, or A * NQ > 16.  Refusals write nothing and are checked in this order.
+// dueling, or A * NQ > 16.
+// munchausen = alpha in (0, 1] (Munchausen RL; dqn.hip has the definition): on the scalar or the quantile net, with
+// q[a] the target net's Q-values (the mean of the action's quantiles), tlp[a] = (q[a] - max q) - m_tau * log sum_a
+// exp((q[a] - max q) / m_tau) and pi = softmax(q / m_tau),
+//   y[b][j] = (G + alpha * clamp(tlp(obs[r0])[act[r0]], m_clip, 0)) + disc * boot * sum_a pi[a] * (theta[a][j] - tlp[a])
+// with pi, tlp, theta at nobs[last]; online is not read and only y depends on it.  -3 for munchausen outside [0, 1]
+// and, with munchausen > 0, for m_tau <= 0, m_clip >= 0, double_q, dueling or atoms; munchausen = 0 ignores m_tau
+// and m_clip and launches the hard-max kernels.  Refusals write nothing and are checked in this order.
 // -1: a null pointer (online with double_q; idx, w, wmax with a tree; idx with last at n_step == 1); -2: B < 1,
 // filled outside [1, 2^31) or, with a tree, outside [1, L], L outside [1, 2^30]; -3: H not 64 / 128, D outside
 // [1, 16], A < 1 or A + dueling > 16; -2: n_step < 1, N < 1 or filled % N != 0; -4: newest outside [0, filled / N)

@@ -466,6 +466,223 @@ __global__ __launch_bounds__(256, 1) void dqn_targets_kernel(DqnTargetArgsOf<NST
   }
 }
 
+// ------------------------------------------------------------------ Munchausen (soft) targets
+// Munchausen RL (Vieillard, Pietquin, Geist 2020) changes only the target.  With q[0..A) the target net's Q-values
+// (on a quantile net the MEAN of each action's quantiles: the ascending sum of quantile_sum, then one division by NQ),
+// all in fp32, a ascending, with the precise expf / logf:
+//   mx = max_a q[a];  d[a] = q[a] - mx;  S = sum_a expf(d[a] / tau);  lse = logf(S)        (S >= 1: the max adds 1)
+//   tlp[a] = d[a] - tau * lse   (tau * log pi(a));   pi[a] = expf(d[a] / tau) / S
+//   bonus = alpha * clamp(tlp at obs[r0] of act[r0], clip, 0)                               act clamped into [0, A)
+//   V     = sum_a pi[a] * (q[a] - tlp[a])                          at nobs[last]            scalar net
+//   V_j   = sum_a pi[a] * (theta[a * NQ + j] - tlp[a])             at nobs[last]            quantile net, j < NQ
+//   y     = (G + bonus) + disc * boot * V                          G, disc, boot, last: those of dqn_targets_kernel
+// The bonus is added once, for the sampled transition, whatever n_step is.  There is no argmax, hence no online pass
+// and nothing parked between passes: the target net is staged once and every batch row takes TWO trunk passes
+// through that one LDS image, obs[r0] and nobs[last].  They run as one pass over the weights (dense_fwd2): each weight
+// fragment is read from LDS once and feeds the MFMA of either row tile, and the two accumulate chains are
+// independent, so one covers the other's latency.  The registers that hold the obs[r0] tile for the forward pass
+// (feature 4k + g in lane group g) are the ones stored to Xb[b]: the row is read from the ring once.
+// Sampling, the walk and every output but y are those of dqn_targets_kernel, bit for bit (the store tail is repeated
+// here so that its instances keep their code).
+template <class Base>
+struct DqnSoftArgs : Base {
+  float alpha = 0.f;  // scale of the bonus, in (0, 1]
+  float tau = 1.f;    // entropy temperature, > 0
+  float clip = -1.f;  // lower clip of tau * log pi, < 0
+};
+
+template <bool NSTEP, bool QR>
+using DqnSoftArgsOf = std::conditional_t<QR, DqnQrArgs<DqnSoftArgs<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>>,
+                                         DqnSoftArgs<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>>>;
+
+// dense_fwd (with the ReLU) for two row tiles at once: the same loads of W, one MFMA per tile and weight fragment.
+// Each tile's accumulate order is dense_fwd's, so its result is dense_fwd's bit for bit.
+template <int NI, int NO>
+RRL_DEV void dense_fwd2(const float* __restrict__ W, int S, const float* __restrict__ b, const floatx4 (&in0)[NI],
+                        const floatx4 (&in1)[NI], floatx4 (&out0)[NO], floatx4 (&out1)[NO], int kr_last = 4) {
+  const int l = lane_id();
+  const int i = l & 15, g = l >> 4;
+#pragma unroll
+  for (int to = 0; to < NO; ++to) out0[to] = out1[to] = *reinterpret_cast<const floatx4*>(b + 16 * to + 4 * g);
+  floatx4 wc[NO], wn[NO];
+#pragma unroll
+  for (int to = 0; to < NO; ++to) wc[to] = *reinterpret_cast<const floatx4*>(W + (16 * to + i) * S + 4 * g);
+#pragma unroll
+  for (int ti = 0; ti < NI; ++ti) {
+    if (ti + 1 < NI) {
+#pragma unroll
+      for (int to = 0; to < NO; ++to)
+        wn[to] = *reinterpret_cast<const floatx4*>(W + (16 * to + i) * S + 16 * (ti + 1) + 4 * g);
+    }
+    const int kr = (ti == NI - 1) ? kr_last : 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (r < kr) {
+#pragma unroll
+        for (int to = 0; to < NO; ++to) {
+          out0[to] = mfma4(wc[to][r], in0[ti][r], out0[to]);
+          out1[to] = mfma4(wc[to][r], in1[ti][r], out1[to]);
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (ti + 1 < NI) {
+#pragma unroll
+      for (int to = 0; to < NO; ++to) wc[to] = wn[to];
+    }
+  }
+#pragma unroll
+  for (int to = 0; to < NO; ++to) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      out0[to][r] = fmaxf(out0[to][r], 0.f);
+      out1[to][r] = fmaxf(out1[to][r], 0.f);
+    }
+  }
+}
+
+// policy_forward for the two row tiles x0, x1 of one column of rows.
+template <int HT>
+RRL_DEV void soft_forward2(const float* __restrict__ lds, const floatx4 (&x0)[1], const floatx4 (&x1)[1], int kr_last,
+                           int AO, float (&out0)[kMaxAct], float (&out1)[kMaxAct]) {
+  using L = LdsNet<1, HT>;
+  floatx4 a1[HT], b1[HT], a2[HT], b2[HT];
+  dense_fwd2<1, HT>(lds + L::W1, L::S1, lds + L::B1, x0, x1, a1, b1, kr_last);
+  dense_fwd2<HT, HT>(lds + L::W2, L::S2, lds + L::B2, a1, b1, a2, b2);
+  policy_logits<HT>(lds + L::W3, lds + L::B3, AO, L::H, a2, out0);
+  policy_logits<HT>(lds + L::W3, lds + L::B3, AO, L::H, b2, out1);
+}
+
+// tlp and pi of one row's AO = A * NQ outputs (NQ = 1: a scalar net), held at every register of the action, so that
+// the callers' unrolled walks never index a register array by a variable.  The walk over the 16 registers carries a
+// quantile counter, as quantile_sum does: the last register of an action closes its ascending sum, `ends` has a bit
+// for each such register, and the max, S and the terms run over those registers in ascending order.
+RRL_DEV void soft_terms(int AO, int NQ, float tau, const float (&out)[kMaxAct], float (&tlp)[kMaxAct],
+                        float (&pi)[kMaxAct]) {
+  float q[kMaxAct], e[kMaxAct];
+  uint32_t ends = 0;
+  int i = 0;
+  float s = 0.f, mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < kMaxAct; ++k) {
+    q[k] = 0.f;
+    if (k < AO) {
+      s = (i == 0) ? out[k] : s + out[k];
+      if (++i == NQ) {
+        q[k] = s / (float)NQ;
+        mx = fmaxf(mx, q[k]);
+        ends |= 1u << k;
+        i = 0;
+      }
+    }
+  }
+  float S = 0.f;
+#pragma unroll
+  for (int k = 0; k < kMaxAct; ++k) {
+    e[k] = 0.f;
+    if ((ends >> k) & 1u) {
+      e[k] = expf((q[k] - mx) / tau);
+      S += e[k];
+    }
+  }
+  const float lse = logf(S);
+  float t = 0.f, pr = 0.f;
+#pragma unroll
+  for (int k = kMaxAct - 1; k >= 0; --k) {  // downwards: an action's registers take the values of its last one
+    if ((ends >> k) & 1u) {
+      t = (q[k] - mx) - tau * lse;
+      pr = e[k] / S;
+    }
+    tlp[k] = t;
+    pi[k] = pr;
+  }
+}
+
+template <int HT, bool PER, bool NSTEP, bool QR>
+__global__ __launch_bounds__(256, 1) void dqn_soft_targets_kernel(DqnSoftArgsOf<NSTEP, QR> p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int l = lane_id();
+  const int j = l & 15, g = l >> 4;
+  const int wave = threadIdx.x >> 6;
+  int NQ = 1;
+  if constexpr (QR) NQ = p.NQ;
+  const int AO = p.A * NQ;
+
+  stage_net<1, HT>(lds, p.target, p.D, AO, false);
+  __syncthreads();
+  for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
+    const int b = base + 16 * wave + j;
+    const bool ok = b < p.B;
+    size_t r = 0;
+    if (ok) r = PER ? per_sample_row(b, p) : dqn_sample_row(b, p);
+    size_t last = r;
+    float G = 0.f, disc = p.gamma;
+    if (ok) {
+      if constexpr (NSTEP) {
+        const NStepWalk w = dqn_nstep_walk((uint32_t)r, p);
+        last = w.last, G = w.G, disc = w.disc;
+      } else {
+        G = p.rew[r];
+      }
+    }
+    floatx4 x0[1], x1[1];
+    const float* row0 = p.obs + r * (size_t)p.D;
+    const float* row1 = p.nobs + last * (size_t)p.D;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int f = 4 * k + g;
+      x0[0][k] = (ok && f < p.D) ? row0[f] : 0.f;
+      x1[0][k] = (ok && f < p.D) ? row1[f] : 0.f;
+    }
+    float out0[kMaxAct], out1[kMaxAct];
+    soft_forward2<HT>(lds, x0, x1, (p.D + 3) >> 2, AO, out0, out1);
+
+    // the head, replicated in the four lane groups: the bonus from obs[r0], then the soft values from nobs[last]
+    float tlp[kMaxAct], pi[kMaxAct];
+    soft_terms(AO, NQ, p.tau, out0, tlp, pi);
+    const int a0 = ok ? min(max(p.act[r], 0), p.A - 1) : 0;
+    float tlp0 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kMaxAct; ++k)
+      if (k == a0 * NQ) tlp0 = tlp[k];
+    const float head = G + p.alpha * fminf(fmaxf(tlp0, p.clip), 0.f);
+    soft_terms(AO, NQ, p.tau, out1, tlp, pi);
+    const float boot = (ok && p.done[last] == 1.f) ? 0.f : 1.f;
+    for (int jq = 0; jq < NQ; ++jq) {  // one target live at a time
+      float V = 0.f;
+      int i = 0;
+#pragma unroll
+      for (int k = 0; k < kMaxAct; ++k)
+        if (k < AO) {
+          if (i == jq) V += pi[k] * (out1[k] - tlp[k]);
+          if (++i == NQ) i = 0;
+        }
+      if (ok && g == 0) p.y[(size_t)b * NQ + jq] = head + disc * boot * V;
+    }
+    if (ok) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int f = 4 * k + g;
+        if (f < p.D) p.Xb[(size_t)b * p.D + f] = x0[0][k];
+      }
+      if (g == 0) {
+        if constexpr (NSTEP) {
+          if (p.last != nullptr) p.last[b] = (int)last;
+        }
+        p.act_b[b] = p.act[r];
+        if (p.idx != nullptr) p.idx[b] = (int)r;
+        if (PER) {
+          const float leaf = p.tree[p.P2 + r], total = p.tree[1];
+          // a walk on a sound tree ends on a positive leaf; anything else weighs like the uniform sampler
+          const float wb = (leaf > 0.f && total > 0.f) ? powf((float)p.filled * leaf / total, -p.beta) : 1.f;
+          p.w[b] = wb;
+          atomicMax(p.wmax, __float_as_int(wb));
+        }
+      }
+    }
+  }
+}
+
 }  // namespace rrl
 
 using namespace rrl;
@@ -635,6 +852,41 @@ static int dispatch_c51_targets(const DqnNStepArgs& a, const C51Support& sup, in
   }
 }
 
+// The Munchausen instances of (H, PER, NSTEP, QR): the same blocks with alpha, tau and the clip behind them (and NQ
+// behind those); NQ = 0 is the scalar net.
+template <int HT, bool PER, bool NSTEP, bool QR>
+static int launch_soft_targets(const DqnNStepArgs& a, const DqnTargetsCall& c, int grid, hipStream_t s) {
+  DqnSoftArgsOf<NSTEP, QR> q;
+  static_cast<std::conditional_t<NSTEP, DqnNStepArgs, DqnTargetArgs>&>(q) = a;
+  q.alpha = c.munchausen;
+  q.tau = c.m_tau;
+  q.clip = c.m_clip;
+  int outputs = a.A;
+  if constexpr (QR) {
+    q.NQ = c.quantiles;
+    outputs = a.A * c.quantiles;
+  }
+  raise_lds_limit<dqn_soft_targets_kernel<HT, PER, NSTEP, QR>>();
+  const size_t bytes = (size_t)LdsNet<1, HT>::floats(outputs) * sizeof(float);
+  hipLaunchKernelGGL((dqn_soft_targets_kernel<HT, PER, NSTEP, QR>), dim3(grid), dim3(256), bytes, s, q);
+  return (int)hipGetLastError();
+}
+
+template <bool QR>
+static int dispatch_soft_targets(const DqnNStepArgs& a, const DqnTargetsCall& c, bool per, bool nstep, int grid,
+                                 hipStream_t s) {
+  switch ((per ? 4 : 0) | (nstep ? 2 : 0) | (c.H == 128 ? 1 : 0)) {
+    case 0: return launch_soft_targets<4, false, false, QR>(a, c, grid, s);
+    case 1: return launch_soft_targets<8, false, false, QR>(a, c, grid, s);
+    case 2: return launch_soft_targets<4, false, true, QR>(a, c, grid, s);
+    case 3: return launch_soft_targets<8, false, true, QR>(a, c, grid, s);
+    case 4: return launch_soft_targets<4, true, false, QR>(a, c, grid, s);
+    case 5: return launch_soft_targets<8, true, false, QR>(a, c, grid, s);
+    case 6: return launch_soft_targets<4, true, true, QR>(a, c, grid, s);
+    default: return launch_soft_targets<8, true, true, QR>(a, c, grid, s);
+  }
+}
+
 static int dqn_targets_grid(int B, int num_cu) {
   int grid = (B + 63) / 64;
   const int cap = num_cu > 0 ? num_cu : 256;
@@ -659,6 +911,11 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
     tpa = c51_support(c->A, c->atoms, c->v_min, c->v_max, &sup);
     if (tpa == 0) return -3;
   }
+  // Munchausen targets: alpha in [0, 1]; alpha > 0 needs tau > 0 and a clip < 0, has no argmax for double_q to select
+  // and is built for the plain and the quantile net
+  const bool soft = c->munchausen > 0.f;
+  if (!(c->munchausen >= 0.f && c->munchausen <= 1.f)) return -3;
+  if (soft && (!(c->m_tau > 0.f) || !(c->m_clip < 0.f) || c->double_q || duel || c->atoms != 0)) return -3;
   if (c->n_step < 1 || c->N < 1 || c->filled % c->N != 0) return -2;
   if (c->newest < 0 || c->newest >= c->filled / c->N) return -4;
   DqnNStepArgs a;
@@ -685,7 +942,10 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
   }
   const int grid = dqn_targets_grid(c->B, num_cu);
   int rc;
-  if (tpa > 0) {
+  if (soft) {
+    rc = NQ > 0 ? dispatch_soft_targets<true>(a, *c, per, nstep, grid, s)
+                : dispatch_soft_targets<false>(a, *c, per, nstep, grid, s);
+  } else if (tpa > 0) {
     rc = dispatch_tpa<kMaxTpa>(tpa, [&](auto w) {
       return dispatch_c51_targets<decltype(w)::TPA>(a, sup, c->H, per, nstep, grid, s);
     });

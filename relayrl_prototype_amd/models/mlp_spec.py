@@ -45,6 +45,30 @@ def c51_outputs(A: int, atoms: int, v_min: float, v_max: float, dueling: bool = 
     return A * NA
 
 
+def munchausen_on(munchausen: float, m_tau: float, m_clip: float, double_q: bool = False, dueling: bool = False,
+                  atoms: int = 0) -> bool:
+    """Whether the Munchausen targets are on (``munchausen`` = alpha > 0), and whether the kernels have the
+    combination: alpha in [0, 1]; alpha > 0 needs ``m_tau`` > 0 and ``m_clip`` < 0, has no argmax for ``double_q`` to
+    select and is built for the plain and the quantile net.  Raises ``ValueError`` naming the fields otherwise."""
+    alpha = float(munchausen)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"munchausen must be in [0, 1], got {munchausen}")
+    if alpha == 0.0:
+        return False
+    if not float(m_tau) > 0.0:
+        raise ValueError(f"munchausen = {alpha} needs m_tau > 0, got {m_tau}")
+    if not float(m_clip) < 0.0:
+        raise ValueError(f"munchausen = {alpha} needs m_clip < 0, got {m_clip}")
+    if double_q:
+        raise ValueError(f"munchausen = {alpha} with double_q = True is not built: the soft target has no argmax to "
+                         "select; set double_q=False")
+    if dueling:
+        raise ValueError(f"munchausen = {alpha} with dueling = True is not built: set one of the two")
+    if int(atoms):
+        raise ValueError(f"munchausen = {alpha} with atoms = {atoms} is not built: set one of the two")
+    return True
+
+
 @dataclass(frozen=True)
 class MLPSpec:
     """Linear(D,H)-ReLU-Linear(H,H)-ReLU-Linear(H,A) [+ log_std(A)]."""

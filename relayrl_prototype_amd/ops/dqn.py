@@ -18,7 +18,7 @@ import torch
 
 from . import philox
 from . import reference as ref
-from ..models.mlp_spec import MLPSpec, c51_outputs, q_outputs
+from ..models.mlp_spec import MLPSpec, c51_outputs, munchausen_on, q_outputs
 
 
 class ReplayRing(NamedTuple):
@@ -172,7 +172,8 @@ def dqn_nstep_walk_ref(rows, ring: ReplayRing, filled: int, newest: int, n_step:
 def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: int, gamma: float, double_q: bool,
                     seed: int, update: int, B: int, dtype=torch.float32, tree=None, beta: Optional[float] = None,
                     n_step: int = 1, newest: Optional[int] = None, dueling: bool = False, quantiles: int = 0,
-                    atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0):
+                    atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0, munchausen: float = 0.0,
+                    m_tau: float = 0.03, m_clip: float = -1.0):
     """-> ``(Xb [B, D], act_b [B] int32, y [B], idx [B] int64)`` in ``dtype``;
     ``y = rew + gamma * (done == 1 ? 0 : 1) * Q_target(nobs, a*)`` with ``a*`` the lowest-index argmax of the
     target (``double_q`` false) or online net.  With ``tree`` (the priority sum tree of ops/per.py) the rows
@@ -194,9 +195,21 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
     ``atoms`` = NA >= 2: both nets are categorical nets of ``A * NA`` outputs on ``[v_min, v_max]``, ``a*`` is the
     lowest-index argmax of the selecting net's expectations (``reference.c51_q``) and ``y`` is m [B, NA], the projection
     (``reference.c51_project``) of the target net's distribution of ``a*`` through ``Tz_j = G + disc * boot * z_j``.
-    Again everything but ``y`` is that of the scalar call."""
+    Again everything but ``y`` is that of the scalar call.
+
+    ``munchausen`` = alpha > 0 (scalar and quantile nets, no ``double_q``; ``munchausen_on`` has the rule): the
+    Munchausen target.  With ``q`` the target net's Q-values (on a quantile net the mean ``quantile_q / NQ``) and
+    ``(tlp, pi) = reference.munchausen_terms(q, m_tau)``,
+
+        bonus = alpha * clamp(tlp(obs[r0])[act[r0]], m_clip, 0)                  # act clamped into [0, A)
+        y[b, j] = (G + bonus) + disc * boot * sum_a pi[a] * (theta[a, j] - tlp[a])        # pi, tlp, theta at nobs[last]
+
+    ``a`` ascending (a scalar net has ``theta = q`` and one target per row).  The bonus is added once, for the sampled
+    transition, whatever ``n_step`` is; ``online`` is not read.  float64 is the oracle, float32 repeats the kernel's
+    order."""
     D = ring.obs.shape[-1]
     dev = ring.obs.device
+    soft = munchausen_on(munchausen, m_tau, m_clip, double_q, dueling, atoms)
     NA = check_atoms(A, atoms, v_min, v_max, dueling, quantiles) if atoms else 0
     NQ = check_quantiles(A, quantiles, dueling)
     _check_q_nets(online if double_q else None, target, D, H, A, dueling, NQ, NA)
@@ -218,7 +231,24 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
                          for x in dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)[:3])
     nobs = ring.nobs.reshape(-1, D)[last].to(dtype)
     boot = (ring.done.reshape(-1)[last] != 1).to(dtype)
-    if NA > 0:
+    if soft:
+        AO, n = q_outputs(A, False, NQ), max(NQ, 1)
+        tgt = target.to(dtype)
+        mean = (lambda out: ref.quantile_q(out, A, NQ) / torch.tensor(float(NQ), dtype=dtype)) if NQ else (lambda out: out)
+        out0 = ref.trunk(tgt, ring.obs.reshape(-1, D)[idx].to(dtype), D, H, AO)[0]
+        a0 = ring.act.reshape(-1)[idx].long().clamp(0, A - 1)
+        tlp0 = ref.munchausen_terms(mean(out0), m_tau)[0].gather(-1, a0.unsqueeze(-1)).squeeze(-1)
+        head = G + torch.tensor(float(munchausen), dtype=dtype) * tlp0.clamp(float(m_clip), 0.0)
+        out1 = ref.trunk(tgt, nobs, D, H, AO)[0]
+        tlp, pi = ref.munchausen_terms(mean(out1), m_tau)
+        theta = out1.reshape(-1, A, n)
+        V = torch.zeros(theta.shape[0], n, dtype=dtype, device=dev)
+        for a in range(A):
+            V = V + pi[:, a, None] * (theta[:, a, :] - tlp[:, a, None])
+        db = (disc * boot).unsqueeze(-1)
+        y = head.unsqueeze(-1) + db * V
+        y = y if NQ else y.squeeze(-1)
+    elif NA > 0:
         q_t, p_t = ref.c51_q(ref.trunk(target.to(dtype), nobs, D, H, A * NA)[0], A, NA, v_min, v_max)
         q_sel = ref.c51_q(ref.trunk(online.to(dtype), nobs, D, H, A * NA)[0], A, NA, v_min, v_max)[0] if double_q else q_t
         astar, _ = ref.greedy_from_logits(q_sel)
@@ -263,7 +293,8 @@ def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
 def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
                 gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32,
                 tree=None, beta: Optional[float] = None, n_step: int = 1, newest: Optional[int] = None,
-                dueling: bool = False, quantiles: int = 0, atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0):
+                dueling: bool = False, quantiles: int = 0, atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0,
+                munchausen: float = 0.0, m_tau: float = 0.03, m_clip: float = -1.0):
     """Sample, gather and TD target in one launch -> ``(Xb, act_b, y, idx)``; ``out`` = the four tensors to
     write into (``idx`` int32 on the GPU, or None to skip it).  CPU tensors take the torch reference in
     ``dtype``; a GPU tensor without the extension raises.
@@ -287,11 +318,17 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
 
     ``atoms`` = NA >= 2 (with ``v_min < v_max``) selects the categorical instances on the wide output layer: ``online`` /
     ``target`` are ``MLPSpec(D, H, A * NA)`` nets and ``y`` is the projected distribution m [B, NA] (``dqn_targets_ref``
-    has the semantics); only ``y`` differs from the scalar launch.  It is refused with ``dueling`` or ``quantiles``."""
+    has the semantics); only ``y`` differs from the scalar launch.  It is refused with ``dueling`` or ``quantiles``.
+
+    ``munchausen`` = alpha in (0, 1] selects the Munchausen instances (``dqn_targets_ref`` has the semantics; ``m_tau`` > 0
+    the temperature, ``m_clip`` < 0 the clip of the bonus): the target net alone is staged and evaluated at ``obs[r0]``
+    and ``nobs[last]``, on a scalar or a quantile net, and only ``y`` differs from the hard-max launch.  It is refused
+    with ``double_q``, ``dueling`` or ``atoms``; ``munchausen = 0`` is the hard-max launch as it was."""
     from . import use_hip, hip
 
     per = tree is not None
     dueling = bool(dueling)
+    soft = munchausen_on(munchausen, m_tau, m_clip, double_q, dueling, atoms)
     NA = check_atoms(A, atoms, v_min, v_max, dueling, quantiles) if atoms else 0
     NQ = check_quantiles(A, quantiles, dueling) if quantiles else 0
     _check_q_nets(online if double_q else None, target, ring.obs.shape[-1], H, A, dueling, NQ, NA)
@@ -310,7 +347,7 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
         raise ValueError("at n_step = 1 last is idx: it cannot be written without idx")
     if not use_hip(target):
         res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
-                              n_step, newest, dueling, NQ, NA, v_min, v_max)
+                              n_step, newest, dueling, NQ, NA, v_min, v_max, munchausen, m_tau, m_clip)
         if out is None:
             return res
         if n_step == 1:
@@ -332,12 +369,15 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
     if per and out[3] is None:
         raise ValueError("the prioritised form writes idx: it cannot be skipped")
     w, wmax = out[4:6] if per else (None, None)
-    # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling, quantiles, atoms, v_min, v_max)
-    # in its order: a
-    # positional call parses faster than a keyword one, and this is the one place that makes it
+    # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling, quantiles, atoms, v_min, v_max,
+    # munchausen, m_tau, m_clip) in its order: a positional call parses faster than a keyword one, and this is the one
+    # place that makes it; a hard-max call passes what it always passed
+    tail = (NA, float(v_min), float(v_max)) if NA or soft else ()
+    if soft:
+        tail += (float(munchausen), float(m_tau), float(m_clip))
     hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
                       ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), *out[:4], tree,
                       float(beta) if per else None, w, wmax, n_step, newest,
                       out[base] if len(out) > base else None, dueling, NQ,
-                      *((NA, float(v_min), float(v_max)) if NA else ()))
+                      *tail)
     return out

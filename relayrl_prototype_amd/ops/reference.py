@@ -165,6 +165,23 @@ def quantile_q(out: torch.Tensor, A: int, NQ: int) -> torch.Tensor:
     return s
 
 
+def munchausen_terms(q: torch.Tensor, tau: float):
+    """The soft-policy terms of Munchausen RL for Q-values ``q`` [..., A] -> ``(tlp, pi)``, both [..., A], in ``q``'s
+    dtype and the kernels' operation order (rrl::soft_terms), ``a`` ascending:
+
+        mx = max_a q[a];  d[a] = q[a] - mx;  S = sum_a exp(d[a] / tau);  lse = log(S)
+        tlp[a] = d[a] - tau * lse          # tau * log pi(a): S >= 1, never the log of a small pi
+        pi[a]  = exp(d[a] / tau) / S"""
+    t = torch.tensor(float(tau), dtype=q.dtype, device=q.device)
+    d = q - q.max(dim=-1, keepdim=True).values
+    e = torch.exp(d / t)
+    S = e[..., 0]
+    for a in range(1, q.shape[-1]):
+        S = S + e[..., a]
+    S = S.unsqueeze(-1)
+    return d - t * torch.log(S), e / S
+
+
 def _stepwise(dtype):
     """Categorical-head oracles work on float64 tensors; in float32 every operation's result is rounded to fp32, which
     turns ``a * b + c`` into the kernels' fused multiply-add (the float64 product of two fp32 values is exact)."""

@@ -68,7 +68,16 @@ the projected target distribution ``[B, NA]`` and ``GradHead.Q_C51`` applies the
 loss is the priority.  It composes with ``double_q``, ``prioritized`` and ``n_step`` and is refused with ``quantiles``,
 ``dueling`` and ``noisy``; ``models.mlp_spec.c51_outputs`` has the tile limit.
 
-Left for later: quantiles with the dueling head, more than 16 outputs, per-env noise, several ranks, hipGraph
+``munchausen = alpha > 0`` is Munchausen RL (Vieillard et al. 2020), a change of the target alone: ``dqn_targets`` adds
+``alpha * clamp(m_tau * log pi(a | s), m_clip, 0)`` of the sampled transition to the reward and bootstraps from the
+entropy-regularised expectation ``sum_a pi (q - m_tau log pi)`` of the target net instead of its maximum, ``pi`` the
+softmax of the target net's Q-values at temperature ``m_tau`` (M-DQN on the scalar net, per quantile on the quantile
+net).  The soft target has no argmax, so ``double_q`` must be off and no selecting net is composed or staged; the actor,
+the evaluator, the gradient heads, Adam and the tree are those of the hard-max run.  It composes with ``prioritized``,
+``n_step``, ``noisy`` and ``quantiles`` and is refused with ``double_q``, ``dueling`` and ``atoms``.
+
+Left for later: Munchausen targets with the dueling or the categorical head, a bonus per step of the n-step walk, a
+Boltzmann actor, quantiles with the dueling head, more than 16 outputs, per-env noise, several ranks, hipGraph
 capture, serving the policy to agents (the trainer exposes no ``learner``, so a TrainingServer engine publishes no
 model).
 """
@@ -83,7 +92,7 @@ from ..algorithms.core import FlatNet
 from ..ops import GradHead, MLPSpec, ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_targets, grad_slabs, hip, mlp_grad
 from ..ops import PriorityTree, per_insert, per_update
 from ..ops import adam_step, noisy_compose, noisy_grad, noisy_sigma_init
-from ..models.mlp_spec import c51_outputs
+from ..models.mlp_spec import c51_outputs, munchausen_on
 from ..parallel.comm import Comm
 from .rollout_learn import episode_metrics
 from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
@@ -138,6 +147,9 @@ class DQNConfig:
     atoms: int = 0                  # C51: atoms per action on the wide output layer (0: off; mlp_spec.c51_outputs)
     v_min: float = 0.0              # the support of the atoms: z_i = v_min + i * (v_max - v_min) / (atoms - 1)
     v_max: float = 0.0
+    munchausen: float = 0.0         # Munchausen targets: the scale alpha of the log-policy bonus (0: hard-max targets)
+    m_tau: float = 0.03             # their entropy temperature, > 0
+    m_clip: float = -1.0            # the lower clip of m_tau * log pi in the bonus, < 0
 
     def __post_init__(self):
         self.dueling = _as_bool("dueling", self.dueling)
@@ -182,6 +194,13 @@ class DQNConfig:
             if self.noisy:
                 raise ValueError(f"atoms = {na} with noisy = True is not built: the noisy layers hold at most 16 "
                                  "outputs; set one of the two")
+        for k in ("munchausen", "m_tau", "m_clip"):
+            try:
+                setattr(self, k, float(getattr(self, k)))
+            except (TypeError, ValueError):
+                raise ValueError(f"{k} must be a number, got {getattr(self, k)!r}") from None
+        self.double_q = _as_bool("double_q", self.double_q)  # "false" must switch it off for the soft target
+        munchausen_on(self.munchausen, self.m_tau, self.m_clip, self.double_q, self.dueling, self.atoms)
         if not 1 <= self.n_step <= int(self.buffer_slots):
             raise ValueError(f"n_step must be in [1, buffer_slots = {self.buffer_slots}], got {self.n_step}")
         self.prioritized = _as_bool("prioritized", self.prioritized)
@@ -270,6 +289,9 @@ class DQNTrainer:
         self._grad_kw = dict(quantiles=NQ)
         if NA:  # the categorical head: the same three keywords everywhere, the gradient included
             self._head_kw = self._grad_kw = dict(atoms=NA, v_min=cfg.v_min, v_max=cfg.v_max)
+        # what only the targets take; a hard-max trainer passes what it always passed
+        self._soft_kw = (dict(munchausen=cfg.munchausen, m_tau=cfg.m_tau, m_clip=cfg.m_clip) if cfg.munchausen > 0
+                         else {})
         self.target = self.q.params.clone()
         self.theta = None
         if cfg.noisy:  # theta = [mu; sigma] with Adam state of 2P; the net's own tensors are its mu half
@@ -375,14 +397,15 @@ class DQNTrainer:
         if self.per is None:
             dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, out=(self.Xb, self.act_b, self.y, None),
-                        **nstep, **self._head_kw)
+                        **nstep, **self._head_kw, **self._soft_kw)
             mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, **self._grad_kw)
             self._apply()
         else:
             dqn_targets(online, target, cfg.hidden, self.A, self.ring, filled, cfg.gamma, cfg.double_q,
                         self.sample_seed, self.updates, cfg.batch_size, tree=self.per.tree, beta=self.last_beta,
-                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep, **self._head_kw)
+                        out=(self.Xb, self.act_b, self.y, self.idx, self.w, self.wmax), **nstep, **self._head_kw,
+                        **self._soft_kw)
             mlp_grad(self.head, params, self.Xb, self.A, cfg.hidden, act=self.act_b, ret=self.y,
                      clip_eps=cfg.huber_delta, grad_slab=self.slab, loss_slab=self.loss, row_w=self.w,
                      w_norm=self.wmax, td_abs=self.td_abs, **self._grad_kw)
@@ -503,6 +526,10 @@ class DQNTrainer:
         if mine != theirs:
             raise ValueError(f"this trainer has atoms={mine} ({self.q.P} parameters); the checkpoint has "
                              f"atoms={theirs} ({got} parameters): build the trainer with the checkpoint's atoms setting")
+        mine, theirs = float(self.cfg.munchausen), float(sd.get("cfg", {}).get("munchausen", 0.0) or 0.0)  # absent: hard max
+        if mine != theirs:
+            raise ValueError(f"this trainer has munchausen={mine}; the checkpoint has munchausen={theirs}: build the "
+                             "trainer with the checkpoint's munchausen setting")
         mine = bool(self.cfg.dueling)
         theirs = sd.get("cfg", {}).get("dueling")  # absent in a checkpoint from before the dueling head: plain
         if got != self.q.P or (theirs is not None and bool(theirs) != mine):

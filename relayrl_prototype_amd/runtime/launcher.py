@@ -128,6 +128,25 @@ PRESETS: Dict[str, Preset] = {
                 "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
                 "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "dueling": True,
                 "noisy": True}),
+    "cartpole-dqn-munchausen": Preset(
+        "cartpole-dqn-munchausen", "cartpole-dqn-nstep with Munchausen targets (M-DQN, Vieillard et al. 2020) instead "
+        "of double Q: the clipped, scaled log-policy of the taken action is added to the reward and the bootstrap is "
+        "the entropy-regularised expectation over actions, both from one fused soft-target kernel (--set "
+        "double_q=false --set munchausen=0.9 on any plain or quantile DQN preset is the same mechanism)",
+        "vec", {"env": "CartPole-v1", "algo": "dqn", "num_envs": 1024, "rollout_len": 4, "buffer_slots": 256,
+                "batch_size": 1024, "updates_per_epoch": 4, "gamma": 0.99, "q_lr": 5e-4, "eps_start": 1.0,
+                "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
+                "double_q": False, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
+                "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "munchausen": 0.9}),
+    "cartpole-dqn-munchausen-qr": Preset(
+        "cartpole-dqn-munchausen-qr", "cartpole-dqn-quantile with Munchausen targets instead of double Q: the soft "
+        "policy comes from the means of the target net's quantiles and every quantile takes the soft bootstrap",
+        "vec", {"env": "CartPole-v1", "algo": "dqn", "num_envs": 1024, "rollout_len": 4, "buffer_slots": 256,
+                "batch_size": 1024, "updates_per_epoch": 4, "gamma": 0.99, "q_lr": 5e-4, "eps_start": 1.0,
+                "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
+                "double_q": False, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
+                "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "quantiles": 8,
+                "munchausen": 0.9}),
 }
 
 
