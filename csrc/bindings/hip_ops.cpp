@@ -63,7 +63,7 @@ void mlp_forward(int64_t mode, const Tensor& params, const Tensor& X, int64_t A,
   TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
   const int64_t B = X.size(0), D = X.size(1);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
+  TORCH_CHECK(D >= 1 && D <= 128, "obs dim must be in [1, 128], got ", D);
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
   TORCH_CHECK(mode >= MODE_VALUE && mode <= MODE_GAUSS_EVAL, "bad mode");
   const bool gauss = mode == MODE_GAUSS_SAMPLE || mode == MODE_GAUSS_EVAL;
@@ -105,7 +105,7 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   TORCH_CHECK(X.dim() == 2, "X must be [B, D]");
   const int64_t B = X.size(0), D = X.size(1);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
-  TORCH_CHECK(D >= 1 && D <= 32, "obs dim must be in [1, 32]");
+  TORCH_CHECK(D >= 1 && D <= 128, "obs dim must be in [1, 128], got ", D);
   TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
   TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_C51, "bad head");
   const bool gauss = head == HEAD_PPO_GAUSS || head == HEAD_PG_GAUSS;
@@ -113,6 +113,7 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   const bool value = head == HEAD_VALUE_MSE;
   const bool qr = head == HEAD_Q_QR, c51 = head == HEAD_Q_C51;
   const bool qhead = head == HEAD_Q_TD || head == HEAD_Q_DUEL || qr || c51;  // reads act + ret; no advantages
+  TORCH_CHECK(D <= 32 || !qhead, "obs dim must be in [1, 32]");  // the Q heads, as before the wide-input kernels
   TORCH_CHECK(c51 == (atoms != 0), "atoms >= 2 goes with the Q_C51 head and no other: head ", head, " got atoms = ",
               atoms);
   TORCH_CHECK(qr ? quantiles >= 1 : quantiles == 0, "quantiles >= 1 goes with the Q_QR head and no other: head ", head,

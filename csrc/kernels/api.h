@@ -83,7 +83,8 @@ struct MlpGradCall {
 extern "C" {
 
 // ---- mlp_forward.hip
-// mode: a FwdMode
+// mode: a FwdMode.  -2: A outside [1, 16] or D outside [1, 128] (33 .. 128 run the 4- and 8-tile instances, W1 resident
+// in LDS); -3: H not 64 / 128.  Nothing is written on a refusal
 int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D, int A, int H, const float* mask,
                     const int* act_in, const float* actc_in, int* act_out, float* actc_out, float* out0,
                     float* out1, float* logits_out, uint64_t seed, uint64_t step, uint32_t row_offset,
@@ -91,7 +92,7 @@ int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D,
 // 1 = bf16x6 weight-stationary split kernel, 0 = fp32 MFMA; returns the previous mode (-1 queries)
 int rrl_set_value_fwd_mode(int mode);
 
-// ---- mlp_grad.hip
+// ---- mlp_grad.hip, mlp_grad_wide.hip
 // The fused forward + backward of every head.  Per head, what is read besides params, X, the slabs and the three
 // optional groups below (a field a head does not read is ignored, except where a refusal names it):
 //   HEAD_PG_CAT     act, adv; mask, adv_stats (may be null); ent_coef
@@ -132,7 +133,8 @@ int rrl_set_value_fwd_mode(int mode);
 // Nothing is written on a refusal; checked in this order.
 // -1: a head that is no GradHead; HEAD_Q_QR with quantiles < 1, or quantiles != 0 with another head; HEAD_Q_QR with a
 // null params, X, act, ret or slab; row_w without w_norm or the reverse; row_w or td_abs with a head that is not one
-// of the three Q heads.  -2: A outside [1, 16] or D outside [1, 32]; HEAD_Q_QR with B < 1, A * NQ > 16 or kappa <= 0.
+// of the three Q heads.  -2: A outside [1, 16], D outside [1, 128], or D > 32 with a Q head (33 .. 128 run the five
+// on-policy heads on mlp_grad_wide.hip, which stages W1 per slab); HEAD_Q_QR with B < 1, A * NQ > 16 or kappa <= 0.
 // -3: H not 64 / 128, or HEAD_Q_DUEL with A > 15.  -2: HEAD_Q_QR with P not that of MLPSpec(D, H, A * NQ).  -4: the
 // net and the staging do not fit the LDS
 int rrl_mlp_grad(const rrl::MlpGradCall* c, int num_cu, void* stream);

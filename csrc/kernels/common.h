@@ -197,7 +197,8 @@ RRL_DEV void dense_fwd(const float* __restrict__ W, int S, const float* __restri
   }
 }
 
-// k-steps of the last interleaved input tile that carry real features.
+// k-steps of the last interleaved input tile that carry real features; <= 0 (no k-step: dense_fwd tests r < kr) where
+// D leaves that whole tile empty, as D = 33 does in 4 tiles.
 RRL_DEV int input_kr_last(int D, int DT) {
   const int rem = D - 16 * (DT - 1);
   return rem >= 16 ? 4 : (rem + 3) >> 2;

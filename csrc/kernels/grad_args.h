@@ -55,5 +55,9 @@ bool policy_grad_split_supported(int D, int H, int A, int head);
 int launch_policy_grad_split(const GradArgs& a, int head, int grid, hipStream_t s);
 // Value forward V(x) on the same weight-stationary bf16x6 layers (fp32-accurate), p.vout.
 int launch_value_fwd_split(const GradArgs& a, int grid, hipStream_t s);
+// Wide observations (mlp_grad_wide.hip): the five on-policy heads at 33 <= D <= 128, H = 64 or 128, W1 staged per
+// slab.  -2 for any other shape or head.
+bool grad_wide_supported(int D, int H, int head);
+int launch_grad_wide(const GradArgs& a, int head, int H, int grid, hipStream_t s);
 
 }  // namespace rrl

@@ -205,7 +205,7 @@ extern "C" int rrl_mlp_forward(int mode, const float* params, const float* X, in
                                const float* gate, float* x_copy, int* act_host, float* actc_host, int num_cu,
                                void* stream) {
   if (B <= 0) return 0;
-  if (A < 1 || A > kMaxAct || D < 1 || D > 32) return -2;
+  if (A < 1 || A > kMaxAct || D < 1 || D > 128) return -2;
   FwdArgs a{params, X, B, D, A, H, mask, act_in, actc_in, act_out, actc_out, out0, out1, logits_out,
             (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, (uint32_t)(step >> 32), row_offset, gate,
             x_copy, act_host, actc_host};
@@ -229,6 +229,13 @@ extern "C" int rrl_mlp_forward(int mode, const float* params, const float* X, in
   const int cap = 2 * (num_cu > 0 ? num_cu : 256);
   if (grid > cap) grid = cap;
   hipStream_t s = (hipStream_t)stream;
+  if (D > 32) {
+    // Wide observations: 4 input tiles (D <= 64) or 8 (D <= 128), W1 resident like every other layer; LdsNet<8, 8> with
+    // 16 outputs is 144,512 B, so one workgroup per CU.  A tile past D holds zeros in x and in W1 and costs MFMAs only.
+    if (H == 128) return D <= 64 ? dispatch_mode<4, 8>(mode, a, grid, s) : dispatch_mode<8, 8>(mode, a, grid, s);
+    if (H == 64) return D <= 64 ? dispatch_mode<4, 4>(mode, a, grid, s) : dispatch_mode<8, 4>(mode, a, grid, s);
+    return -3;
+  }
   const int DT = (D <= 16) ? 1 : 2;
   if (H == 128) return DT == 1 ? dispatch_mode<1, 8>(mode, a, grid, s) : dispatch_mode<2, 8>(mode, a, grid, s);
   if (H == 64) return DT == 1 ? dispatch_mode<1, 4>(mode, a, grid, s) : dispatch_mode<2, 4>(mode, a, grid, s);

@@ -25,11 +25,10 @@
 #include "heads.h"
 #include "grad_args.h"
 #include "actor_step.h"  // raise_lds_limit
+#include "wgrad.h"
 #include "wide.h"
 
 namespace rrl {
-
-constexpr int kStageLd = 68;  // [feature][64 batch + 4 pad]
 
 // The categorical head's block (HEAD_Q_C51): GradQrArgs with qtarget the projected distribution m [B][NA] (NQ is
 // not read) and the support behind it, so that every other instance keeps its block.
@@ -48,75 +47,6 @@ template <int HEAD>
 __host__ __device__ inline int grad_outputs(const GradArgsOf<HEAD>& p) {
   if constexpr (HEAD == HEAD_Q_QR) return p.A * p.NQ;
   else return (HEAD == HEAD_VALUE_MSE) ? 1 : (HEAD == HEAD_Q_DUEL) ? p.A + 1 : p.A;
-}
-
-// acc[to][ti] += sum_b At[16*(to0+to)+i][b] * Bt[16*(ti0+ti)+i][b], b over the 64-row slab.
-// Operands of batch block bb+1 are loaded while block bb's MFMAs issue.
-template <int NTO, int NTI>
-RRL_DEV void wgrad(const float* __restrict__ At, const float* __restrict__ Bt, int to0, int ti0,
-                   floatx4 (&acc)[NTO][NTI], float (&bacc)[NTO]) {
-  const int l = lane_id();
-  const int i = l & 15, g = l >> 4;
-  floatx4 a[NTO], b[NTI], an[NTO], bn[NTI];
-#pragma unroll
-  for (int to = 0; to < NTO; ++to)
-    a[to] = *reinterpret_cast<const floatx4*>(At + (16 * (to0 + to) + i) * kStageLd + 4 * g);
-#pragma unroll
-  for (int ti = 0; ti < NTI; ++ti)
-    b[ti] = *reinterpret_cast<const floatx4*>(Bt + (16 * (ti0 + ti) + i) * kStageLd + 4 * g);
-#pragma unroll
-  for (int bb = 0; bb < 4; ++bb) {
-    if (bb < 3) {
-#pragma unroll
-      for (int to = 0; to < NTO; ++to)
-        an[to] = *reinterpret_cast<const floatx4*>(At + (16 * (to0 + to) + i) * kStageLd + 16 * (bb + 1) + 4 * g);
-#pragma unroll
-      for (int ti = 0; ti < NTI; ++ti)
-        bn[ti] = *reinterpret_cast<const floatx4*>(Bt + (16 * (ti0 + ti) + i) * kStageLd + 16 * (bb + 1) + 4 * g);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int to = 0; to < NTO; ++to) {
-#pragma unroll
-        for (int ti = 0; ti < NTI; ++ti) acc[to][ti] = mfma4(a[to][r], b[ti][r], acc[to][ti]);
-      }
-    }
-#pragma unroll
-    for (int to = 0; to < NTO; ++to) bacc[to] += (a[to][0] + a[to][1]) + (a[to][2] + a[to][3]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (bb < 3) {
-#pragma unroll
-      for (int to = 0; to < NTO; ++to) a[to] = an[to];
-#pragma unroll
-      for (int ti = 0; ti < NTI; ++ti) b[ti] = bn[ti];
-    }
-  }
-}
-
-// Write NT transposed tiles of this wave (16 batch columns) into a staging image.
-template <int NT>
-RRL_DEV void stage_tiles(float* __restrict__ St, int wave, const floatx4 (&v)[NT]) {
-  const int l = lane_id();
-  const int j = l & 15, g = l >> 4;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) St[(16 * t + 4 * g + r) * kStageLd + 16 * wave + j] = v[t][r];
-  }
-}
-
-// Interleaved input tile (load_x_tile layout: reg r of group g = feature 16t + 4r + g)
-// written into the staging image in natural feature order.
-template <int NT>
-RRL_DEV void stage_x_tiles(float* __restrict__ St, int wave, const floatx4 (&v)[NT]) {
-  const int l = lane_id();
-  const int j = l & 15, g = l >> 4;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) St[(16 * t + 4 * r + g) * kStageLd + 16 * wave + j] = v[t][r];
-  }
 }
 
 // A3 > 0: the last layer has A3 (<= 2) outputs and its weight gradient is accumulated on
@@ -917,7 +847,8 @@ extern "C" int rrl_mlp_grad(const MlpGradCall* c, int num_cu, void* stream) {
   if (qr && (!c->params || !c->X || !c->act || !c->ret || !c->grad_slab || !c->loss_slab)) return -1;
   if ((c->row_w == nullptr) != (c->w_norm == nullptr)) return -1;
   if ((c->row_w != nullptr || c->td_abs != nullptr) && !qhead) return -1;
-  if (A < 1 || A > kMaxAct || D < 1 || D > 32) return -2;
+  if (A < 1 || A > kMaxAct || D < 1 || D > 128) return -2;
+  if (D > 32 && qhead) return -2;  // the Q heads' nets have device envs' inputs, D <= 32
   if (qr && (c->B < 1 || (long long)A * NQ > kMaxAct || !(c->clip_eps > 0.f))) return -2;
   if (H != 64 && H != 128) return -3;
   if (head == HEAD_Q_DUEL && A + 1 > kMaxAct) return -3;  // the net has A + 1 outputs
@@ -942,6 +873,7 @@ extern "C" int rrl_mlp_grad(const MlpGradCall* c, int num_cu, void* stream) {
     return launch_value_grad_split(a, grid, s);
   if (head != HEAD_VALUE_MSE && g_value_grad_mode == 1 && policy_grad_split_supported(D, H, A, head))
     return launch_policy_grad_split(a, head, grid, s);
+  if (D > 32) return launch_grad_wide(a, head, H, grid, s);  // W1 staged per slab (mlp_grad_wide.hip)
   const int DT = (D <= 16) ? 1 : 2;
   if (H == 128) return DT == 1 ? dispatch_head<1, 8>(head, a, grid, s) : dispatch_head<2, 8>(head, a, grid, s);
   return DT == 1 ? dispatch_head<1, 4>(head, a, grid, s) : dispatch_head<2, 4>(head, a, grid, s);

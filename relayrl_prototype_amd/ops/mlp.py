@@ -54,6 +54,14 @@ def _i32(t):
     return None if t is None else t.contiguous().to(torch.int32)
 
 
+MAX_OBS_DIM = 128  # the widest input the HIP forward and gradient kernels take (8 input tiles)
+
+
+def _check_obs_dim(D: int):
+    if not 1 <= D <= MAX_OBS_DIM:
+        raise ValueError(f"obs dim must be in [1, {MAX_OBS_DIM}] on the GPU, got D = {D}")
+
+
 def mlp_forward(mode: int, params: torch.Tensor, X: torch.Tensor, A: int, H: int, mask=None, act_in=None,
                 actc_in=None, seed: int = 0, step: int = 0, row_offset: int = 0, out: Optional[dict] = None,
                 gate=None):
@@ -74,6 +82,7 @@ def mlp_forward(mode: int, params: torch.Tensor, X: torch.Tensor, A: int, H: int
                     out[k] = v
             return out
         return r
+    _check_obs_dim(X.shape[1])
     dev = X.device
     out = {} if out is None else out
     mode = int(mode)
@@ -222,6 +231,7 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
         ls[0, 4] = st.get("v", 0.0)
         ls[0, 5] = st.get("count", n)
         return g.view(1, -1), ls
+    _check_obs_dim(D)
     chunks = grad_chunks(B)
     if len(chunks) > 1 and (qr or c51):
         raise ValueError(f"the quantile and categorical heads take a single-launch batch (<= {GRAD_CHUNK_ROWS} rows)")

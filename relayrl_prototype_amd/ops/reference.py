@@ -68,11 +68,13 @@ def cat_sample_from_u(logits: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def mlp_forward_ref(mode, params, X, A, H, mask=None, act_in=None, actc_in=None, seed=0, step=0, row_offset=0):
+def mlp_forward_ref(mode, params, X, A, H, mask=None, act_in=None, actc_in=None, seed=0, step=0, row_offset=0,
+                    dtype=torch.float32):
+    """``dtype=torch.float64`` gives the float64 oracle; the Philox draws are the same in both."""
     B, D = X.shape
     gaussian = mode in (MODE_GAUSS_SAMPLE, MODE_GAUSS_EVAL)
     Aeff = 1 if mode == MODE_VALUE else A
-    out, log_std = trunk(params.float(), X.float(), D, H, Aeff, gaussian)
+    out, log_std = trunk(params.to(dtype), X.to(dtype), D, H, Aeff, gaussian)
     res = {}
     if mode == MODE_VALUE:
         res["v"] = out[:, 0]
@@ -295,6 +297,7 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
                  w_norm=None, quantiles=0, atoms=0, v_min=0.0, v_max=0.0):
     """Returns (flat gradient, stats dict) of sum_i loss_i * inv_B (+ entropy bonus);
     ``dtype=torch.float64`` gives the float64 oracle (tools/grad_fuzz_probe.py).
+    The value and policy heads also return the rows behind their sums: ``loss_rows`` and ``v_rows`` / ``ent_rows``.
     ``HEAD_Q_TD``: loss_i = huber(Q(x_i)[act_i] - ret_i, delta) with delta = ``clip_eps``, times
     ``row_w[i] / w_norm`` where the weights of prioritised replay are given; ``stats["td_abs"]`` is
     |Q - ret| per row.  ``HEAD_Q_DUEL`` is the same loss on a dueling net: ``A`` stays the number of
@@ -331,7 +334,7 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
         v = out[:, 0]
         li = (v - ret) ** 2
         loss = li.sum() * inv_B
-        stats.update(loss=li.sum().item(), v=v.sum().item(), count=B)
+        stats.update(loss=li.sum().item(), v=v.sum().item(), count=B, loss_rows=li.detach(), v_rows=v.detach())
     elif head == HEAD_Q_QR:
         idx = act.long().reshape(B, 1, 1).expand(B, 1, NQ)
         theta = out.reshape(B, A, NQ).gather(1, idx).squeeze(1)            # [B, NQ]
@@ -389,7 +392,7 @@ def mlp_grad_ref(head, params, X, A, H, mask=None, act=None, actc=None, adv=None
             li = -torch.minimum(s1, s2)
             stats["clipfrac"] = ((ratio - 1).abs() > clip_eps).float().sum().item()
         loss = li.sum() * inv_B - ent_coef * ent.sum() * inv_B
-        stats.update(loss=li.sum().item(), entropy=ent.sum().item(), count=B)
+        stats.update(loss=li.sum().item(), entropy=ent.sum().item(), count=B, loss_rows=li.detach(), ent_rows=ent.detach())
         if logp_old is not None:
             stats["kl"] = (logp_old - logp).sum().item()
     loss.backward()
