@@ -54,6 +54,15 @@ void destroy_stream(int64_t st) {
   if (st) (void)hipStreamDestroy((hipStream_t)(uintptr_t)st);
 }
 
+// The categorical modes and heads take up to 64 actions (more than 16 on the wide output layer, mlp_cat_wide.hip, whose
+// trunk takes obs dim <= 32); every other mode and head holds 16 outputs.
+static void check_act_dim(int64_t A, int64_t D, bool categorical) {
+  const int64_t hi = categorical ? 64 : 16;
+  TORCH_CHECK(A >= 1 && A <= hi, "act dim must be in [1, ", hi, "] for ",
+              categorical ? "the categorical modes and heads" : "this mode or head", ", got ", A);
+  TORCH_CHECK(A <= 16 || D <= 32, "obs dim must be in [1, 32] with more than 16 actions, got ", D, " with act dim ", A);
+}
+
 void mlp_forward(int64_t mode, const Tensor& params, const Tensor& X, int64_t A, int64_t H, const OptT& mask,
                  const OptT& act_in, const OptT& actc_in, const OptT& act_out, const OptT& actc_out,
                  const Tensor& out0, const OptT& out1, const OptT& logits_out, int64_t seed, int64_t step,
@@ -64,8 +73,8 @@ void mlp_forward(int64_t mode, const Tensor& params, const Tensor& X, int64_t A,
   const int64_t B = X.size(0), D = X.size(1);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 128, "obs dim must be in [1, 128], got ", D);
-  TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
   TORCH_CHECK(mode >= MODE_VALUE && mode <= MODE_GAUSS_EVAL, "bad mode");
+  check_act_dim(A, D, mode == MODE_CAT_SAMPLE || mode == MODE_CAT_EVAL || mode == MODE_LOGITS);
   const bool gauss = mode == MODE_GAUSS_SAMPLE || mode == MODE_GAUSS_EVAL;
   const int64_t Aeff = mode == MODE_VALUE ? 1 : A;
   check_numel(params, "params", flat_size(D, H, Aeff, gauss));
@@ -106,8 +115,8 @@ void mlp_grad(int64_t head, const Tensor& params, const Tensor& X, int64_t A, in
   const int64_t B = X.size(0), D = X.size(1);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 128, "obs dim must be in [1, 128], got ", D);
-  TORCH_CHECK(A >= 1 && A <= 16, "act dim must be in [1, 16]");
   TORCH_CHECK(head >= HEAD_PG_CAT && head <= HEAD_Q_C51, "bad head");
+  check_act_dim(A, D, head == HEAD_PG_CAT || head == HEAD_PPO_CAT);
   const bool gauss = head == HEAD_PPO_GAUSS || head == HEAD_PG_GAUSS;
   const bool cat = head == HEAD_PG_CAT || head == HEAD_PPO_CAT;
   const bool value = head == HEAD_VALUE_MSE;

@@ -83,8 +83,11 @@ struct MlpGradCall {
 extern "C" {
 
 // ---- mlp_forward.hip
-// mode: a FwdMode.  -2: A outside [1, 16] or D outside [1, 128] (33 .. 128 run the 4- and 8-tile instances, W1 resident
-// in LDS); -3: H not 64 / 128.  Nothing is written on a refusal
+// mode: a FwdMode.  A <= 16 runs mlp_forward_kernel whatever the mode; 17 <= A <= 64 with MODE_CAT_SAMPLE, MODE_CAT_EVAL
+// or MODE_LOGITS runs the wide output layer (mlp_cat_wide.hip: logits distributed over the lane groups, D <= 32),
+// whatever rrl_set_value_fwd_mode says.  Checked in this order.  -2: A outside [1, 64] for the three categorical modes
+// or outside [1, 16] for every other, or D outside [1, 128] (33 .. 128 run the 4- and 8-tile instances, W1 resident in
+// LDS); -2: A > 16 with D > 32; -3: H not 64 / 128.  Nothing is written on a refusal
 int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D, int A, int H, const float* mask,
                     const int* act_in, const float* actc_in, int* act_out, float* actc_out, float* out0,
                     float* out1, float* logits_out, uint64_t seed, uint64_t step, uint32_t row_offset,
@@ -92,10 +95,12 @@ int rrl_mlp_forward(int mode, const float* params, const float* X, int B, int D,
 // 1 = bf16x6 weight-stationary split kernel, 0 = fp32 MFMA; returns the previous mode (-1 queries)
 int rrl_set_value_fwd_mode(int mode);
 
-// ---- mlp_grad.hip, mlp_grad_wide.hip
+// ---- mlp_grad.hip, mlp_grad_wide.hip, mlp_cat_wide.hip
 // The fused forward + backward of every head.  Per head, what is read besides params, X, the slabs and the three
 // optional groups below (a field a head does not read is ignored, except where a refusal names it):
-//   HEAD_PG_CAT     act, adv; mask, adv_stats (may be null); ent_coef
+//   HEAD_PG_CAT     act, adv; mask [B][A], adv_stats (may be null); ent_coef.  This head and HEAD_PPO_CAT take A up to
+//                   64: 17 .. 64 run mlp_cat_wide.hip (the wide output layer, D <= 32) with the same arithmetic,
+//                   whatever rrl_set_value_grad_mode says
 //   HEAD_VALUE_MSE  ret; the net has one output whatever A says
 //   HEAD_PPO_CAT    act, adv, logp_old; mask, adv_stats (may be null); clip_eps the PPO clip, ent_coef
 //   HEAD_PPO_GAUSS  actc, adv, logp_old; adv_stats (may be null); clip_eps the PPO clip, ent_coef
@@ -133,8 +138,9 @@ int rrl_set_value_fwd_mode(int mode);
 // Nothing is written on a refusal; checked in this order.
 // -1: a head that is no GradHead; HEAD_Q_QR with quantiles < 1, or quantiles != 0 with another head; HEAD_Q_QR with a
 // null params, X, act, ret or slab; row_w without w_norm or the reverse; row_w or td_abs with a head that is not one
-// of the three Q heads.  -2: A outside [1, 16], D outside [1, 128], or D > 32 with a Q head (33 .. 128 run the five
-// on-policy heads on mlp_grad_wide.hip, which stages W1 per slab); HEAD_Q_QR with B < 1, A * NQ > 16 or kappa <= 0.
+// of the three Q heads.  -2: A outside [1, 64] for HEAD_PG_CAT / HEAD_PPO_CAT or outside [1, 16] for every other
+// head, D outside [1, 128], or D > 32 with a Q head or with A > 16 (33 .. 128 run the five on-policy heads on
+// mlp_grad_wide.hip, which stages W1 per slab); HEAD_Q_QR with B < 1, A * NQ > 16 or kappa <= 0.
 // -3: H not 64 / 128, or HEAD_Q_DUEL with A > 15.  -2: HEAD_Q_QR with P not that of MLPSpec(D, H, A * NQ).  -4: the
 // net and the staging do not fit the LDS
 int rrl_mlp_grad(const rrl::MlpGradCall* c, int num_cu, void* stream);

@@ -59,5 +59,8 @@ int launch_value_fwd_split(const GradArgs& a, int grid, hipStream_t s);
 // slab.  -2 for any other shape or head.
 bool grad_wide_supported(int D, int H, int head);
 int launch_grad_wide(const GradArgs& a, int head, int H, int grid, hipStream_t s);
+// Categorical policies of 17 .. 64 actions (mlp_cat_wide.hip): HEAD_PG_CAT and HEAD_PPO_CAT at D <= 32, H = 64 or 128,
+// on the wide output layer of wide.h.  -2 for any other shape or head, -4 where the image does not fit the LDS.
+int launch_grad_cat_wide(const GradArgs& a, int head, int H, int grid, hipStream_t s);
 
 }  // namespace rrl

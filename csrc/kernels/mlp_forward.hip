@@ -11,36 +11,12 @@
 //                     ContinuousPolicyNetwork, kernel.py:49-75, completed).
 #include "api.h"
 #include "common.h"
+#include "fwd_args.h"
 #include "grad_args.h"
 #include "heads.h"
+#include "wide.h"  // kMaxCatAct
 
 namespace rrl {
-
-struct FwdArgs {
-  const float* params;
-  const float* X;        // [B][D]
-  int B, D, A, H;
-  const float* mask;     // [B][A] or null
-  const int* act_in;     // [B] (CAT_EVAL)
-  const float* actc_in;  // [B][A] (GAUSS_EVAL)
-  int* act_out;          // [B]
-  float* actc_out;       // [B][A]
-  float* out0;           // v / logp
-  float* out1;           // entropy (may be null)
-  float* logits_out;     // [B][A] (MODE_LOGITS) or mean for Gaussian (may be null)
-  uint32_t seed_lo, seed_hi;
-  uint32_t step_lo, step_hi;
-  uint32_t row_offset;   // stream id of row 0 (global env index)
-  const float* gate;     // MODE_VALUE: [B] done codes; only 16-row tiles holding a code 2
-                         // (time-limit truncation) are evaluated, or null = every row
-  // host-env rollout (runtime/host_rollout.cpp): X may be PINNED HOST memory read over PCIe
-  // (zero-copy); x_copy gets the rows in HBM for the learner and act_host / actc_host the
-  // sampled actions in pinned host memory for the env threads -- one launch per half-step,
-  // no H2D / D2H copies.  All null on the ordinary path.
-  float* x_copy;         // [B][D] or null
-  int* act_host;         // [B] or null (CAT_SAMPLE)
-  float* actc_host;      // [B][A] or null (GAUSS_SAMPLE)
-};
 
 template <int DT, int HT, int MODE>
 __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(FwdArgs p) {
@@ -205,7 +181,9 @@ extern "C" int rrl_mlp_forward(int mode, const float* params, const float* X, in
                                const float* gate, float* x_copy, int* act_host, float* actc_host, int num_cu,
                                void* stream) {
   if (B <= 0) return 0;
-  if (A < 1 || A > kMaxAct || D < 1 || D > 128) return -2;
+  const bool cat = mode == MODE_CAT_SAMPLE || mode == MODE_CAT_EVAL || mode == MODE_LOGITS;
+  if (A < 1 || A > (cat ? kMaxCatAct : kMaxAct) || D < 1 || D > 128) return -2;
+  if (A > kMaxAct && D > 32) return -2;  // more than 16 actions: the wide output layer, whose trunk takes D <= 32
   FwdArgs a{params, X, B, D, A, H, mask, act_in, actc_in, act_out, actc_out, out0, out1, logits_out,
             (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, (uint32_t)(step >> 32), row_offset, gate,
             x_copy, act_host, actc_host};
@@ -223,6 +201,7 @@ extern "C" int rrl_mlp_forward(int mode, const float* params, const float* X, in
     if (sg > scap) sg = scap;
     return launch_value_fwd_split(g, sg, (hipStream_t)stream);
   }
+  if (A > kMaxAct) return launch_fwd_cat_wide(a, mode, num_cu, (hipStream_t)stream);  // mlp_cat_wide.hip
   const int tiles = (B + kTileB - 1) / kTileB;
   const int waves_needed = tiles;
   int grid = (waves_needed + 3) / 4;

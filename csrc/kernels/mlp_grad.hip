@@ -477,29 +477,6 @@ __global__ __launch_bounds__(256, 1) void mlp_grad_kernel(GradArgsOf<HEAD> p) {
 }
 
 // ------------------------------------------------------------------ HEAD_Q_C51 on the wide output layer (wide.h)
-// din += W^T dout over the NO tiles of one action's block of the padded W3 (dense_bwd_data without the clear and
-// the mask, so that the actions accumulate into one dh2).
-template <int NI, int NO>
-RRL_DEV void dense_bwd_acc(const float* __restrict__ W, int S, const floatx4 (&dout)[NO], floatx4 (&din)[NI]) {
-  const int l = lane_id();
-  const int i = l & 15, g = l >> 4;
-#pragma unroll
-  for (int to = 0; to < NO; ++to) {
-    float wc[4][NI];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int ti = 0; ti < NI; ++ti) wc[r][ti] = W[(16 * to + 4 * g + r) * S + i + 16 * ti];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int ti = 0; ti < NI; ++ti) din[ti] = mfma4(wc[r][ti], dout[to][r], din[ti]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
 // The categorical instance.  The net is MLPSpec(D, H, A * NA), D <= 16; p.qtarget is the projected target m [B][NA]
 // of dqn_targets and loss_row = -sum_i m_i log p(act, i), dout[act block] = invB * w * (p - m).
 //
@@ -847,8 +824,9 @@ extern "C" int rrl_mlp_grad(const MlpGradCall* c, int num_cu, void* stream) {
   if (qr && (!c->params || !c->X || !c->act || !c->ret || !c->grad_slab || !c->loss_slab)) return -1;
   if ((c->row_w == nullptr) != (c->w_norm == nullptr)) return -1;
   if ((c->row_w != nullptr || c->td_abs != nullptr) && !qhead) return -1;
-  if (A < 1 || A > kMaxAct || D < 1 || D > 128) return -2;
-  if (D > 32 && qhead) return -2;  // the Q heads' nets have device envs' inputs, D <= 32
+  const bool cat = head == HEAD_PG_CAT || head == HEAD_PPO_CAT;
+  if (A < 1 || A > (cat ? kMaxCatAct : kMaxAct) || D < 1 || D > 128) return -2;
+  if (D > 32 && (qhead || A > kMaxAct)) return -2;  // the Q heads and the wide output layer take D <= 32
   if (qr && (c->B < 1 || (long long)A * NQ > kMaxAct || !(c->clip_eps > 0.f))) return -2;
   if (H != 64 && H != 128) return -3;
   if (head == HEAD_Q_DUEL && A + 1 > kMaxAct) return -3;  // the net has A + 1 outputs
@@ -869,6 +847,7 @@ extern "C" int rrl_mlp_grad(const MlpGradCall* c, int num_cu, void* stream) {
   }
   const int grid = rrl_mlp_grad_slabs(c->B, num_cu);
   hipStream_t s = (hipStream_t)stream;
+  if (A > kMaxAct) return launch_grad_cat_wide(a, head, H, grid, s);  // 17 .. 64 actions (mlp_cat_wide.hip)
   if (head == HEAD_VALUE_MSE && g_value_grad_mode == 1 && value_grad_split_supported(D, H))
     return launch_value_grad_split(a, grid, s);
   if (head != HEAD_VALUE_MSE && g_value_grad_mode == 1 && policy_grad_split_supported(D, H, A, head))

@@ -23,6 +23,8 @@ namespace rrl {
 
 constexpr int kMaxWideTiles = 8;  // OT = A * TPA output tiles at most
 constexpr int kMaxTpa = 4;        // 64 atoms per action at most
+// A categorical POLICY of 17 .. 64 actions is one block of this layout (A = 1, NA = the actions): mlp_cat_wide.hip
+constexpr int kMaxCatAct = 16 * kMaxTpa;
 
 // The support z_i = v_min + i * dz, dz = (v_max - v_min) / (NA - 1), as one fused multiply-add.
 struct C51Support {
@@ -111,6 +113,29 @@ RRL_DEV void wide_logits(const float* __restrict__ lds, int OT, int a, int NA, c
                          floatx4 (&lg)[TPA]) {
   using L = LdsWide<HT>;
   wide_logits_at<HT, TPA>(lds + L::W3_of(OT) + 16 * TPA * a * L::S3, lds + L::B3 + 16 * TPA * a, NA, h2, lg);
+}
+
+// din += W^T dout over the NO tiles of one action's block of the padded W3 (dense_bwd_data without the clear and
+// the mask, so that the actions accumulate into one dh2).
+template <int NI, int NO>
+RRL_DEV void dense_bwd_acc(const float* __restrict__ W, int S, const floatx4 (&dout)[NO], floatx4 (&din)[NI]) {
+  const int l = lane_id();
+  const int i = l & 15, g = l >> 4;
+#pragma unroll
+  for (int to = 0; to < NO; ++to) {
+    float wc[4][NI];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int ti = 0; ti < NI; ++ti) wc[r][ti] = W[(16 * to + 4 * g + r) * S + i + 16 * ti];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int ti = 0; ti < NI; ++ti) din[ti] = mfma4(wc[r][ti], dout[to][r], din[ti]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
 }
 
 // Softmax of one action's logits in place (lg becomes p) and its expectation sum_i z_i p_i, in the order of the

@@ -62,13 +62,33 @@ def _check_obs_dim(D: int):
         raise ValueError(f"obs dim must be in [1, {MAX_OBS_DIM}] on the GPU, got D = {D}")
 
 
+MAX_ACTIONS = 16  # outputs the fused heads hold; the value, Gaussian and Q heads stop here
+MAX_CAT_ACTIONS = 64  # the categorical modes and heads: 17 .. 64 run on the wide output layer (mlp_cat_wide.hip)
+MAX_WIDE_ACT_OBS_DIM = 32  # whose trunk takes observations up to 32 wide
+_CAT_MODES = (int(FwdMode.CAT_SAMPLE), int(FwdMode.CAT_EVAL), int(FwdMode.LOGITS))
+_CAT_HEADS = (int(GradHead.PG_CAT), int(GradHead.PPO_CAT))
+
+
+def _check_act_dim(A: int, D: int, categorical: bool):
+    hi = MAX_CAT_ACTIONS if categorical else MAX_ACTIONS
+    if not 1 <= A <= hi:
+        what = "the categorical modes and heads" if categorical else "this mode or head"
+        raise ValueError(f"act dim must be in [1, {hi}] for {what} on the GPU, got A = {A}")
+    if A > MAX_ACTIONS and D > MAX_WIDE_ACT_OBS_DIM:
+        raise ValueError(f"obs dim must be in [1, {MAX_WIDE_ACT_OBS_DIM}] with more than {MAX_ACTIONS} actions on the "
+                         f"GPU, got D = {D} with A = {A}")
+
+
 def mlp_forward(mode: int, params: torch.Tensor, X: torch.Tensor, A: int, H: int, mask=None, act_in=None,
                 actc_in=None, seed: int = 0, step: int = 0, row_offset: int = 0, out: Optional[dict] = None,
                 gate=None):
     """Batched fused forward.  Returns a dict with keys among v / act / logp / entropy / logits / mean.
 
     ``gate`` (VALUE mode): [B] done codes; the kernel evaluates only the 16-row tiles that
-    contain a time-limit truncation (code 2) -- the bootstrap values of cut episodes."""
+    contain a time-limit truncation (code 2) -- the bootstrap values of cut episodes.
+
+    On the GPU the categorical modes (CAT_SAMPLE, CAT_EVAL, LOGITS) take ``A`` up to ``MAX_CAT_ACTIONS`` = 64: up to 16
+    run the replicated heads, 17 .. 64 the wide output layer with ``D <= 32``.  Every other mode takes ``A <= 16``."""
     X = X.contiguous().float()
     B = X.shape[0]
     h = _hip_for(X)
@@ -86,6 +106,7 @@ def mlp_forward(mode: int, params: torch.Tensor, X: torch.Tensor, A: int, H: int
     dev = X.device
     out = {} if out is None else out
     mode = int(mode)
+    _check_act_dim(A, X.shape[1], mode in _CAT_MODES)
     if mode == FwdMode.VALUE:
         v = out.get("v")
         if v is None:
@@ -153,6 +174,9 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
              w_norm=None, td_abs=None, quantiles: int = 0, atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0):
     """Fused forward+backward.  GPU: fills grad_slab [nslab, P] and loss_slab [nslab, 8] and
     returns them; CPU: returns (grad [1, P], loss stats [1, 8]) computed with autograd.
+
+    On the GPU ``PG_CAT`` and ``PPO_CAT`` take ``A`` up to ``MAX_CAT_ACTIONS`` = 64 (17 .. 64 on the wide output layer,
+    with ``D <= 32``); every other head takes ``A <= 16``.  ``mask`` is [B, A] whatever ``A`` is.
 
     ``nvalid`` (int32 [1]) / ``inv_B_dev`` (fp32 [1]): the batch shape read from device memory
     -- rows >= nvalid are inert and inv_B_dev replaces inv_B -- so a captured graph can replay
@@ -232,6 +256,7 @@ def mlp_grad(head: int, params, X, A: int, H: int, mask=None, act=None, actc=Non
         ls[0, 5] = st.get("count", n)
         return g.view(1, -1), ls
     _check_obs_dim(D)
+    _check_act_dim(A, D, head in _CAT_HEADS)
     chunks = grad_chunks(B)
     if len(chunks) > 1 and (qr or c51):
         raise ValueError(f"the quantile and categorical heads take a single-launch batch (<= {GRAD_CHUNK_ROWS} rows)")
