@@ -59,8 +59,11 @@ every 100 epochs: one line per run in ``profiles/dqn_c51_learning.jsonl``.
 ``--munchausen`` adds, from the same process, the microseconds per launch of the Munchausen (soft) ``dqn_targets`` against
 the hard-max one on the filled rings of ``cartpole-dqn``, ``-per``, ``-nstep`` and ``-quantile``
 (``dqn_targets_<preset>_<double_q|hard_max|soft>_us``); the line goes to ``profiles/dqn_munchausen_bench.jsonl`` unless
-``--out`` names another file.  ``--munchausen-learning EPOCHS`` instead records, for seeds 1..3 of ``cartpole-dqn-nstep``,
-``cartpole-dqn-munchausen``, ``cartpole-dqn-quantile`` and ``cartpole-dqn-munchausen-qr``, the greedy mean return over 256
+``--out`` names another file.  ``--q-lambda LAM`` adds the lambda-return ``dqn_targets`` against the n-step one at
+``n_step`` 3, 5 and 8 (``lambda_records``) and the epochs of ``cartpole-dqn``, ``-nstep`` and ``-lambda``, into
+``profiles/dqn_lambda_bench.jsonl``; ``--q-lambda-learning EPOCHS`` records the curves of ``cartpole-dqn-lambda`` beside
+``cartpole-dqn-nstep`` in ``profiles/dqn_lambda_learning.jsonl``.
+``--munchausen-learning EPOCHS`` instead records, for seeds 1..3 of ``cartpole-dqn-nstep``, ``cartpole-dqn-munchausen``, ``cartpole-dqn-quantile`` and ``cartpole-dqn-munchausen-qr``, the greedy mean return over 256
 episodes every 100 epochs: one line per run in ``profiles/dqn_munchausen_learning.jsonl``.
 """
 import argparse
@@ -370,7 +373,7 @@ def quantile_learning(a, dev, presets=("cartpole-dqn-nstep", "cartpole-dqn-quant
                 if epoch % 100 == 0:
                     curve.append(round(tr.evaluate(episodes=1, num_envs=256).stats()["mean_return"], 1))
             lines.append(json.dumps(dict(preset=preset, quantiles=cfg.quantiles, atoms=cfg.atoms, n_step=cfg.n_step,
-                                         munchausen=cfg.munchausen,
+                                         munchausen=cfg.munchausen, q_lambda=cfg.q_lambda,
                                          seed=seed, eval_every=100, env_steps_per_epoch=cfg.num_envs * cfg.rollout_len,
                                          greedy_mean_return_256=curve)))
             print(lines[-1], flush=True)
@@ -415,6 +418,59 @@ def munchausen_records(a, dev, event_us):
             key = f"dqn_targets_{preset[len('cartpole-'):].replace('-', '_')}_{form}"
             rec[key + "_us"] = med
             rec[key + "_us_range"] = [lo, hi]
+    return rec
+
+
+def lambda_records(a, dev, event_us):
+    """The lambda-return targets launch against the n-step one in one process, per launch, at the ``cartpole-dqn-nstep``
+    shape on its filled ring: ``n_step`` 3, 5 and 8, uniform and prioritised, with and without ``double_q``
+    (``dqn_targets_<uniform|per>_<double_q|single>_n<K>_<nstep|lambda>_us`` and the ratio), then the epoch of
+    ``cartpole-dqn``, ``-nstep`` and ``-lambda``."""
+    from relayrl_prototype_amd.ops import dqn_targets
+    from relayrl_prototype_amd.runtime.dqn_trainer import DQNConfig, DQNTrainer
+    from relayrl_prototype_amd.runtime.launcher import PRESETS
+
+    rec = dict(q_lambda=a.q_lambda)
+    cfg = DQNConfig(**PRESETS["cartpole-dqn-nstep"].overrides)
+    tr = DQNTrainer(cfg, device=dev)
+    for _ in range(a.warmup):
+        tr.train_epoch()
+    assert tr.updates > 0, "the warm-up must reach learning_starts"
+    N, B, C = cfg.num_envs, cfg.batch_size, cfg.buffer_slots
+    filled = min(tr.slots_written, C) * N
+    for sampler in ("uniform", "per"):
+        kw = dict(out=(tr.Xb, tr.act_b, tr.y, None), newest=(tr.cursor - 1) % C)
+        if sampler == "per":
+            kw.update(tree=tr.per.tree, beta=0.7, out=(tr.Xb, tr.act_b, tr.y, tr.idx, tr.w, tr.wmax))
+        for double_q in (True, False):
+            for n in (3, 5, 8):
+                key = f"dqn_targets_{sampler}_{'double_q' if double_q else 'single'}_n{n}"
+                for form, lam in (("nstep", {}), ("lambda", dict(q_lambda=a.q_lambda))):
+                    def targets():
+                        dqn_targets(tr.q.params, tr.target, cfg.hidden, tr.A, tr.ring, filled, cfg.gamma, double_q,
+                                    tr.sample_seed, 7, B, n_step=n, **kw, **lam)
+
+                    targets()
+                    torch.cuda.synchronize()
+                    med, lo, hi = event_us(targets, a.iters, a.reps)
+                    rec[f"{key}_{form}_us"] = med
+                    rec[f"{key}_{form}_us_range"] = [lo, hi]
+                rec[key + "_ratio"] = round(rec[key + "_lambda_us"] / rec[key + "_nstep_us"], 3)
+    for preset in ("cartpole-dqn", "cartpole-dqn-nstep", "cartpole-dqn-lambda"):
+        tr = DQNTrainer(DQNConfig(**PRESETS[preset].overrides), device=dev)
+        for _ in range(a.warmup):
+            tr.train_epoch()
+        times = []
+        for _ in range(3):  # the run-to-run range of the epoch, in this process
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.epochs):
+                tr.train_epoch()
+            torch.cuda.synchronize()
+            times.append(round(1e6 * (time.perf_counter() - t0) / a.epochs, 2))
+        tag = preset[len("cartpole-"):].replace("-", "_")
+        rec[f"epoch_{tag}_us"] = sorted(times)[1]
+        rec[f"epoch_{tag}_us_range"] = [min(times), max(times)]
     return rec
 
 
@@ -515,7 +571,13 @@ def main():
                     help="also measure the Munchausen (soft) targets launch against the hard-max one")
     ap.add_argument("--munchausen-learning", type=int, default=0, metavar="EPOCHS",
                     help="record greedy-return curves of cartpole-dqn-munchausen and -munchausen-qr beside their parents instead")
+    ap.add_argument("--q-lambda", type=float, default=None, metavar="LAM",
+                    help="also measure the lambda-return targets launch at LAM against the n-step one")
+    ap.add_argument("--q-lambda-learning", type=int, default=0, metavar="EPOCHS",
+                    help="record greedy-return curves of cartpole-dqn-lambda beside cartpole-dqn-nstep instead")
     a = ap.parse_args()
+    if a.q_lambda is not None and not 0.0 <= a.q_lambda < 1.0:
+        raise SystemExit("--q-lambda takes a value in [0, 1): 1 is the n-step launch itself")
     if a.atoms and not 2 <= a.atoms <= 64:
         raise SystemExit("--atoms takes 2 .. 64 (CartPole has 2 actions and the wide layer 8 tiles of 16 outputs)")
     if a.quantiles < 0 or 2 * a.quantiles > 16:
@@ -523,8 +585,11 @@ def main():
     if any(k < 1 for k in a.n_step):
         raise SystemExit("--n-step takes values >= 1")
     if (a.prioritized or a.n_step or a.dueling or a.noisy or a.noisy_learning or a.quantiles
-            or a.quantile_learning or a.atoms or a.c51_learning or a.munchausen or a.munchausen_learning) and not a.out:
+            or a.quantile_learning or a.atoms or a.c51_learning or a.munchausen or a.munchausen_learning
+            or a.q_lambda is not None or a.q_lambda_learning) and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "dqn_lambda_learning.jsonl" if a.q_lambda_learning else
+                             "dqn_lambda_bench.jsonl" if a.q_lambda is not None else
                              "dqn_munchausen_learning.jsonl" if a.munchausen_learning else
                              "dqn_munchausen_bench.jsonl" if a.munchausen else
                              "dqn_c51_learning.jsonl" if a.c51_learning else
@@ -553,6 +618,8 @@ def main():
     if a.munchausen_learning:
         return quantile_learning(a, dev, ("cartpole-dqn-nstep", "cartpole-dqn-munchausen", "cartpole-dqn-quantile",
                                           "cartpole-dqn-munchausen-qr"), a.munchausen_learning)
+    if a.q_lambda_learning:
+        return quantile_learning(a, dev, ("cartpole-dqn-nstep", "cartpole-dqn-lambda"), a.q_lambda_learning)
     cfg = DQNConfig(**PRESETS["cartpole-dqn"].overrides)
     tr = DQNTrainer(cfg, device=dev)
     for _ in range(a.warmup):
@@ -615,6 +682,8 @@ def main():
         rec.update(c51_records(a, dev, event_us))
     if a.munchausen:
         rec.update(munchausen_records(a, dev, event_us))
+    if a.q_lambda is not None:
+        rec.update(lambda_records(a, dev, event_us))
     rec.update(iters=a.iters, reps=a.reps, tag=a.tag, device=torch.cuda.get_device_name(0))
     line = json.dumps(rec)
     print(line, flush=True)

@@ -83,6 +83,22 @@ inline bool munchausen_on(double munchausen, double m_tau, double m_clip, bool d
   return true;
 }
 
+// Lambda-return targets (lam = q_lambda): lam in [0, 1]; lam < 1 mixes the 1 .. n-step targets of a walk of 2 to 8
+// steps on the scalar hard-max target, so it goes with neither distributional head nor the soft target.  Returns
+// whether they are on.  A NaN fails the first comparison and is refused.
+inline bool lambda_on(double q_lambda, int64_t n_step, int64_t quantiles, int64_t atoms, double munchausen) {
+  TORCH_CHECK(q_lambda >= 0.0 && q_lambda <= 1.0, "q_lambda must be in [0, 1], got ", q_lambda);
+  if (q_lambda == 1.0) return false;
+  TORCH_CHECK(n_step >= 2 && n_step <= 8, "q_lambda = ", q_lambda, " needs n_step in [2, 8], got ", n_step);
+  TORCH_CHECK(quantiles == 0, "q_lambda = ", q_lambda, " with quantiles = ", quantiles,
+              " is not built: a mixture of return distributions is not the mean of their quantiles");
+  TORCH_CHECK(atoms == 0, "q_lambda = ", q_lambda, " with atoms = ", atoms,
+              " is not built: a mixture of return distributions is not the mean of their atoms");
+  TORCH_CHECK(munchausen == 0.0, "q_lambda = ", q_lambda, " with munchausen = ", munchausen,
+              " is not built: set one of the two");
+  return true;
+}
+
 // Floats of MLPSpec(D, H, A) (+ log_std).
 inline int64_t flat_size(int64_t D, int64_t H, int64_t A, bool log_std = false) {
   return H * D + H + H * H + H + A * H + A + (log_std ? A : 0);

@@ -110,15 +110,18 @@ void per_update(const Tensor& tree, const Tensor& pmax, int64_t L, const Tensor&
 // One launch for every form: a tree selects the prioritised one (it needs beta, idx, w and wmax, which are not
 // looked at without one), n_step > 1 the walk.  Without `newest` there is no walk to check and the slots are one
 // row each (N = 1, newest = 0); with it N is the ring's, and n_step, filled % N and newest are the entry point's
-// to refuse.  munchausen > 0 selects the Munchausen targets (check.h: munchausen_on has the rule).
+// to refuse.  munchausen > 0 selects the Munchausen targets (check.h: munchausen_on has the rule), q_lambda < 1 the
+// lambda-return ones (check.h: lambda_on).
 void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A, const Tensor& obs, const Tensor& nobs,
                  const Tensor& act, const Tensor& rew, const Tensor& done, int64_t filled, double gamma, bool double_q,
                  int64_t sample_key, int64_t update, const Tensor& Xb, const Tensor& act_b, const Tensor& y,
                  const OptT& idx, const OptT& tree, std::optional<double> beta, const OptT& w, const OptT& wmax,
                  int64_t n_step, std::optional<int64_t> newest, const OptT& last, bool dueling, int64_t quantiles,
-                 int64_t atoms, double v_min, double v_max, double munchausen, double m_tau, double m_clip) {
+                 int64_t atoms, double v_min, double v_max, double munchausen, double m_tau, double m_clip,
+                 double q_lambda) {
   TORCH_CHECK(obs.dim() == 3, "ring obs must be [C, N, D]");
   const bool soft = munchausen_on(munchausen, m_tau, m_clip, double_q, dueling, atoms);
+  const bool lam = lambda_on(q_lambda, n_step, quantiles, atoms, munchausen);
   const int64_t D = obs.size(2);
   TORCH_CHECK(H == 64 || H == 128, "hidden size must be 64 or 128");
   TORCH_CHECK(D >= 1 && D <= 16, "obs dim must be in [1, 16]");
@@ -175,6 +178,8 @@ void dqn_targets(const OptT& online, const Tensor& target, int64_t H, int64_t A,
   c.munchausen = soft ? (float)munchausen : 0.f;
   c.m_tau = (float)m_tau;
   c.m_clip = (float)m_clip;
+  // a q_lambda that rounds up to 1.0f is the n-step target to the last bit of fp32: it takes that launch
+  c.q_lambda = lam ? (float)q_lambda : 1.f;
   c.sample_key = (uint64_t)sample_key;
   c.update = (uint64_t)update;
   c.Xb = Xb.data_ptr<float>();
@@ -272,5 +277,5 @@ void register_dqn_ops(pybind11::module_& m) {
         py::arg("w") = py::none(), py::arg("wmax") = py::none(), py::arg("n_step") = 1, py::arg("newest") = py::none(),
         py::arg("last") = py::none(), py::arg("dueling") = false, py::arg("quantiles") = 0, py::arg("atoms") = 0,
         py::arg("v_min") = 0.0, py::arg("v_max") = 0.0, py::arg("munchausen") = 0.0, py::arg("m_tau") = 0.03,
-        py::arg("m_clip") = -1.0);
+        py::arg("m_clip") = -1.0, py::arg("q_lambda") = 1.0);
 }

@@ -56,6 +56,7 @@ struct DqnTargetsCall {
   float v_min, v_max;            // the support of the atoms: z_i = v_min + i * (v_max - v_min) / (NA - 1)
   float munchausen;              // 0: the hard-max targets above; alpha in (0, 1]: Munchausen targets (scalar or quantile)
   float m_tau, m_clip;           // with munchausen > 0: the temperature (> 0) and the lower clip of tau * log pi (< 0)
+  float q_lambda;                // 1: the n-step / one-step targets above; lam in [0, 1): the lambda-return along the walk
 };
 
 // The arguments of rrl_mlp_grad, which has the contract.
@@ -270,10 +271,24 @@ int rrl_dqn_rollout(int env, const float* params, int N, int T, int H, int C, in
 //   y[b][j] = (G + alpha * clamp(tlp(obs[r0])[act[r0]], m_clip, 0)) + disc * boot * sum_a pi[a] * (theta[a][j] - tlp[a])
 // with pi, tlp, theta at nobs[last]; online is not read and only y depends on it.  -3 for munchausen outside [0, 1]
 // and, with munchausen > 0, for m_tau <= 0, m_clip >= 0, double_q, dueling or atoms; munchausen = 0 ignores m_tau
-// and m_clip and launches the hard-max kernels.  Refusals write nothing and are checked in this order.
+// and m_clip and launches the hard-max kernels.
+// q_lambda = lam in [0, 1) (Peng's Q(lambda); DQN(lambda), Daley & Amato 2019): the lambda-return along the same walk,
+// on the scalar hard-max target (plain or dueling nets, either sampler, with or without double_q).  The walk visits
+// r_0 = r0, r_1, .., r_{m-1} = last (r_{k+1} = r_k + N, wrapped at filled; m as above, 1 <= m <= n_step); a*_k is the
+// lowest-index argmax of the selecting net at nobs[r_k] and V_k = Q_target(nobs[r_k], a*_k).  In fp32 and in this order:
+//   gl = gamma * lam;  one = 1 - lam;  g1 = gamma * one;  gb = gamma * (done[last] == 1 ? 0 : 1);  c = 1;  y = 0
+//   for k = 0 .. m - 1:  t = fma(k < m - 1 ? g1 : gb, V_k, rew[r_k]);  y = fma(c, t, y);  c = c * gl
+// i.e. y[b] = sum_k c_k (rew[r_k] + gamma beta_k V_k) with c_k = (gamma lam)^k, beta_k = 1 - lam before the last row
+// and the bootstrap flag on it.  lam -> 1 tends to the n-step target and lam = 0 is the one-step one; q_lambda == 1
+// launches the kernels above.  Only y depends on q_lambda.  -3 for q_lambda outside [0, 1] (a NaN included) and, with
+// q_lambda < 1, for n_step outside [2, 8] (the a*_k of double_q are parked 4 bits each in one word), quantiles != 0,
+// atoms != 0 (a mixture of return distributions is not the mean of their quantiles or atoms) or munchausen > 0; these
+// are judged right after the munchausen rule, so before the -2 of n_step < 1.
+// Refusals write nothing and are checked in this order.
 // -1: a null pointer (online with double_q; idx, w, wmax with a tree; idx with last at n_step == 1); -2: B < 1,
 // filled outside [1, 2^31) or, with a tree, outside [1, L], L outside [1, 2^30]; -3: H not 64 / 128, D outside
-// [1, 16], A < 1 or A + dueling > 16; -2: n_step < 1, N < 1 or filled % N != 0; -4: newest outside [0, filled / N)
+// [1, 16], A < 1 or A + dueling > 16, then the quantile, atom, munchausen and q_lambda rules above; -2: n_step < 1,
+// N < 1 or filled % N != 0; -4: newest outside [0, filled / N)
 int rrl_dqn_targets(const rrl::DqnTargetsCall* c, int num_cu, void* stream);
 
 // ---- per.hip

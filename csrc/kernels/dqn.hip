@@ -23,6 +23,10 @@
 // Both also have a QR instance for the quantile-regression Q-network (heads.h: A * NQ outputs, action-major):
 // it stages and evaluates A * NQ outputs, acts on the argmax of the per-action quantile sums and writes NQ
 // targets per batch row.  NQ travels in an argument block of its own, so the QR = false instances keep theirs.
+//
+// Two more targets kernels change the target alone and share the sampling, the walk and the store tail: the Munchausen
+// (soft) targets, dqn_soft_targets_kernel, and the lambda-returns, dqn_lambda_targets_kernel, which runs every row of the
+// n-step walk through the staged net(s).
 #include <type_traits>
 
 #include "actor_step.h"
@@ -683,6 +687,163 @@ __global__ __launch_bounds__(256, 1) void dqn_soft_targets_kernel(DqnSoftArgsOf<
   }
 }
 
+// ------------------------------------------------------------------ lambda-return targets
+// Peng's Q(lambda) on the replay ring (Kozuno et al. 2021; DQN(lambda), Daley & Amato 2019): the exponentially weighted
+// mix of the 1 .. m-step targets along ONE walk.  The walk is dqn_nstep_walk: it visits r_0 = r0, r_1, .., r_{m-1} =
+// last (r_{k+1} = r_k + N, wrapped at filled), 1 <= m <= n_step.  At every visited row a*_k is the lowest-index argmax
+// of the selecting net at nobs[r_k] (the online net with double_q, else the target net; the advantages of a dueling
+// net) and V_k = Q_target(nobs[r_k], a*_k) (the dueling Q of a dueling net).  With lam = q_lambda in [0, 1), all fp32:
+//   gl = gamma * lam;  one = 1 - lam;  g1 = gamma * one;  gb = gamma * (done[last] == 1 ? 0 : 1)
+//   c = 1;  y = 0
+//   for k = 0 .. m - 1:  t = fma(k < m - 1 ? g1 : gb, V_k, rew[r_k]);  y = fma(c, t, y);  c = c * gl
+// the forward-order sum  y = sum_k c_k (rew[r_k] + gamma beta_k V_k),  c_k = (gamma lam)^k,  beta_k = 1 - lam before
+// the last row and the bootstrap flag on it: nothing per step is stored.  lam -> 1 is the n-step target, lam = 0 the
+// one-step one (an intermediate row of a walk is running, so its own bootstrap flag is 1).
+//
+// How the work is split.  A wave owns 16 batch rows, as in the kernels above, and its lanes walk first: all that is
+// kept of a walk is m (the rows follow from r0 and k).  The forward passes then run in lock-step over k: the wave takes
+// the steps two at a time, k and k + 1, as the two row tiles of ONE pass over the staged weights (soft_forward2: each
+// weight fragment is read from LDS once and feeds the MFMA of either tile, the two accumulate chains cover each
+// other's latency), so a walk of m rows costs ceil(m / 2) passes over the LDS image, not m.  The loop ends, for the
+// whole wave at once, when no lane has a step left, and runs the one-tile body when no lane has a step k + 1.  A lane
+// whose walk is shorter stays in the MFMAs on a zero tile and its visit is skipped; either tile's result is
+// policy_forward's bit for bit, so a row's target does not depend on the walks of its neighbours.
+//
+// double_q: one LDS image at a time, as above.  The online pass runs the same loop and packs a*_k into 4 bits each
+// (n_step <= 8 and A <= 16: one word), parks the word in y[b] as bits, m - 1 in act_b[b] and, prioritised, the row in
+// idx[b]; the target pass reads them back in lane group 0 (the thread that wrote them), clamps them (m - 1 to the walk
+// lengths the ring and n_step allow, each a* into [0, A)), and hands them to the other lane groups by a lane broadcast.
+// The walk and the tree descent happen once per batch row.
+// Xb, act_b, idx, last, w and wmax are those of dqn_targets_kernel<.., NSTEP = true, ..>, bit for bit.
+struct DqnLambdaArgs : DqnNStepArgs {
+  float lam = 0.f;  // q_lambda, in [0, 1)
+};
+
+// The Q-values of the m rows of one walk, two steps per pass over the LDS image: visit(k, r_k, q) for k < m, ascending.
+template <int HT, class Visit>
+RRL_DEV void lambda_rows(const float* __restrict__ lds, const DqnLambdaArgs& p, uint32_t r0, int m, int AO,
+                         Visit&& visit) {
+  const int g = lane_id() >> 4;
+  const int kr_last = (p.D + 3) >> 2;
+  uint32_t ra = r0;  // r_k; N <= filled and r_k < filled, so one subtraction wraps the sum
+  for (int k = 0; k < p.n_step; k += 2) {
+    const bool on_a = k < m, on_b = k + 1 < m;
+    if (__ballot(on_a) == 0) break;  // wave-uniform: every walk of the tile is through
+    uint32_t rb = ra + p.N;
+    if (rb >= p.filled) rb -= p.filled;
+    floatx4 xa[1], xb[1];
+    const float* row_a = p.nobs + (size_t)ra * p.D;
+    const float* row_b = p.nobs + (size_t)rb * p.D;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int f = 4 * i + g;
+      xa[0][i] = (on_a && f < p.D) ? row_a[f] : 0.f;
+      xb[0][i] = (on_b && f < p.D) ? row_b[f] : 0.f;
+    }
+    float qa[kMaxAct], qb[kMaxAct];
+    if (__ballot(on_b) != 0) {  // wave-uniform again: all 64 lanes are in the MFMAs of either body
+      soft_forward2<HT>(lds, xa, xb, kr_last, AO, qa, qb);
+    } else {
+      policy_forward<1, HT>(lds, xa, kr_last, AO, qa);
+#pragma unroll
+      for (int a = 0; a < kMaxAct; ++a) qb[a] = 0.f;
+    }
+    if (on_a) visit(k, ra, qa);
+    if (on_b) visit(k + 1, rb, qb);
+    ra = rb + p.N;
+    if (ra >= p.filled) ra -= p.filled;
+  }
+}
+
+template <int HT, bool PER, bool DUEL>
+__global__ __launch_bounds__(256, 1) void dqn_lambda_targets_kernel(DqnLambdaArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int l = lane_id();
+  const int j = l & 15, g = l >> 4;
+  const int wave = threadIdx.x >> 6;
+  const int AO = p.A + (DUEL ? 1 : 0);
+  const float gl = p.gamma * p.lam;
+  const float g1 = p.gamma * (1.f - p.lam);
+
+  if (p.double_q) {
+    stage_net<1, HT>(lds, p.online, p.D, AO, false);
+    __syncthreads();
+    for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
+      const int b = base + 16 * wave + j;
+      const bool ok = b < p.B;
+      uint32_t r = 0;
+      int m = 0;  // a row past B visits nothing
+      if (ok) {
+        r = PER ? per_sample_row(b, p) : dqn_sample_row(b, p);
+        m = dqn_nstep_walk(r, p).m;
+      }
+      uint32_t picks = 0;
+      lambda_rows<HT>(lds, p, r, m, AO, [&](int k, uint32_t, const float (&q)[kMaxAct]) {
+        picks |= (uint32_t)argmax_first(p.A, q) << (4 * k);
+      });
+      if (ok && g == 0) {
+        p.y[b] = __uint_as_float(picks);
+        p.act_b[b] = m - 1;
+        if (PER) p.idx[b] = (int)r;
+      }
+    }
+    __syncthreads();  // every wave is done with the online image
+  }
+  stage_net<1, HT>(lds, p.target, p.D, AO, false);
+  __syncthreads();
+  for (int base = blockIdx.x * 64; base < p.B; base += gridDim.x * 64) {
+    const int b = base + 16 * wave + j;
+    const bool ok = b < p.B;
+    uint32_t r = 0, picks = 0;
+    int m = 0;
+    if (p.double_q) {
+      // parked by this wave's lane group 0, which reads it back: the walk is not repeated.  m - 1 is clamped to what
+      // n_step and the ring allow (so r_k stays inside the ring and 4 k inside the word)
+      uint32_t m1 = 0;
+      if (ok && g == 0) {
+        r = PER ? min((uint32_t)p.idx[b], p.filled - 1u) : dqn_sample_row(b, p);
+        m1 = min((uint32_t)p.act_b[b], min((uint32_t)p.n_step, p.slots) - 1u);
+        picks = __float_as_uint(p.y[b]);
+      }
+      r = __shfl(r, j, 64);
+      picks = __shfl(picks, j, 64);
+      m = ok ? 1 + (int)__shfl(m1, j, 64) : 0;
+    } else if (ok) {
+      r = PER ? per_sample_row(b, p) : dqn_sample_row(b, p);
+      m = dqn_nstep_walk(r, p).m;
+    }
+    const uint32_t last = ok ? dqn_nstep_last(r, (uint32_t)(m - 1), p) : 0u;
+    const float gb = p.gamma * ((ok && p.done[last] == 1.f) ? 0.f : 1.f);
+    float c = 1.f, y = 0.f;
+    lambda_rows<HT>(lds, p, r, m, AO, [&](int k, uint32_t rk, const float (&q)[kMaxAct]) {
+      // a parked a* comes back from memory: the clamp keeps it among the A outputs
+      const int astar = p.double_q ? min((int)((picks >> (4 * k)) & 15u), p.A - 1) : argmax_first(p.A, q);
+      float V;
+      if constexpr (DUEL) V = dueling_q(p.A, q, astar);
+      else V = pick_logit(p.A, q, astar);
+      const float t = fmaf(k < m - 1 ? g1 : gb, V, p.rew[rk]);
+      y = fmaf(c, t, y);
+      c = c * gl;
+    });
+    if (ok) {
+      for (int f = g; f < p.D; f += 4) p.Xb[(size_t)b * p.D + f] = p.obs[(size_t)r * p.D + f];
+      if (g == 0) {
+        p.y[b] = y;
+        if (p.last != nullptr) p.last[b] = (int)last;
+        p.act_b[b] = p.act[r];
+        if (p.idx != nullptr) p.idx[b] = (int)r;
+        if (PER) {
+          const float leaf = p.tree[p.P2 + r], total = p.tree[1];
+          // a walk on a sound tree ends on a positive leaf; anything else weighs like the uniform sampler
+          const float wb = (leaf > 0.f && total > 0.f) ? powf((float)p.filled * leaf / total, -p.beta) : 1.f;
+          p.w[b] = wb;
+          atomicMax(p.wmax, __float_as_int(wb));
+        }
+      }
+    }
+  }
+}
+
 }  // namespace rrl
 
 using namespace rrl;
@@ -887,6 +1048,32 @@ static int dispatch_soft_targets(const DqnNStepArgs& a, const DqnTargetsCall& c,
   }
 }
 
+// The lambda-return instances of (H, PER, DUEL): the n-step block with q_lambda behind it.
+template <int HT, bool PER, bool DUEL>
+static int launch_lambda_targets(const DqnNStepArgs& a, float lam, int grid, hipStream_t s) {
+  DqnLambdaArgs q;
+  static_cast<DqnNStepArgs&>(q) = a;
+  q.lam = lam;
+  raise_lds_limit<dqn_lambda_targets_kernel<HT, PER, DUEL>>();
+  const size_t bytes = (size_t)LdsNet<1, HT>::floats(a.A + (DUEL ? 1 : 0)) * sizeof(float);
+  hipLaunchKernelGGL((dqn_lambda_targets_kernel<HT, PER, DUEL>), dim3(grid), dim3(256), bytes, s, q);
+  return (int)hipGetLastError();
+}
+
+static int dispatch_lambda_targets(const DqnNStepArgs& a, float lam, int H, bool per, bool duel, int grid,
+                                   hipStream_t s) {
+  switch ((per ? 4 : 0) | (duel ? 2 : 0) | (H == 128 ? 1 : 0)) {
+    case 0: return launch_lambda_targets<4, false, false>(a, lam, grid, s);
+    case 1: return launch_lambda_targets<8, false, false>(a, lam, grid, s);
+    case 2: return launch_lambda_targets<4, false, true>(a, lam, grid, s);
+    case 3: return launch_lambda_targets<8, false, true>(a, lam, grid, s);
+    case 4: return launch_lambda_targets<4, true, false>(a, lam, grid, s);
+    case 5: return launch_lambda_targets<8, true, false>(a, lam, grid, s);
+    case 6: return launch_lambda_targets<4, true, true>(a, lam, grid, s);
+    default: return launch_lambda_targets<8, true, true>(a, lam, grid, s);
+  }
+}
+
 static int dqn_targets_grid(int B, int num_cu) {
   int grid = (B + 63) / 64;
   const int cap = num_cu > 0 ? num_cu : 256;
@@ -916,6 +1103,12 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
   const bool soft = c->munchausen > 0.f;
   if (!(c->munchausen >= 0.f && c->munchausen <= 1.f)) return -3;
   if (soft && (!(c->m_tau > 0.f) || !(c->m_clip < 0.f) || c->double_q || duel || c->atoms != 0)) return -3;
+  // lambda-returns: q_lambda in [0, 1]; below 1 the walk has 2 to 8 steps (the parked a* are 4 bits each in one word)
+  // and the target is the scalar hard-max one: a mixture of return distributions is not the mean of their quantiles
+  // or atoms, and the soft target has no a* to mix
+  const bool lam_on = c->q_lambda < 1.f;
+  if (!(c->q_lambda >= 0.f && c->q_lambda <= 1.f)) return -3;
+  if (lam_on && (c->n_step < 2 || c->n_step > 8 || NQ != 0 || c->atoms != 0 || soft)) return -3;
   if (c->n_step < 1 || c->N < 1 || c->filled % c->N != 0) return -2;
   if (c->newest < 0 || c->newest >= c->filled / c->N) return -4;
   DqnNStepArgs a;
@@ -942,7 +1135,9 @@ extern "C" int rrl_dqn_targets(const DqnTargetsCall* c, int num_cu, void* stream
   }
   const int grid = dqn_targets_grid(c->B, num_cu);
   int rc;
-  if (soft) {
+  if (lam_on) {
+    rc = dispatch_lambda_targets(a, c->q_lambda, c->H, per, duel, grid, s);
+  } else if (soft) {
     rc = NQ > 0 ? dispatch_soft_targets<true>(a, *c, per, nstep, grid, s)
                 : dispatch_soft_targets<false>(a, *c, per, nstep, grid, s);
   } else if (tpa > 0) {

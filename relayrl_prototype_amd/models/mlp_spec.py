@@ -69,6 +69,29 @@ def munchausen_on(munchausen: float, m_tau: float, m_clip: float, double_q: bool
     return True
 
 
+def lambda_on(q_lambda: float, n_step: int = 1, quantiles: int = 0, atoms: int = 0, munchausen: float = 0.0) -> bool:
+    """Whether the lambda-return targets are on (``q_lambda`` < 1), and whether the kernels have the combination:
+    ``q_lambda`` in [0, 1]; below 1 it mixes the 1 .. n-step targets of a walk of ``n_step`` in [2, 8] steps on the scalar
+    hard-max target.  A mixture of return distributions is not the mean of their quantiles or atoms and the soft target
+    has no argmax to mix, so those are refused.  Raises ``ValueError`` naming the fields otherwise."""
+    lam = float(q_lambda)
+    if not 0.0 <= lam <= 1.0:  # a NaN fails it too
+        raise ValueError(f"q_lambda must be in [0, 1], got {q_lambda}")
+    if lam == 1.0:
+        return False
+    if not 2 <= int(n_step) <= 8:
+        raise ValueError(f"q_lambda = {lam} needs n_step in [2, 8], got {n_step}")
+    if int(quantiles):
+        raise ValueError(f"q_lambda = {lam} with quantiles = {quantiles} is not built: a mixture of return "
+                         "distributions is not the mean of their quantiles")
+    if int(atoms):
+        raise ValueError(f"q_lambda = {lam} with atoms = {atoms} is not built: a mixture of return distributions is "
+                         "not the mean of their atoms")
+    if float(munchausen) > 0.0:
+        raise ValueError(f"q_lambda = {lam} with munchausen = {munchausen} is not built: set one of the two")
+    return True
+
+
 @dataclass(frozen=True)
 class MLPSpec:
     """Linear(D,H)-ReLU-Linear(H,H)-ReLU-Linear(H,A) [+ log_std(A)]."""

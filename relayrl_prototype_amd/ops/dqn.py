@@ -7,7 +7,8 @@
 * ``dqn_sample_rows_ref`` / ``dqn_nstep_walk_ref`` / ``dqn_targets_ref``: the oracles the kernel is held to.
 
 ``n_step > 1`` forms the n-step return at sample time: the sampled row walks forward through the ring
-(same env, next slot) before the bootstrap, see ``dqn_nstep_walk_ref``.
+(same env, next slot) before the bootstrap, see ``dqn_nstep_walk_ref``.  ``q_lambda < 1`` mixes the 1 .. m-step targets
+of that walk into the lambda-return, see ``dqn_lambda_y_ref``.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ import torch
 
 from . import philox
 from . import reference as ref
-from ..models.mlp_spec import MLPSpec, c51_outputs, munchausen_on, q_outputs
+from ..models.mlp_spec import MLPSpec, c51_outputs, lambda_on, munchausen_on, q_outputs
 
 
 class ReplayRing(NamedTuple):
@@ -173,7 +174,7 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
                     seed: int, update: int, B: int, dtype=torch.float32, tree=None, beta: Optional[float] = None,
                     n_step: int = 1, newest: Optional[int] = None, dueling: bool = False, quantiles: int = 0,
                     atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0, munchausen: float = 0.0,
-                    m_tau: float = 0.03, m_clip: float = -1.0):
+                    m_tau: float = 0.03, m_clip: float = -1.0, q_lambda: float = 1.0):
     """-> ``(Xb [B, D], act_b [B] int32, y [B], idx [B] int64)`` in ``dtype``;
     ``y = rew + gamma * (done == 1 ? 0 : 1) * Q_target(nobs, a*)`` with ``a*`` the lowest-index argmax of the
     target (``double_q`` false) or online net.  With ``tree`` (the priority sum tree of ops/per.py) the rows
@@ -206,10 +207,15 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
 
     ``a`` ascending (a scalar net has ``theta = q`` and one target per row).  The bonus is added once, for the sampled
     transition, whatever ``n_step`` is; ``online`` is not read.  float64 is the oracle, float32 repeats the kernel's
-    order."""
+    order.
+
+    ``q_lambda`` = lam in [0, 1) (plain and dueling nets, ``n_step`` in [2, 8]; ``lambda_on`` has the rule): the
+    lambda-return along the same walk, ``dqn_lambda_y_ref``.  Only ``y`` differs from the n-step call; ``q_lambda = 1`` is
+    that call."""
     D = ring.obs.shape[-1]
     dev = ring.obs.device
     soft = munchausen_on(munchausen, m_tau, m_clip, double_q, dueling, atoms)
+    lam_on = lambda_on(q_lambda, n_step, quantiles, atoms, munchausen)
     NA = check_atoms(A, atoms, v_min, v_max, dueling, quantiles) if atoms else 0
     NQ = check_quantiles(A, quantiles, dueling)
     _check_q_nets(online if double_q else None, target, D, H, A, dueling, NQ, NA)
@@ -231,7 +237,10 @@ def dqn_targets_ref(online, target, H: int, A: int, ring: ReplayRing, filled: in
                          for x in dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)[:3])
     nobs = ring.nobs.reshape(-1, D)[last].to(dtype)
     boot = (ring.done.reshape(-1)[last] != 1).to(dtype)
-    if soft:
+    if lam_on:
+        y = dqn_lambda_y_ref(online, target, H, A, ring, filled, gamma, double_q, rows, newest, n_step, q_lambda,
+                             dueling, dtype)
+    elif soft:
         AO, n = q_outputs(A, False, NQ), max(NQ, 1)
         tgt = target.to(dtype)
         mean = (lambda out: ref.quantile_q(out, A, NQ) / torch.tensor(float(NQ), dtype=dtype)) if NQ else (lambda out: out)
@@ -290,11 +299,41 @@ def _q_and_astar(online, target, nobs, D, H, A, double_q, dueling, dtype):
     return (ref.dueling_q(out_t, A) if dueling else out_t), astar
 
 
+def dqn_lambda_y_ref(online, target, H: int, A: int, ring: ReplayRing, filled: int, gamma: float, double_q: bool, rows,
+                     newest: int, n_step: int, q_lambda: float, dueling: bool = False, dtype=torch.float32):
+    """The lambda-return targets ``y [B]`` of the sampled ring rows ``rows`` (Peng's Q(lambda) along the n-step walk).
+    The walk (``dqn_nstep_walk_ref``) visits ``r_0 = r0, .., r_{m-1} = last``, ``r_{k+1} = r_k + N`` wrapped at
+    ``filled``; ``a*_k`` is the lowest-index argmax of the selecting net at ``nobs[r_k]`` and ``V_k`` the target net's Q of
+    it there.  In ``dtype`` and in the kernel's forward order (the kernel fuses each multiply-add):
+
+        gl = gamma * lam; g1 = gamma * (1 - lam); gb = gamma * (done[last] == 1 ? 0 : 1); c = 1; y = 0
+        for k in 0 .. m - 1:  t = (g1 if k < m - 1 else gb) * V_k + rew[r_k];  y = y + c * t;  c = c * gl
+    """
+    D, N = ring.obs.shape[-1], int(ring.act.shape[1])
+    dev = ring.obs.device
+    m = torch.from_numpy(dqn_nstep_walk_ref(rows, ring, filled, newest, n_step, gamma, dtype)[3]).to(dev)
+    r = torch.from_numpy(np.asarray(rows, np.int64)).to(dev)
+    last = (r + (m - 1) * N) % filled
+    g, lam = torch.tensor(float(gamma), dtype=dtype), torch.tensor(float(q_lambda), dtype=dtype)
+    gl, g1 = g * lam, g * (1 - lam)
+    gb = g * (ring.done.reshape(-1)[last] != 1).to(dtype)
+    rew, nobs = ring.rew.reshape(-1).to(dtype), ring.nobs.reshape(-1, D).to(dtype)
+    c, y = torch.ones((), dtype=dtype), torch.zeros(len(r), dtype=dtype, device=dev)
+    for k in range(int(m.max())):
+        q_t, astar = _q_and_astar(online, target, nobs[r], D, H, A, double_q, dueling, dtype)
+        t = torch.where(k < m - 1, g1, gb) * q_t.gather(-1, astar.unsqueeze(-1)).squeeze(-1) + rew[r]
+        y = torch.where(k < m, y + c * t, y)
+        c = c * gl
+        r = r + N
+        r = torch.where(r >= filled, r - filled, r)
+    return y
+
+
 def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A: int, ring: ReplayRing, filled: int,
                 gamma: float, double_q: bool, seed: int, update: int, B: int, out=None, dtype=torch.float32,
                 tree=None, beta: Optional[float] = None, n_step: int = 1, newest: Optional[int] = None,
                 dueling: bool = False, quantiles: int = 0, atoms: int = 0, v_min: float = 0.0, v_max: float = 0.0,
-                munchausen: float = 0.0, m_tau: float = 0.03, m_clip: float = -1.0):
+                munchausen: float = 0.0, m_tau: float = 0.03, m_clip: float = -1.0, q_lambda: float = 1.0):
     """Sample, gather and TD target in one launch -> ``(Xb, act_b, y, idx)``; ``out`` = the four tensors to
     write into (``idx`` int32 on the GPU, or None to skip it).  CPU tensors take the torch reference in
     ``dtype``; a GPU tensor without the extension raises.
@@ -323,12 +362,19 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
     ``munchausen`` = alpha in (0, 1] selects the Munchausen instances (``dqn_targets_ref`` has the semantics; ``m_tau`` > 0
     the temperature, ``m_clip`` < 0 the clip of the bonus): the target net alone is staged and evaluated at ``obs[r0]``
     and ``nobs[last]``, on a scalar or a quantile net, and only ``y`` differs from the hard-max launch.  It is refused
-    with ``double_q``, ``dueling`` or ``atoms``; ``munchausen = 0`` is the hard-max launch as it was."""
+    with ``double_q``, ``dueling`` or ``atoms``; ``munchausen = 0`` is the hard-max launch as it was.
+
+    ``q_lambda`` = lam in [0, 1) selects the lambda-return instances (``dqn_lambda_y_ref`` has the semantics): every row
+    the n-step walk visits goes through the staged net(s) and ``y`` mixes the 1 .. m-step targets with weights
+    ``(1 - lam) lam^k``; only ``y`` differs from the n-step launch.  It needs ``n_step`` in [2, 8], composes with
+    ``double_q``, ``dueling`` and the tree, and is refused with ``quantiles``, ``atoms`` or ``munchausen``; ``q_lambda = 1``
+    is the n-step (or one-step) launch as it was."""
     from . import use_hip, hip
 
     per = tree is not None
     dueling = bool(dueling)
     soft = munchausen_on(munchausen, m_tau, m_clip, double_q, dueling, atoms)
+    lam_on = lambda_on(q_lambda, n_step, quantiles, atoms, munchausen)
     NA = check_atoms(A, atoms, v_min, v_max, dueling, quantiles) if atoms else 0
     NQ = check_quantiles(A, quantiles, dueling) if quantiles else 0
     _check_q_nets(online if double_q else None, target, ring.obs.shape[-1], H, A, dueling, NQ, NA)
@@ -347,7 +393,7 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
         raise ValueError("at n_step = 1 last is idx: it cannot be written without idx")
     if not use_hip(target):
         res = dqn_targets_ref(online, target, H, A, ring, filled, gamma, double_q, seed, update, B, dtype, tree, beta,
-                              n_step, newest, dueling, NQ, NA, v_min, v_max, munchausen, m_tau, m_clip)
+                              n_step, newest, dueling, NQ, NA, v_min, v_max, munchausen, m_tau, m_clip, q_lambda)
         if out is None:
             return res
         if n_step == 1:
@@ -370,11 +416,13 @@ def dqn_targets(online: Optional[torch.Tensor], target: torch.Tensor, H: int, A:
         raise ValueError("the prioritised form writes idx: it cannot be skipped")
     w, wmax = out[4:6] if per else (None, None)
     # the binding's optionals (tree, beta, w, wmax, n_step, newest, last, dueling, quantiles, atoms, v_min, v_max,
-    # munchausen, m_tau, m_clip) in its order: a positional call parses faster than a keyword one, and this is the one
-    # place that makes it; a hard-max call passes what it always passed
-    tail = (NA, float(v_min), float(v_max)) if NA or soft else ()
-    if soft:
+    # munchausen, m_tau, m_clip, q_lambda) in its order: a positional call parses faster than a keyword one, and this is
+    # the one place that makes it; a hard-max call passes what it always passed
+    tail = (NA, float(v_min), float(v_max)) if NA or soft or lam_on else ()
+    if soft or lam_on:
         tail += (float(munchausen), float(m_tau), float(m_clip))
+    if lam_on:
+        tail += (float(q_lambda),)
     hip().dqn_targets(online if double_q else None, target, int(H), int(A), ring.obs, ring.nobs, ring.act, ring.rew,
                       ring.done, int(filled), float(gamma), bool(double_q), int(seed), int(update), *out[:4], tree,
                       float(beta) if per else None, w, wmax, n_step, newest,

@@ -76,7 +76,16 @@ net).  The soft target has no argmax, so ``double_q`` must be off and no selecti
 the evaluator, the gradient heads, Adam and the tree are those of the hard-max run.  It composes with ``prioritized``,
 ``n_step``, ``noisy`` and ``quantiles`` and is refused with ``double_q``, ``dueling`` and ``atoms``.
 
-Left for later: Munchausen targets with the dueling or the categorical head, a bonus per step of the n-step walk, a
+``q_lambda = lam < 1`` (with ``n_step`` in [2, 8]) is the lambda-return of Peng's Q(lambda) (Kozuno et al. 2021; DQN(lambda),
+Daley & Amato 2019), again a change of the target alone: ``dqn_targets`` runs EVERY row of the n-step walk through the
+staged net(s) and mixes the 1 .. m-step targets of the walk with weights ``(1 - lam) lam^k`` (``ops.dqn.dqn_lambda_y_ref``),
+where ``n_step`` alone cuts at one length.  ``lam = 0`` is the one-step target and ``lam -> 1`` the n-step one;
+``q_lambda = 1`` launches the kernels it always launched.  It composes with ``double_q``, ``prioritized``, ``dueling`` and
+``noisy`` and is refused with ``quantiles``, ``atoms`` (a mixture of return distributions is not the mean of their
+quantiles or atoms) and ``munchausen``.
+
+Left for later: lambda-returns on the distributional or Munchausen targets, Retrace-style traces (the ring stores no
+behaviour probabilities), Munchausen targets with the dueling or the categorical head, a bonus per step of the n-step walk, a
 Boltzmann actor, quantiles with the dueling head, more than 16 outputs, per-env noise, several ranks, hipGraph
 capture, serving the policy to agents (the trainer exposes no ``learner``, so a TrainingServer engine publishes no
 model).
@@ -92,7 +101,7 @@ from ..algorithms.core import FlatNet
 from ..ops import GradHead, MLPSpec, ReplayRing, dqn_rollout, dqn_rollout_grid, dqn_targets, grad_slabs, hip, mlp_grad
 from ..ops import PriorityTree, per_insert, per_update
 from ..ops import adam_step, noisy_compose, noisy_grad, noisy_sigma_init
-from ..models.mlp_spec import c51_outputs, munchausen_on
+from ..models.mlp_spec import c51_outputs, lambda_on, munchausen_on
 from ..parallel.comm import Comm
 from .rollout_learn import episode_metrics
 from .vec_trainer import CONTINUOUS_DEVICE_ENVS, DEVICE_ENVS
@@ -150,6 +159,7 @@ class DQNConfig:
     munchausen: float = 0.0         # Munchausen targets: the scale alpha of the log-policy bonus (0: hard-max targets)
     m_tau: float = 0.03             # their entropy temperature, > 0
     m_clip: float = -1.0            # the lower clip of m_tau * log pi in the bonus, < 0
+    q_lambda: float = 1.0           # lambda-returns along the n-step walk (1: the n-step target; < 1 needs n_step in [2, 8])
 
     def __post_init__(self):
         self.dueling = _as_bool("dueling", self.dueling)
@@ -194,13 +204,14 @@ class DQNConfig:
             if self.noisy:
                 raise ValueError(f"atoms = {na} with noisy = True is not built: the noisy layers hold at most 16 "
                                  "outputs; set one of the two")
-        for k in ("munchausen", "m_tau", "m_clip"):
+        for k in ("munchausen", "m_tau", "m_clip", "q_lambda"):
             try:
                 setattr(self, k, float(getattr(self, k)))
             except (TypeError, ValueError):
                 raise ValueError(f"{k} must be a number, got {getattr(self, k)!r}") from None
         self.double_q = _as_bool("double_q", self.double_q)  # "false" must switch it off for the soft target
         munchausen_on(self.munchausen, self.m_tau, self.m_clip, self.double_q, self.dueling, self.atoms)
+        lambda_on(self.q_lambda, self.n_step, self.quantiles, self.atoms, self.munchausen)
         if not 1 <= self.n_step <= int(self.buffer_slots):
             raise ValueError(f"n_step must be in [1, buffer_slots = {self.buffer_slots}], got {self.n_step}")
         self.prioritized = _as_bool("prioritized", self.prioritized)
@@ -292,6 +303,8 @@ class DQNTrainer:
         # what only the targets take; a hard-max trainer passes what it always passed
         self._soft_kw = (dict(munchausen=cfg.munchausen, m_tau=cfg.m_tau, m_clip=cfg.m_clip) if cfg.munchausen > 0
                          else {})
+        if cfg.q_lambda < 1.0:  # the lambda-return kernel; never together with the soft target
+            self._soft_kw = dict(q_lambda=cfg.q_lambda)
         self.target = self.q.params.clone()
         self.theta = None
         if cfg.noisy:  # theta = [mu; sigma] with Adam state of 2P; the net's own tensors are its mu half
@@ -530,6 +543,11 @@ class DQNTrainer:
         if mine != theirs:
             raise ValueError(f"this trainer has munchausen={mine}; the checkpoint has munchausen={theirs}: build the "
                              "trainer with the checkpoint's munchausen setting")
+        mine, theirs = float(self.cfg.q_lambda), sd.get("cfg", {}).get("q_lambda")
+        theirs = 1.0 if theirs is None else float(theirs)  # absent: the n-step target
+        if mine != theirs:
+            raise ValueError(f"this trainer has q_lambda={mine}; the checkpoint has q_lambda={theirs}: build the "
+                             "trainer with the checkpoint's q_lambda setting")
         mine = bool(self.cfg.dueling)
         theirs = sd.get("cfg", {}).get("dueling")  # absent in a checkpoint from before the dueling head: plain
         if got != self.q.P or (theirs is not None and bool(theirs) != mine):

@@ -147,6 +147,16 @@ PRESETS: Dict[str, Preset] = {
                 "double_q": False, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
                 "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 3, "quantiles": 8,
                 "munchausen": 0.9}),
+    "cartpole-dqn-lambda": Preset(
+        "cartpole-dqn-lambda", "cartpole-dqn-nstep with lambda-returns (Peng's Q(lambda); DQN(lambda), Daley & Amato 2019): "
+        "the walk has up to 5 steps and the target mixes its 1 .. 5-step targets with weights (1 - lam) lam^k, every "
+        "visited row going through the staged nets of one fused targets kernel; untuned (--set q_lambda=0.7 --set "
+        "n_step=5 on any scalar DQN preset is the same mechanism)",
+        "vec", {"env": "CartPole-v1", "algo": "dqn", "num_envs": 1024, "rollout_len": 4, "buffer_slots": 256,
+                "batch_size": 1024, "updates_per_epoch": 4, "gamma": 0.99, "q_lr": 5e-4, "eps_start": 1.0,
+                "eps_end": 0.05, "eps_decay_epochs": 500, "learning_starts": 8192, "target_update_every": 100,
+                "double_q": True, "huber_delta": 1.0, "prioritized": True, "per_alpha": 0.6, "per_beta_start": 0.4,
+                "per_beta_end": 1.0, "per_beta_epochs": 500, "per_eps": 1e-3, "n_step": 5, "q_lambda": 0.7}),
 }
 
 
